@@ -1,6 +1,6 @@
 """Benchmark of the 2D-3D matching hot path (BASELINE.json metric: query frames/sec @ 7k x 4800, d256).
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload c2|c1|c4] [--no-cpu-baseline]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload c2|c1|c4] [--no-cpu-baseline] [--dump-outputs DIR]
 
 One process per GPU over RCCL: for N > 1 either ``torch.distributed.run`` starts the ranks, or -- when ``python bench.py
 --gpus N`` is run directly -- this process starts them itself as children (``onepose_st_amd/launch.py``; the parent imports
@@ -62,6 +62,68 @@ def attn_apply_flops(n_tokens: int, fused_kv: bool, n_layers: int = 6, C: int = 
     if fused_kv:
         per_tok += (n_layers - 1) / n_layers * (4.0 * C * C + 2.0 * C * D)
     return float(n_tokens) * per_tok
+
+
+DUMP_BYTES_MAX = 64 << 20          # --dump-outputs: all files together
+DUMP_CONF_ENTRIES = 1 << 22        # conf_matrix entries written (16 MB f32): the whole matrix when it fits, else that many entries of whole rows
+DUMP_SEED = 0                      # the fixed draw of the conf_matrix rows (and of the matches, should the lists alone exceed the budget)
+MATCH_KEYS = ("b_ids", "i_ids", "j_ids", "mconf", "mkpts_3d_db", "mkpts_query_c", "mkpts_query_f", "expec_f", "m_bids", "gt_mask")
+
+
+def _host_array(t):
+    """float32 for float32 / bool / half tensors, float64 for integers and float64 (exact for ids below 2^53)"""
+    import torch
+
+    t = t.detach().cpu()
+    if t.dtype == torch.bool or (t.is_floating_point() and t.dtype != torch.float64):
+        return t.float().numpy()
+    return t.double().numpy()
+
+
+def output_arrays(data: dict, poses=()) -> dict:
+    """What a caller of the timed path receives for one step, as float32 / float64 arrays of at most DUMP_BYTES_MAX bytes in all: the match
+    lists of the model's ``data`` (MATCH_KEYS), ``conf_matrix`` (whole, or ``conf_matrix_rows``: DUMP_CONF_ENTRIES // M of its B * N rows
+    drawn with DUMP_SEED, with their flat row numbers in ``conf_matrix_row_index``; the lazy form was never computed and is left out) and
+    the step's poses ``(pose [B, 3, 4], inliers, status)`` from the PnP pool."""
+    import numpy as np
+    import torch
+
+    out = {k: _host_array(data[k]) for k in MATCH_KEYS if isinstance(data.get(k), torch.Tensor)}
+    conf = data.get("conf_matrix")
+    if isinstance(conf, torch.Tensor):
+        B, N, M = conf.shape
+        if B * N * M <= DUMP_CONF_ENTRIES:
+            out["conf_matrix"] = _host_array(conf)
+        else:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B * N, size=max(1, DUMP_CONF_ENTRIES // M), replace=False))
+            out["conf_matrix_rows"] = _host_array(conf.reshape(B * N, M)[torch.from_numpy(rows).to(conf.device)])
+            out["conf_matrix_row_index"] = rows.astype(np.float64)
+    if poses:
+        out["pose"] = np.stack([np.asarray(p[0], dtype=np.float64) for p in poses])
+        out["pnp_inliers"] = np.array([p[1] for p in poses], dtype=np.float64)
+        out["pnp_status"] = np.array([p[2] for p in poses], dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES_MAX and "i_ids" in out:
+        # only a very large batch gets here: the same seeded draw of matches from every list, their positions in `match_index`
+        K = len(out["i_ids"])
+        per_match = sum(out[k].nbytes for k in MATCH_KEYS if k in out) / max(K, 1) + 8
+        keep = int((DUMP_BYTES_MAX - (total - sum(out[k].nbytes for k in MATCH_KEYS if k in out))) // per_match)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(K, size=max(0, min(K, keep)), replace=False))
+        for k in MATCH_KEYS:
+            if k in out:
+                out[k] = out[k][pick]
+        out["match_index"] = pick.astype(np.float64)
+    return out
+
+
+def write_outputs(dirname: str, arrays: dict) -> dict:
+    """``dirname/<name>.npy`` for every array; -> what was written (for the result line)"""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": dirname, "files": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def rank_report(rows, world: int, frames_expected: int, poses_expected: int = -1) -> dict:
@@ -130,7 +192,13 @@ def main():
     ap.add_argument("--no-side-legs", action="store_true",
                     help="skip the BASELINE config 3 (32 frames per step) and config 4 (15k x 19 200) side legs that a default c2 run appends to its line")
     ap.add_argument("--cpu-seconds", type=float, default=40.0, help="budget of the CPU baseline leg (all-core, full-forward and single-thread samples)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the contract's region computed in its last step (rank 0's frames: match lists, "
+                         "conf_matrix or a fixed sample of its rows, poses) as DIR/<name>.npy in float32 / float64, at most 64 MB in all "
+                         "(bench.output_arrays); the inputs depend on the arguments alone, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 without a launcher: this process becomes the driver and starts one child per GPU (it never touches the GPU
     #      itself and never exec's; the reference fans out from its driver too, inference_OnePosePlus.py:81-98) --------------
@@ -387,10 +455,13 @@ def main():
     own_done = [0, 0]       # frames finished / poses joined by this rank INSIDE the last timed region (measured, not args.steps * B)
     HOT_STEPS = int(os.environ.get("OPHIP_BENCH_HOT_STEPS", "32"))          # untimed matcher-only frames right before every timed region (see timed_region)
 
-    def timed_region(active_pool, hot_steps=None):
+    last_step = []          # keep_last: [data of the last timed step, its poses] -- what the caller of the path received (--dump-outputs)
+
+    def timed_region(active_pool, hot_steps=None, keep_last=False):
         """W warm-up + exactly K timed steps with `active_pool` solving the poses (None: matcher only); returns seconds (max over ranks).
         hot_steps: untimed matcher-only frames right in front of the clock (default HOT_STEPS; 0 = the region starts on a GPU that has just
-        been idle for the warm-up's pose join: the post-idle clock transient is then INSIDE the timed steps, `value_no_hot_steps`)"""
+        been idle for the warm-up's pose join: the post-idle clock transient is then INSIDE the timed steps, `value_no_hot_steps`)
+        keep_last: hold on to the last timed step's outputs in `last_step` once the clock has stopped"""
         nonlocal pool
         n_hot = HOT_STEPS if hot_steps is None else hot_steps
         pool = active_pool
@@ -419,12 +490,14 @@ def main():
         t0 = time.perf_counter()
         for i in range(args.steps):
             step(i)
-        drain()
+        last_data = drain()
         t_gpu = time.perf_counter()
-        join_poses()
+        poses_ = join_poses()
         sync_all()
         dt_ = time.perf_counter() - t0
         gc.enable()
+        if keep_last:
+            last_step[:] = [last_data, poses_[-B:]]
         host_t["tail"] = dt_ - (t_gpu - t0)          # after the last frame left the GPU: its pose (and the final barrier)
         own_dt[0] = dt_
         own_done[0], own_done[1] = done["frames"] - f0, done["poses"] - p0
@@ -524,7 +597,7 @@ def main():
     tc0 = thread_cpu() if os.environ.get("OPHIP_BENCH_TRACE") else None
     t_wall0 = time.perf_counter()
     thr0 = throttle_stat()
-    dt = timed_region(pools.get(args.pnp_policy))
+    dt = timed_region(pools.get(args.pnp_policy), keep_last=bool(args.dump_outputs) and rank == 0)
     dt_own = own_dt[0]
     main_done = list(own_done)
     thr1 = throttle_stat()
@@ -537,6 +610,10 @@ def main():
     if os.environ.get("OPHIP_BENCH_TRACE") and rank == 0:
         print("host us/step: " + ", ".join(f"{k} {1e6 * v / args.steps:.0f}" for k, v in host_t.items() if k != "tail")
               + f"; wall {1e6 * dt / args.steps:.0f}; after the last frame left the GPU {1e6 * host_t.get('tail', 0.0):.0f} us in all", file=sys.stderr)
+    dumped = None
+    if last_step:          # to the host now, before the untimed measurements below enqueue further frames
+        dumped = write_outputs(args.dump_outputs, output_arrays(*last_step))
+        last_step.clear()
     launches, kern_ms = hip.timing_read()
     hip.timing_select("")
     stage_kernels = {}
@@ -745,6 +822,8 @@ def main():
     }
     if coarse_stage is not None:
         result["coarse_stage"] = coarse_stage
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if args.roofline_kernel == "conf":
         # the HBM-bound kernel of the path (dual softmax + mutual-NN): conf_kernel reads the stored similarity once and writes
         # conf_matrix once -- 2 x 4 B per (i, j) pair.  The STAGE's algorithmic traffic (inputs once + ONE f32 write of the matrix) is
