@@ -386,6 +386,35 @@ int ophip_rows_layernorm128(const float* x, const float* gamma, const float* bet
 int ophip_fine2_match(const float* f0, const float* f1, const float* mkpts1_c, int K, int W, float scale, float* expec_f, float* mkpts1_f,
                       void* stream);
 
+/* Coarse encoder layer with FULL (softmax) attention (loftr_coarse.attention = "full": transformer.py:29-38, linear_attention.py:64-95):
+ * msg = softmax(Q K^T / sqrt(32)) V per head (8 heads of 32), then the same merge / LayerNorm / MLP / LayerNorm / residual tail as the
+ * linear layer.  Same stream wiring and in-place rule as ophip_encoder_layer; wpack is the f32 layer block of ophip_encoder_layer.
+ * The attention runs on split-bf16 MFMA (hi*hi + hi*lo + lo*hi, f32 accumulate) with an online softmax; the projections and the tail on
+ * the exact-f32 MFMA tiles.  workspace: ophip_encoder_full_workspace_bytes() bytes.  No mask variant: the reference's masked full
+ * attention raises (linear_attention.py:85 reads q_mask[:, :, None, None] of a None q_mask in the 3D stream's cross layer).
+ * ophip_full_attention_h8d32: the attention step alone, q [B][L][256], k, v [B][S][256] -> msg [B][L][256]. */
+size_t ophip_encoder_full_workspace_bytes(int B, int L3d, int L2d);
+int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
+                                const float* wpack, int is_cross, void* workspace, void* stream);
+int ophip_full_attention_h8d32(const float* q, const float* k, const float* v, int B, int L, int S, float* msg, void* stream);
+
+/* Fine stage with FULL attention in the fine encoder (loftr_fine.attention = "full"), composed over all matches like the detector's fine stage:
+ * token rows [cap][25][128] (windows) and [cap][128] (3D tokens), linear layers on ophip_rows_linear_x3, LayerNorms on ophip_rows_layernorm128.
+ * Grids cover the capacity cap of the match lists and read the device-side count (count[0]); rows of matches >= count are zeros.
+ *   ophip_fine_full_gather     W x W windows of the fine map (strides as ophip_fine_refine) around j_ids, and desc3d[b, :, i] per match
+ *   ophip_fine_full_attention  softmax(q k^T / sqrt(16)) v per match, 8 heads of 16: q [K][L][128], k, v [K][S][128], 1 <= L, S <= 32, f32;
+ *                              count may be NULL (all K live)
+ *   ophip_fine_full_match      FineMatching (utils/fine_matching.py:28-110) with ONE 3D token per match: <f3, window row> / sqrt(128) ->
+ *                              softmax -> expectation and std over the normalised grid; mkpts_f = mkpts_c + expectation * (W / 2) * scale
+ *                              (* query_scale[b][[1, 0]] when given), scale = image height / fine height */
+int ophip_fine_full_gather(const float* feat_f, long long fs_b, long long fs_c, long long fs_y, long long fs_x, int hf, int wf,
+                           const float* desc3d_f, long long d_bs, long long d_cs, const long long* b_ids, const long long* i_ids,
+                           const long long* j_ids, const int* count, int cap, int wc, int stride, int W, float* windows, float* feat3d,
+                           void* stream);
+int ophip_fine_full_attention(const float* q, const float* k, const float* v, int K, int L, int S, const int* count, float* msg, void* stream);
+int ophip_fine_full_match(const float* feat3d, const float* windows, const float* mkpts_c, const long long* b_ids, const float* query_scale,
+                          const int* count, int cap, int W, float scale, float* expec_f, float* mkpts_f, void* stream);
+
 /* Row f-2 -- the query crop of the frame loop (local_feature_2D_detector.py:164-190 crop_img_by_bbox, called from
  * detect :208-247 and previous_pose_detect :249-280): box [x0, y0, x1, y1) of a grayscale uint8 frame [H][W] -> out [S][S]
  * float in [0, 1] (= the reference's two cv2.warpAffine passes + astype(float32) / 255: integer-shift crop, then isotropic

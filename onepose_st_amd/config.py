@@ -116,8 +116,8 @@ def validate_config(cfg: dict) -> None:
         enc = cfg[name]
         if enc["type"] != "LoFTR":
             raise ValueError(f"{name}.type")
-        if enc["attention"] != "linear":
-            raise NotImplementedError(f"{name}.attention (HIP path: linear)")
+        if enc["attention"] not in ("linear", "full"):
+            raise NotImplementedError(f"{name}.attention (HIP path: 'linear' or 'full')")
         if enc["kernel_fn"] != "elu + 1":
             raise ValueError(f"{name}.kernel_fn")
         if enc["norm_method"] != "layernorm":

@@ -124,6 +124,13 @@ _SIGNATURES = {
     "ophip_conv2d_bf16": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_i, c_f,
                                 c_f, c_f, c_f, c_i, c_i, ctypes.c_void_p]),
     "ophip_crop_resize_gray": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
+    "ophip_encoder_full_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "ophip_encoder_layer_full_x3": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, ctypes.c_void_p]),
+    "ophip_full_attention_h8d32": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
+    "ophip_fine_full_gather": (c_i, [c_f, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_f, c_ll, c_ll, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
+                                     c_f, c_f, ctypes.c_void_p]),
+    "ophip_fine_full_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
+    "ophip_fine_full_match": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_float, c_f, c_f, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -135,6 +135,18 @@ class OnePosePlus_model(nn.Module):
         self.precision = str(config.get("hip_precision", os.environ.get("OPHIP_PRECISION", "bf16x3")))
         if self.precision not in ("f32", "bf16x3", "bf16"):
             raise ValueError(f"hip_precision {self.precision!r}: expected 'f32', 'bf16x3' or 'bf16'")
+        # loftr_coarse.attention = "full" (transformer.py:29-38): softmax attention in the coarse encoder, on the split-bf16 flash-attention
+        # kernel of csrc/encoder_full.hip; it runs the stage-by-stage path in the default arithmetic mode only
+        self.coarse_full = cc["attention"] == "full"
+        if self.coarse_full and self.precision != "bf16x3":
+            raise NotImplementedError(f"loftr_coarse.attention = 'full' runs with hip_precision 'bf16x3' only (got {self.precision!r})")
+        # loftr_fine.attention = "full": the fine stage composed over all matches from row kernels (csrc/fine_full.hip, ophip_rows_linear_x3),
+        # split-bf16 linear layers; its own arithmetic, so neither the plain-bf16 mode nor the plain-bf16 fine stage applies
+        self.fine_full = cf["attention"] == "full"
+        if self.fine_full and self.precision != "bf16x3":
+            raise NotImplementedError(f"loftr_fine.attention = 'full' runs with hip_precision 'bf16x3' only (got {self.precision!r})")
+        if self.fine_full and config.get("hip_fine_precision") is not None and str(config["hip_fine_precision"]) != "bf16x3":
+            raise NotImplementedError("loftr_fine.attention = 'full' runs with hip_fine_precision 'bf16x3' only")
         # the FINE stage's arithmetic when the path runs in "bf16x3": "bf16x3" (default: every keypoint within 1e-4 relative of the reference's)
         # or "bf16" -- plain bf16 operands, a third of the stage's matrix work: match indices unchanged (the fine stage only moves a match's
         # sub-pixel offset), keypoints within 0.05 px, pose within 1e-5 of the default's (tests/test_gpu_parity.py::test_fine_stage_in_plain_bf16...).
@@ -262,6 +274,9 @@ class OnePosePlus_model(nn.Module):
         if self.precision == "bf16x3":
             blocks["coarse_x3"] = [packing.pack_coarse_layer_x3w8(sd, f"loftr_coarse.layers.{i}.").to(device)
                                    for i in range(len(self.loftr_coarse.layer_names))]
+        if self.fine_full:
+            blocks["fine_full"] = [{n: t.to(device) for n, t in packing.pack_fine_layer_full_x3(sd, f"loftr_fine.layers.{i}.").items()}
+                                   for i in range(len(self.loftr_fine.layer_names))]
         if self.precision != "f32":
             blocks["fine_bf16"] = packing.pack_fine_layers_bf16(sd, "loftr_fine.layers.", len(self.loftr_fine.layer_names)).to(device)
         self._packed = (key, blocks)
@@ -336,6 +351,13 @@ class OnePosePlus_model(nn.Module):
         if not feat_c.is_cuda:
             raise hip.HipLibraryError("OnePosePlus_model runs on the HIP device only (no CPU fallback): move the "
                                       "model and its inputs to 'cuda'")
+        if self.coarse_full and "query_image_mask" in data:
+            if "cross" in self.loftr_coarse.layer_names:
+                # the reference's masked full attention never completes: its 3D stream's cross layer passes x_mask=None with a source
+                # mask, and FullAttention evaluates q_mask[:, :, None, None] on that None (linear_attention.py:85)
+                raise TypeError("'NoneType' object is not subscriptable: query_image_mask with loftr_coarse.attention = 'full' "
+                                "(the reference's FullAttention indexes the None q_mask of the 3D stream's cross layer, linear_attention.py:85)")
+            raise NotImplementedError("query_image_mask with loftr_coarse.attention = 'full'")
         hip.load()
         lib_call, P = hip.call, hip.ptr
         cfg = self.config
@@ -389,7 +411,7 @@ class OnePosePlus_model(nn.Module):
         lazy = self.conf_matrix_mode == "lazy" and not _force_eager
         # a lazy frame whose selection meets an exact row tie it cannot resolve without the stored row is run again with conf_matrix
         rerun = (lambda: self.enqueue_features(data, feat_c, feat_f, image_hw, want_fine_debug, host_copy, _pe_applied, False, True)) if lazy else None
-        if (self.frame_call and self.precision == "bf16x3" and self.overlap_fine and not _pe_applied and not want_fine_debug
+        if (self.frame_call and self.precision == "bf16x3" and not self.coarse_full and not self.fine_full and self.overlap_fine and not _pe_applied and not want_fine_debug
                 and not self.debug and bool(cfg["fine_matching"]["enable"])
                 and (self.kpt_3d_pos_encoding is not None or B == 1 or desc_in_d.shape[0] == B)
                 and len(self.loftr_coarse.layer_names) <= 16):
@@ -489,6 +511,15 @@ class OnePosePlus_model(nn.Module):
                     lib_call("ophip_encoder_layer_masked", P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]),
                              1 if name == "cross" else 0, P(ws), PM(), S)
                 x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
+        elif self.coarse_full:
+            # full (softmax) attention: projections, split-bf16 flash attention, tail (csrc/encoder_full.hip)
+            ws = torch.empty(hip.load().ophip_encoder_full_workspace_bytes(B, N, M), device=dev, dtype=torch.uint8)
+            for li, name in enumerate(self.loftr_coarse.layer_names):
+                if li == 0:
+                    wait_previous_fine()
+                lib_call("ophip_encoder_layer_full_x3", P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]),
+                         1 if name == "cross" else 0, P(ws, None), S)
+                x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
         elif self.precision == "bf16x3":
             # 16-token tiles, one eight-wave workgroup per CU, per-wave weight streams (csrc/encoder_x3w8.hip)
             entry = "ophip_encoder_layer_x3w8"
@@ -579,7 +610,13 @@ class OnePosePlus_model(nn.Module):
                 stride = hf // hc
                 fine_scale = (cf["window_size"] // 2) * (data["q_hw_i"][0] / hf)
                 max_matches = cap                                # one match per 3D point at most: the grid covers every possible K (surplus workgroups exit)
-                if self.precision == "f32":
+                if self.fine_full:
+                    fw, fd3 = self._fine_full_stage(ff, ff_strides, hf, wf, desc_fine_d, bstride(desc_fine_d), b_ids, i_ids, j_ids, count, cap, wc,
+                                                    stride, W["fine_full"], bool(cf["enable"]), mkc, qscale, float(data["q_hw_i"][0] / hf),
+                                                    expec, mkf, dev)
+                    if want_fine_debug:
+                        dbg_w, dbg_3 = fw, fd3
+                elif self.precision == "f32":
                     lib_call("ophip_fine_refine" + ("_scaled" if qscale is not None else ""), P(ff), *ff_strides, hf, wf,
                              P(desc_fine_d), bstride(desc_fine_d), desc_fine_d.stride(1),
                              P(b_ids, torch.int64), P(i_ids, torch.int64), P(j_ids, torch.int64), P(count, torch.int32), max_matches,
@@ -606,6 +643,49 @@ class OnePosePlus_model(nn.Module):
         return pend
 
 
+    def _fine_full_stage(self, ff, ff_strides, hf, wf, desc, desc_bs, b_ids, i_ids, j_ids, count, cap, wc, stride, Wf, encoder_on, mkc, qscale,
+                         scale, expec, mkf, dev):
+        """Rows a9-a11 with the fine encoder's full attention, on the current stream: gather (window and 3D token rows), the encoder layers
+        (transformer.py:133-171 on [K, 1, C] 3D tokens and [K, 25, C] windows; a cross layer's 3D update reads the pre-update windows), then
+        FineMatching on the one 3D token per match.  Every row count is the capacity: the kernels read the device-side count.  Returns the
+        encoder's output rows (windows [cap, 25, 128], 3D tokens [cap, 128])."""
+        lib_call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        f32 = dict(device=dev, dtype=torch.float32)
+        cnt = P(count, torch.int32)
+        WS, WW = 5, 25
+        win, f3 = torch.empty(cap, WW, 128, **f32), torch.empty(cap, 128, **f32)
+        lib_call("ophip_fine_full_gather", P(ff), *ff_strides, hf, wf, P(desc), desc_bs, desc.stride(1), P(b_ids, torch.int64), P(i_ids, torch.int64),
+                 P(j_ids, torch.int64), cnt, cap, wc, stride, WS, P(win), P(f3), S)
+
+        def lin(x, T, w, nout, xb=None, relu=False):
+            y = torch.empty(T, nout, **f32)
+            lib_call("ophip_rows_linear_x3", P(x), x.shape[-1], P(xb), xb.shape[-1] if xb is not None else 0, T, P(w, None), nout, 1 if relu else 0,
+                     P(y), S)
+            return y
+
+        def layer(x, Lx, src, Ls, w):                     # LoFTREncoderLayer with FullAttention (transformer.py:65-94)
+            T = cap * Lx
+            q, k, v = lin(x, T, w["q"], 128), lin(src, cap * Ls, w["k"], 128), lin(src, cap * Ls, w["v"], 128)
+            msg = torch.empty(T, 128, **f32)
+            lib_call("ophip_fine_full_attention", P(q), P(k), P(v), cap, Lx, Ls, cnt, P(msg), S)
+            m = lin(msg, T, w["m"], 128)
+            lib_call("ophip_rows_layernorm128", P(m), P(w["norm1_weight"]), P(w["norm1_bias"]), None, T, P(m), S)
+            h = lin(x, T, w["w0"], 256, xb=m, relu=True)
+            o = lin(h, T, w["w2"], 128)
+            y = torch.empty(T, 128, **f32)
+            lib_call("ophip_rows_layernorm128", P(o), P(w["norm2_weight"]), P(w["norm2_bias"]), P(x), T, P(y), S)
+            return y
+        if encoder_on:
+            for li, name in enumerate(self.loftr_fine.layer_names):
+                w = Wf[li]
+                if name == "self":
+                    win, f3 = layer(win, WW, win, WW, w), layer(f3, 1, f3, 1, w)
+                else:
+                    win, f3 = layer(win, WW, f3, 1, w), layer(f3, 1, win, WW, w)
+        win, f3 = win.view(cap, WW, 128), f3.view(cap, 128)
+        lib_call("ophip_fine_full_match", P(f3), P(win), P(mkc), P(b_ids, torch.int64), P(qscale), cnt, cap, WS, float(scale), P(expec), P(mkf), S)
+        return win, f3
+
     def _object_cache_entry(self, kpts_d, desc_in_d, W, dev, B, N, stream, masked=False, keep=True):
         """The object's cache entry ``{"x3d", "y3d0", "kv1", "ev"}`` (``ophip_object_cache``), built on a miss on ``stream`` with the kernels a
         frame would run.  Keyed on the object tensors' storage + version and the packed weights; ``Bo`` = 1 rows when the batch shares one
@@ -614,7 +694,7 @@ class OnePosePlus_model(nn.Module):
         shared = B > 1 and kpts_d.shape[0] == 1 and desc_in_d.shape[0] == 1
         Bo = 1 if shared else B
         names = self.loftr_coarse.layer_names
-        deep = (self.precision == "bf16x3" and len(names) >= 2 and names[0] == "self"
+        deep = (self.precision == "bf16x3" and not self.coarse_full and not self.fine_full and len(names) >= 2 and names[0] == "self"
                 and os.environ.get("OPHIP_OBJECT_CACHE_DEPTH", "2") != "1")
         # (masked: frames with a query_image_mask run both streams through the masked instantiation of the layer kernel; their entry is built
         #  with that instantiation, see ophip_encoder_object_x3w8)

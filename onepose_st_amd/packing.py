@@ -213,3 +213,13 @@ def pack_conv_bf16(w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
 def pack_stem(w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """``[128, 1, 7, 7]`` folded stem weights -> f32 ``[49][128]`` followed by the bias."""
     return torch.cat([w.reshape(w.shape[0], 49).t().contiguous().reshape(-1), bias.reshape(-1)]).to(torch.float32)
+
+
+def pack_fine_layer_full_x3(sd: dict, prefix: str) -> dict:
+    """Fine-encoder layer for the full-attention fine stage (``ophip_rows_linear_x3`` blocks, :func:`pack_linear_x3`): ``q``, ``k``, ``v``,
+    ``m`` (merge), ``w0`` / ``w2`` (MLP) and the two LayerNorms' f32 ``norm1_weight`` ... ``norm2_bias``; ``prefix`` like
+    ``"loftr_fine.layers.0."``."""
+    out = {n: pack_linear_x3(sd[prefix + k]) for n, k in (("q", "q_proj.weight"), ("k", "k_proj.weight"), ("v", "v_proj.weight"),
+                                                          ("m", "merge.weight"), ("w0", "mlp.0.weight"), ("w2", "mlp.2.weight"))}
+    out.update({n: sd[prefix + n.replace("_", ".")].detach().float().contiguous() for n in ("norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")})
+    return out

@@ -1,0 +1,116 @@
+"""Time full (softmax) attention on the device (``attention = "full"``: csrc/encoder_full.hip, csrc/fine_full.hip).
+
+    python tools/time_full_attention.py [--iters 20] [--warmup 5]
+
+Prints one JSON line per item, HIP-event times (median of ``--iters`` after ``--warmup``):
+  * the flash-attention kernel alone (``ophip_full_attention_h8d32``) at the four c2 shapes -- 3D self 7000 x 7000, 2D self 4800 x 4800,
+    the crosses 7000 x 4800 and 4800 x 7000 -- with its algorithmic rate 4 L S 256 flop (QK^T + PV; the split's three products per
+    product are NOT counted), and beside it the reference's composition in torch f32 on the same device
+    (``einsum`` -> ``softmax`` -> ``einsum``, linear_attention.py:82-93);
+  * one whole layer (``ophip_encoder_layer_full_x3``, both streams, self and cross) at c2;
+  * ``forward_features`` of a c2 frame with both encoders full, with the coarse one alone full, and with the default linear ones.
+"""
+from __future__ import annotations
+
+import argparse
+import copy
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from onepose_st_amd import hip, packing  # noqa: E402
+from onepose_st_amd.config import default_config  # noqa: E402
+from onepose_st_amd.model import OnePosePlus_model  # noqa: E402
+from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_state_dict  # noqa: E402
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def torch_full_attention(q, k, v):
+    B, L, S = q.shape[0], q.shape[1], k.shape[1]
+    qh, kh, vh = q.view(B, L, 8, 32), k.view(B, S, 8, 32), v.view(B, S, 8, 32)
+    QK = torch.einsum("nlhd,nshd->nlsh", qh, kh)
+    A = torch.softmax(QK / 32 ** 0.5, dim=2)
+    return torch.einsum("nlsh,nshd->nlhd", A, vh).reshape(B, L, 256)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    hip.load()
+    S = hip.stream_handle
+    g = torch.Generator().manual_seed(0)
+    shapes = [("3d_self", 7000, 7000), ("2d_self", 4800, 4800), ("3d_cross", 7000, 4800), ("2d_cross", 4800, 7000)]
+    tot_us = tot_torch = 0.0
+    for name, L, Sk in shapes:
+        q = torch.randn(1, L, 256, generator=g).to(dev)
+        k, v = torch.randn(1, Sk, 256, generator=g).to(dev), torch.randn(1, Sk, 256, generator=g).to(dev)
+        out = torch.empty(1, L, 256, device=dev)
+        us = timed(lambda: hip.call("ophip_full_attention_h8d32", hip.ptr(q), hip.ptr(k), hip.ptr(v), 1, L, Sk, hip.ptr(out), S()),
+                   args.iters, args.warmup)
+        ref = torch_full_attention(q, k, v)
+        err = (ref - out).abs().max().item()
+        ut = timed(lambda: torch_full_attention(q, k, v), max(3, args.iters // 4), 2)
+        flop = 4.0 * L * Sk * 256
+        tot_us, tot_torch = tot_us + us, tot_torch + ut
+        print(json.dumps({"item": "flash_attention", "shape": name, "L": L, "S": Sk, "us": round(us, 1),
+                          "tflops_algorithmic": round(flop / us * 1e-6, 1), "torch_f32_us": round(ut, 1),
+                          "torch_f32_tflops": round(flop / ut * 1e-6, 1), "speedup_vs_torch": round(ut / us, 2),
+                          "max_abs_diff_vs_torch": err}))
+        del q, k, v, out, ref
+        torch.cuda.empty_cache()
+    print(json.dumps({"item": "flash_attention_c2_layer_pair", "us": round(tot_us, 1), "torch_f32_us": round(tot_torch, 1)}))
+
+    cfg = default_config()
+    sd = make_synthetic_state_dict(0, cfg)
+    x3, x2 = torch.randn(1, 7000, 256, generator=g).to(dev), torch.randn(1, 4800, 256, generator=g).to(dev)
+    y3, y2 = torch.empty_like(x3), torch.empty_like(x2)
+    w = packing.pack_coarse_layer(sd, "loftr_coarse.layers.0.").to(dev)
+    ws = torch.empty(hip.load().ophip_encoder_full_workspace_bytes(1, 7000, 4800), dtype=torch.uint8, device=dev)
+    for cross in (0, 1):
+        us = timed(lambda: hip.call("ophip_encoder_layer_full_x3", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3), hip.ptr(y2), 1, 7000, 4800,
+                                    hip.ptr(w), cross, hip.ptr(ws, None), S()), args.iters, args.warmup)
+        attn = 4.0 * 256 * ((7000 * 4800 * 2) if cross else (7000 * 7000 + 4800 * 4800))
+        print(json.dumps({"item": "layer_full_x3", "cross": cross, "us": round(us, 1), "attention_tflops_algorithmic_whole_layer": round(attn / us * 1e-6, 1)}))
+    del x3, x2, y3, y2, ws
+
+    inp = make_synthetic_inputs(sd, n_points=7000, image_hw=(480, 640), n_plant=3000, seed=1, config=cfg)
+    d = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in inp.items()}
+    for coarse, fine in (("full", "full"), ("full", "linear"), ("linear", "linear")):
+        c = copy.deepcopy(cfg)
+        c["loftr_coarse"]["attention"], c["loftr_fine"]["attention"] = coarse, fine
+        m = OnePosePlus_model(c).eval()
+        m.load_state_dict(sd, strict=True)
+        m.to(dev)
+
+        def run():
+            data = {k: d[k] for k in ("keypoints3d", "descriptors3d_db", "descriptors3d_coarse_db")}
+            m.forward_features(data, d["feat_c"], d["feat_f"], inp["image_hw"])
+        us = timed(run, max(3, args.iters // 2), 2)
+        print(json.dumps({"item": "forward_features_c2", "coarse_attention": coarse, "fine_attention": fine, "us": round(us, 1)}))
+    print(json.dumps({"device": hip.device_info(), "build_stamp": hip.load().ophip_build_stamp().decode()}))
+
+
+if __name__ == "__main__":
+    main()
