@@ -398,6 +398,16 @@ int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, float* y3d, 
                                 const float* wpack, int is_cross, void* workspace, void* stream);
 int ophip_full_attention_h8d32(const float* q, const float* k, const float* v, int B, int L, int S, float* msg, void* stream);
 
+/* The detector's LoFTR coarse encoder with FULL attention (loftr.py, coarse.attention = "full"): LoFTR's cross layer is sequential (image 1
+ * attends to the UPDATED image 0), so it runs one query stream per call.  ophip_encoder_layer_full_x3_stream: y [B][L][256] = the full
+ * layer of x [B][L][256] (batch stride x_bstride floats) against src [B][S][256] (src_bstride) -- Q from x, K and V from src, the kernels
+ * and arithmetic of ophip_encoder_layer_full_x3.  A batch stride of 0 makes that input one image shared by every batch element (one query
+ * frame against B views); its projections are computed once.  src == x with equal strides and S == L is the self layer.  y must not alias
+ * x or src.  wpack: the f32 layer block.  workspace: ophip_encoder_full_stream_workspace_bytes(B, L, S) bytes. */
+size_t ophip_encoder_full_stream_workspace_bytes(int B, int L, int S);
+int ophip_encoder_layer_full_x3_stream(const float* x, long long x_bstride, const float* src, long long src_bstride, float* y, int B, int L,
+                                       int S, const float* wpack, void* workspace, void* stream);
+
 /* Fine stage with FULL attention in the fine encoder (loftr_fine.attention = "full"), composed over all matches like the detector's fine stage:
  * token rows [cap][25][128] (windows) and [cap][128] (3D tokens), linear layers on ophip_rows_linear_x3, LayerNorms on ophip_rows_layernorm128.
  * Grids cover the capacity cap of the match lists and read the device-side count (count[0]); rows of matches >= count are zeros.
@@ -414,6 +424,11 @@ int ophip_fine_full_gather(const float* feat_f, long long fs_b, long long fs_c, 
 int ophip_fine_full_attention(const float* q, const float* k, const float* v, int K, int L, int S, const int* count, float* msg, void* stream);
 int ophip_fine_full_match(const float* feat3d, const float* windows, const float* mkpts_c, const long long* b_ids, const float* query_scale,
                           const int* count, int cap, int W, float scale, float* expec_f, float* mkpts_f, void* stream);
+
+/* The detector's LoFTR fine encoder with FULL attention (loftr.py, fine.attention = "full"): window against window per match.
+ * ophip_fine2_full_attention: softmax(q k^T / sqrt(16)) v per match, 8 heads of 16: q [K][L][128], k, v [K][S][128] -> msg [K][L][128],
+ * 1 <= L, S <= 121 (W x W windows, W <= 11), K known on the host; f32 on the vector ALU (exact row maximum, then exp / sum / values). */
+int ophip_fine2_full_attention(const float* q, const float* k, const float* v, int K, int L, int S, float* msg, void* stream);
 
 /* Row f-2 -- the query crop of the frame loop (local_feature_2D_detector.py:164-190 crop_img_by_bbox, called from
  * detect :208-247 and previous_pose_detect :249-280): box [x0, y0, x1, y1) of a grayscale uint8 frame [H][W] -> out [S][S]

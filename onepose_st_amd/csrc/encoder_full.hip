@@ -9,6 +9,10 @@
 //               32-key tiles with an online softmax (running max and sum in f32); msg -> workspace
 //   full_tail   (over QUERY tokens)   merge -> LayerNorm -> [x, msg] -> MLP 512->512 ReLU ->256 -> LayerNorm -> x + msg
 // No atomics and no split of the source axis: every output is a fixed-order chain, bit-identical on any run or batch position.
+//
+// ophip_encoder_layer_full_x3_stream runs the same three kernels on ONE query stream against one source stream (LoFTR's sequential
+// cross layer: image 0 against image 1, then image 1 against the updated image 0): slot 0 carries the queries, slot 1 the source,
+// and a batch stride of 0 makes an input one image shared by the whole batch, whose projections are computed once.
 #include "tile_bf16.h"
 
 namespace {
@@ -50,7 +54,10 @@ __device__ __forceinline__ float swap32_max(float v) {               // max(v(la
 struct QkvArgs {
     const float* x[2];
     float *q[2], *k[2], *v[2];     // [B][L_s][256] each
-    long long bs[2];               // batch stride (floats) of x and of the planes of stream s
+    long long bs[2];               // batch stride (floats) of the planes of stream s
+    long long xbs[2];              // batch stride (floats) of x[s] (0: one image for every batch element)
+    int nb[2];                     // batch elements of stream s with planes of their own (blocks past them leave)
+    int parts[2];                  // planes written for stream s: 1 = Q, 2 = K | V, 3 = all three
     int L[2];
     int tiles[2];
     const f32x4 *wq, *wkv;         // f32 layer block: Wq tiles per wave, then [w][K heads 2w, 2w+1 | V heads 2w, 2w+1]
@@ -63,20 +70,21 @@ __global__ __launch_bounds__(256) OPHIP_WAVES_PER_SIMD(1, 2) void full_qkv_kerne
     const int tile = blockIdx.x, b = blockIdx.y;
     const int s = tile >= a.tiles[0] ? 1 : 0;
     const int lt = s ? tile - a.tiles[0] : tile;
+    if (b >= a.nb[s]) return;                              // a shared image: its planes are those of batch element 0
     const int L = a.L[s], tok0 = lt * OPHIP_TOK;
     const size_t boff = (size_t)b * a.bs[s];
-    load_rows_tile(smem, LDX, a.x[s] + boff, tok0, L, tid);
+    load_rows_tile(smem, LDX, a.x[s] + (size_t)b * a.xbs[s], tok0, L, tid);
     __syncthreads();
 
     constexpr int KB = C / 8, TS = KB * 64;
     const float* xa = smem + r * LDX + 4 * h;
-    {
+    if (a.parts[s] & 1) {
         f32x16 q[2] = {zero16(), zero16()};
         gemm_lds_x_packed<2>(q, xa, KB, a.wq + (size_t)(2 * wave) * TS + lane, TS);
 #pragma unroll
         for (int t = 0; t < 2; ++t) store_acc_rows(q[t], a.q[s] + boff, tok0, L, 64 * wave + 32 * t, lane);
     }
-    {
+    if (a.parts[s] & 2) {
         f32x16 kv[4] = {zero16(), zero16(), zero16(), zero16()};
         gemm_lds_x_packed<4>(kv, xa, KB, a.wkv + (size_t)(4 * wave) * TS + lane, TS);
 #pragma unroll
@@ -97,7 +105,7 @@ struct FlashArgs {
     const float* q[2];             // query planes of stream s
     const float *k[2], *v[2];      // source planes FOR query stream s (own for "self", the other stream's for "cross")
     float* o[2];
-    long long qbs[2], kbs[2];      // batch strides (floats)
+    long long qbs[2], kbs[2], obs[2];  // batch strides (floats) of the query, source and output planes
     int L[2], S[2];
     int tiles[2];                  // QT-query tiles per stream
     float scale_log2;              // log2(e) / sqrt(HD)
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(256) void full_flash_kernel(FlashArgs a) {
     }
     if (qrow < L) {
         const float inv = 1.0f / l;
-        float* dst = a.o[s] + (size_t)b * a.qbs[s] + (size_t)qrow * C + head * HD + 4 * h;
+        float* dst = a.o[s] + (size_t)b * a.obs[s] + (size_t)qrow * C + head * HD + 4 * h;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const f32x4 w = {o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv};
@@ -213,7 +221,8 @@ struct TailArgs {
     const float* x[2];
     const float* msg[2];
     float* y[2];
-    long long bs[2];
+    long long bs[2];               // batch stride (floats) of msg and y
+    long long xbs[2];              // batch stride (floats) of x (0: one image for every batch element)
     int L[2];
     int tiles[2];
     const f32x4 *wm, *w0, *w2;
@@ -232,7 +241,7 @@ __global__ __launch_bounds__(256) OPHIP_WAVES_PER_SIMD(1, 1) void full_tail_kern
     const int lt = s ? tile - a.tiles[0] : tile;
     const int L = a.L[s], tok0 = lt * OPHIP_TOK;
     const size_t boff = (size_t)b * a.bs[s];
-    load_rows_tile(X, LDX, a.x[s] + boff, tok0, L, tid);
+    load_rows_tile(X, LDX, a.x[s] + (size_t)b * a.xbs[s], tok0, L, tid);
     load_rows_tile(Hh, LDH, a.msg[s] + boff, tok0, L, tid);
     __syncthreads();
 
@@ -317,7 +326,9 @@ extern "C" int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, f
     QkvArgs qa;
     for (int s = 0; s < 2; ++s) {
         qa.q[s] = pl[0][s]; qa.k[s] = pl[1][s]; qa.v[s] = pl[2][s];
-        qa.bs[s] = (long long)Ls[s] * C;
+        qa.bs[s] = qa.xbs[s] = (long long)Ls[s] * C;
+        qa.nb[s] = B;
+        qa.parts[s] = 3;
         qa.L[s] = Ls[s];
     }
     qa.x[0] = x3d; qa.x[1] = x2d;
@@ -332,7 +343,7 @@ extern "C" int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, f
     for (int s = 0; s < 2; ++s) {
         const int src = is_cross ? 1 - s : s;          // stream 0 = 3D points, 1 = 2D grid (transformer.py:148-159)
         fa.q[s] = pl[0][s]; fa.k[s] = pl[1][src]; fa.v[s] = pl[2][src]; fa.o[s] = pl[3][s];
-        fa.qbs[s] = (long long)Ls[s] * C;
+        fa.qbs[s] = fa.obs[s] = (long long)Ls[s] * C;
         fa.kbs[s] = (long long)Ls[src] * C;
         fa.L[s] = Ls[s];
         fa.S[s] = Ls[src];
@@ -346,7 +357,7 @@ extern "C" int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, f
     ta.x[0] = x3d; ta.x[1] = x2d; ta.y[0] = y3d; ta.y[1] = y2d;
     for (int s = 0; s < 2; ++s) {
         ta.msg[s] = pl[3][s];
-        ta.bs[s] = (long long)Ls[s] * C;
+        ta.bs[s] = ta.xbs[s] = (long long)Ls[s] * C;
         ta.L[s] = Ls[s];
     }
     ta.tiles[0] = t3; ta.tiles[1] = t2;
@@ -361,6 +372,87 @@ extern "C" int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, f
     return 0;
 }
 
+// Q and msg planes [B][L][256], K and V planes [B][S][256] (a shared input uses the first [L or S][256] of its planes)
+extern "C" size_t ophip_encoder_full_stream_workspace_bytes(int B, int L, int S) {
+    if (B < 1 || L < 1 || S < 1) return 0;
+    return (size_t)2 * B * ((size_t)L + S) * C * sizeof(float);
+}
+
+// One coarse layer with full attention on ONE query stream: y[b] = layer(x[b] against src[b]), x [B][L][256] at batch stride x_bstride,
+// src [B][S][256] at src_bstride (floats; 0 = one image for every b, projected once).  src == x with equal strides and S == L is the
+// self layer (one Q | K | V pass).  wpack as ophip_encoder_layer_full_x3.
+extern "C" int ophip_encoder_layer_full_x3_stream(const float* x, long long x_bstride, const float* src, long long src_bstride, float* y,
+                                                  int B, int L, int S, const float* wpack, void* workspace, void* stream_) {
+    if (!x || !src || !y || !wpack || !workspace) return ophip_bad_arg(__func__, "null pointer");
+    if (B < 1 || L < 1 || S < 1) return ophip_bad_arg(__func__, "B, L, S must be >= 1");
+    if (y == x || y == src) return ophip_bad_arg(__func__, "in-place layer is not supported (y must not alias x or src)");
+    if ((x_bstride != 0 && x_bstride < (long long)L * C) || (src_bstride != 0 && src_bstride < (long long)S * C) || x_bstride % 4 != 0 ||
+        src_bstride % 4 != 0)
+        return ophip_bad_arg(__func__, "batch strides must be 0 or whole rows of at least L (S) x 256 floats, multiples of 4");
+    hipStream_t stream = (hipStream_t)stream_;
+    const float* wq = wpack;
+    const float* wkv = wq + C * C;
+    const float* wm = wkv + 2 * C * C;
+    const float* w0 = wm + C * C;
+    const float* w2 = w0 + 4 * C * C;
+    const float* ln = w2 + 2 * C * C;
+    const int nbx = x_bstride == 0 ? 1 : B, nbs = src_bstride == 0 ? 1 : B;
+    const bool self = src == x && src_bstride == x_bstride && S == L;
+    float* pq = static_cast<float*>(workspace);
+    float* pk = pq + (size_t)B * L * C;
+    float* pv = pk + (size_t)B * S * C;
+    float* pm = pv + (size_t)B * S * C;
+    const int tl = (L + OPHIP_TOK - 1) / OPHIP_TOK, ts = (S + OPHIP_TOK - 1) / OPHIP_TOK;
+
+    // slot 0: the query rows (Q, or Q | K | V for self); slot 1: the source rows (K | V), no tiles for self
+    QkvArgs qa;
+    qa.x[0] = x; qa.xbs[0] = x_bstride; qa.nb[0] = nbx; qa.parts[0] = self ? 3 : 1; qa.L[0] = L; qa.tiles[0] = tl;
+    qa.x[1] = src; qa.xbs[1] = src_bstride; qa.nb[1] = nbs; qa.parts[1] = 2; qa.L[1] = S; qa.tiles[1] = self ? 0 : ts;
+    for (int s = 0; s < 2; ++s) {
+        qa.q[s] = pq; qa.k[s] = pk; qa.v[s] = pv;
+        qa.bs[s] = (long long)qa.L[s] * C;
+    }
+    qa.wq = reinterpret_cast<const f32x4*>(wq);
+    qa.wkv = reinterpret_cast<const f32x4*>(wkv);
+    const size_t lds_qkv = (size_t)OPHIP_TOK * LDX * sizeof(float);
+    OPHIP_LAUNCH("full_qkv", stream, full_qkv_kernel, dim3(qa.tiles[0] + qa.tiles[1], self ? nbx : (nbx > nbs ? nbx : nbs)), dim3(256), lds_qkv,
+                 stream, qa);
+    OPHIP_CHECK_LAUNCH();
+
+    FlashArgs fa;
+    for (int s = 0; s < 2; ++s) {
+        fa.q[s] = pq; fa.k[s] = pk; fa.v[s] = pv; fa.o[s] = pm;
+        fa.qbs[s] = nbx > 1 ? (long long)L * C : 0;
+        fa.kbs[s] = nbs > 1 ? (long long)S * C : 0;
+        fa.obs[s] = (long long)L * C;
+        fa.L[s] = L; fa.S[s] = S;
+    }
+    fa.tiles[0] = (L + QT - 1) / QT;
+    fa.tiles[1] = 0;
+    fa.scale_log2 = 1.4426950408889634f / sqrtf((float)HD);
+    OPHIP_LAUNCH("full_flash", stream, full_flash_kernel, dim3(fa.tiles[0], NH, B), dim3(256), 0, stream, fa);
+    OPHIP_CHECK_LAUNCH();
+
+    TailArgs ta;
+    for (int s = 0; s < 2; ++s) {
+        ta.x[s] = x; ta.msg[s] = pm; ta.y[s] = y;
+        ta.bs[s] = (long long)L * C;
+        ta.xbs[s] = x_bstride;
+        ta.L[s] = L;
+    }
+    ta.tiles[0] = tl;
+    ta.tiles[1] = 0;
+    ta.wm = reinterpret_cast<const f32x4*>(wm);
+    ta.w0 = reinterpret_cast<const f32x4*>(w0);
+    ta.w2 = reinterpret_cast<const f32x4*>(w2);
+    ta.g1 = ln; ta.b1 = ln + C; ta.g2 = ln + 2 * C; ta.b2 = ln + 3 * C;
+    const size_t lds_tail = (size_t)OPHIP_TOK * (2 * LDX + LDH) * sizeof(float);
+    if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(full_tail_kernel), lds_tail, "hipFuncSetAttribute(full_tail)")) return rc;
+    OPHIP_LAUNCH("full_tail", stream, full_tail_kernel, dim3(tl, B), dim3(256), lds_tail, stream, ta);
+    OPHIP_CHECK_LAUNCH();
+    return 0;
+}
+
 // The attention step alone (timing and tests): q [B][L][256], k, v [B][S][256] -> msg [B][L][256], one stream, 8 heads of 32.
 extern "C" int ophip_full_attention_h8d32(const float* q, const float* k, const float* v, int B, int L, int S, float* msg, void* stream_) {
     if (!q || !k || !v || !msg) return ophip_bad_arg(__func__, "null pointer");
@@ -368,7 +460,7 @@ extern "C" int ophip_full_attention_h8d32(const float* q, const float* k, const 
     FlashArgs fa;
     for (int s = 0; s < 2; ++s) {
         fa.q[s] = q; fa.k[s] = k; fa.v[s] = v; fa.o[s] = msg;
-        fa.qbs[s] = (long long)L * C;
+        fa.qbs[s] = fa.obs[s] = (long long)L * C;
         fa.kbs[s] = (long long)S * C;
         fa.L[s] = L; fa.S[s] = S;
     }

@@ -7,6 +7,9 @@
 //   fine_full_match      the 3D token against its 25 window tokens -> heat-map expectation, std, refined query keypoint
 // Every kernel's grid covers the CAPACITY of the match lists and reads the device-side count: rows of matches >= count are written as
 // zeros (gather, attention) or skipped (match), so nothing waits for the host to learn the count.
+//
+// The detector's LoFTR fine stage with loftr_fine.attention = "full" (loftr.py) needs window against window, W x W up to 11 x 11:
+//   fine2_full_attention softmax(q k^T / 4) v per match, 8 heads of 16, 1 <= L, S <= 121; the match count is known on the host
 #include "tile.h"
 
 namespace {
@@ -103,6 +106,75 @@ __global__ __launch_bounds__(256) void fine_full_attention_kernel(AttnArgs p) {
     }
 }
 
+// ---- LoFTR windows: one workgroup per (match, head), one thread per query token ---------------------------------------------
+// The head's 16 key and 16 value columns of the match sit in LDS (2 x 121 x 64 B = 15.5 KB, so many workgroups share a CU); every lane
+// of a wave reads the same key row, an LDS broadcast.  f32 on the vector ALU, the two passes of fine_full_attention_kernel: the exact row
+// maximum first (the score recomputed in the second pass costs 16 FMAs per key, fewer than an online rescale of 16 accumulators), then
+// exp / sum / weighted values.  q is pre-scaled by 1/4 = 1/sqrt(16), exact in binary.
+constexpr int FW = 121;                         // tokens of an 11 x 11 window
+
+struct Attn2Args {
+    const float *q, *k, *v;                     // [K][L][128], [K][S][128], [K][S][128]
+    int L, S;
+    float* msg;                                 // [K][L][128]
+};
+
+// explicit FMAs: both passes round the score identically (the maximum is one of the scores, so its exp is exactly 1)
+__device__ __forceinline__ float dot16(const float (&q)[DH], const float* __restrict__ row) {
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < DH / 4; ++c) {
+        const f32x4 kk = *reinterpret_cast<const f32x4*>(row + 4 * c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d = __builtin_fmaf(q[4 * c + j], kk[j], d);
+    }
+    return d;
+}
+
+__global__ __launch_bounds__(128) void fine2_full_attention_kernel(Attn2Args p) {
+    __shared__ __attribute__((aligned(16))) float ks[FW * DH], vs[FW * DH];
+    const int m = blockIdx.x, hh = blockIdx.y, tid = threadIdx.x;
+    const float* kg = p.k + (size_t)m * p.S * CF + hh * DH;
+    const float* vg = p.v + (size_t)m * p.S * CF + hh * DH;
+    for (int e = tid; e < p.S * (DH / 4); e += 128) {
+        const int s = e / (DH / 4), c4 = e % (DH / 4);
+        *reinterpret_cast<f32x4*>(ks + s * DH + 4 * c4) = *reinterpret_cast<const f32x4*>(kg + (size_t)s * CF + 4 * c4);
+        *reinterpret_cast<f32x4*>(vs + s * DH + 4 * c4) = *reinterpret_cast<const f32x4*>(vg + (size_t)s * CF + 4 * c4);
+    }
+    __syncthreads();
+    if (tid >= p.L) return;                                  // no barriers below
+    const size_t row = ((size_t)m * p.L + tid) * CF + hh * DH;
+    float qr[DH];
+#pragma unroll
+    for (int c = 0; c < DH / 4; ++c) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p.q + row + 4 * c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) qr[4 * c + j] = 0.25f * t[j];
+    }
+    float mx = -INFINITY;
+    for (int s = 0; s < p.S; ++s) mx = fmaxf(mx, dot16(qr, ks + s * DH));
+    float acc[DH];
+#pragma unroll
+    for (int d = 0; d < DH; ++d) acc[d] = 0.f;
+    float sum = 0.f;
+    for (int s = 0; s < p.S; ++s) {
+        const float e = expf(dot16(qr, ks + s * DH) - mx);
+        sum += e;
+#pragma unroll
+        for (int c = 0; c < DH / 4; ++c) {
+            const f32x4 vv = *reinterpret_cast<const f32x4*>(vs + s * DH + 4 * c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[4 * c + j] += e * vv[j];
+        }
+    }
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int c = 0; c < DH / 4; ++c) {
+        const f32x4 o = {acc[4 * c] * inv, acc[4 * c + 1] * inv, acc[4 * c + 2] * inv, acc[4 * c + 3] * inv};
+        *reinterpret_cast<f32x4*>(p.msg + row + 4 * c) = o;
+    }
+}
+
 struct MatchArgs {
     const float *f3, *win;                      // [cap][128], [cap][WW][128]
     const float* mkc;                           // [cap][2] coarse query keypoints
@@ -184,6 +256,17 @@ extern "C" int ophip_fine_full_attention(const float* q, const float* k, const f
     hipStream_t stream = (hipStream_t)stream_;
     AttnArgs a{q, k, v, L, S, count, msg};
     OPHIP_LAUNCH("fine_full_attention", stream, fine_full_attention_kernel, dim3(K), dim3(256), 0, stream, a);
+    OPHIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ophip_fine2_full_attention(const float* q, const float* k, const float* v, int K, int L, int S, float* msg, void* stream_) {
+    if (!q || !k || !v || !msg) return ophip_bad_arg(__func__, "null pointer");
+    if (K < 0 || L < 1 || L > FW || S < 1 || S > FW) return ophip_bad_arg(__func__, "bad sizes (K >= 0, 1 <= L, S <= 121)");
+    if (K == 0) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    Attn2Args a{q, k, v, L, S, msg};
+    OPHIP_LAUNCH("fine2_full_attention", stream, fine2_full_attention_kernel, dim3(K, NH), dim3(128), 0, stream, a);
     OPHIP_CHECK_LAUNCH();
     return 0;
 }

@@ -131,6 +131,9 @@ _SIGNATURES = {
                                      c_f, c_f, ctypes.c_void_p]),
     "ophip_fine_full_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
     "ophip_fine_full_match": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_float, c_f, c_f, ctypes.c_void_p]),
+    "ophip_encoder_full_stream_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "ophip_encoder_layer_full_x3_stream": (c_i, [c_f, c_ll, c_f, c_ll, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
+    "ophip_fine2_full_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -18,6 +18,11 @@ definition (``oracle/loftr_oracle.py`` restates it on the CPU; parity unpinned).
 * dual-softmax + mutual-nearest between the two grids: ``ophip_coarse_match_2d`` (temperature exactly 0.1, all-sides border);
 * fine stage, window 9 on both images, batched over all matches: ``csrc/loftr_fine.hip``.
 
+``coarse.attention`` / ``fine.attention`` = ``"full"`` (each on its own; the reference config's other option) swap the attention form
+(``FullAttention``, same ``state_dict``): a coarse layer is then ``ophip_encoder_layer_full_x3_stream`` (one query stream per launch,
+the f32 layer block), a shared query image is passed with batch stride 0 instead of being copied V times and its layer-0 self layer runs
+once; the fine layers call ``ophip_fine2_full_attention`` (W x W windows, softmax) in place of the linear attention.
+
 Masks / scales / provided coarse matches (``mask0``, ``scale0``, ``mkpts0_c`` inputs) and the feature-extraction kwargs are the
 SfM pipeline's (out of scope) and raise ``NotImplementedError``.  No CPU fallback.
 """
@@ -76,8 +81,10 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         cc, cf, mc = config["coarse"], config["fine"], config["match_coarse"]
         if cc["d_model"] != 256 or cc["nhead"] != 8 or cf["d_model"] != 128 or cf["nhead"] != 8:
             raise NotImplementedError("HIP kernels are specialised for d_model 256 / 128 with 8 heads")
-        if cc["attention"] != "linear" or cf["attention"] != "linear":
-            raise NotImplementedError("attention: linear")
+        for enc, c in (("coarse", cc), ("fine", cf)):
+            if c["attention"] not in ("linear", "full"):
+                raise NotImplementedError(f"{enc}.attention: linear or full")
+        self.coarse_full, self.fine_full = cc["attention"] == "full", cf["attention"] == "full"
         if mc["match_type"] != "dual_softmax":
             raise NotImplementedError("match_coarse.match_type: dual_softmax")
         if cc["temp_bug_fix"]:
@@ -119,7 +126,8 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                                  for n in ("norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")})
             self._packed = (key, {
                 "backbone": pack_backbone(bb, device),
-                "coarse": [packing.pack_coarse_layer_x3w8(sd, f"loftr_coarse.layers.{i}.").to(device) for i in range(len(self.loftr_coarse.layer_names))],
+                "coarse": [(packing.pack_coarse_layer if self.coarse_full else packing.pack_coarse_layer_x3w8)(sd, f"loftr_coarse.layers.{i}.").to(device)
+                           for i in range(len(self.loftr_coarse.layer_names))],
                 "fine": fine,
             })
         return self._packed[1]
@@ -132,6 +140,49 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         return self._pe[k]
 
     # ------------------------------------------------------------------------------------------
+    def _coarse_linear(self, Wc, fc0, fc1, shared1, V, L0, L1):
+        call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        x0 = fc0.contiguous()
+        x1 = (fc1.expand(V, -1, -1) if shared1 else fc1).contiguous()
+        ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(V, L0, L1), dtype=torch.uint8, device=x0.device)
+        for w, name in zip(Wc, self.loftr_coarse.layer_names):
+            if name == "self":
+                b0, b1 = torch.empty_like(x0), torch.empty_like(x1)
+                call("ophip_encoder_layer_x3w8", P(x0), P(x1), P(b0), P(b1), V, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None), S)
+                x0, x1 = b0, b1
+            else:
+                n0 = torch.empty_like(x0)              # image 0 against image 1
+                call("ophip_encoder_layer_x3w8_streams", P(x0), P(x1), P(n0), None, V, L0, L1, P(w, None), 1, 1, P(ws, None), S)
+                n1 = torch.empty_like(x1)              # image 1 against the UPDATED image 0
+                call("ophip_encoder_layer_x3w8_streams", P(n0), P(x1), None, P(n1), V, L0, L1, P(w, None), 1, 2, P(ws, None), S)
+                x0, x1 = n0, n1
+        return x0, x1
+
+    def _coarse_full(self, Wc, x0, x1, V, L0, L1):
+        """full attention, one query stream per launch; ``x1 [1, L1, 256]`` against ``x0 [V, L0, 256]`` is one query image shared by the
+        V pairs: it is read with batch stride 0 (projected once) until the first cross layer gives every pair its own rows, and a self
+        layer before that runs on it once"""
+        call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        Lm = max(L0, L1)
+        ws = torch.empty(hip.load().ophip_encoder_full_stream_workspace_bytes(V, Lm, Lm), dtype=torch.uint8, device=x0.device)
+
+        def layer(x, src, w):
+            B = max(x.shape[0], src.shape[0])
+            y = torch.empty(B, x.shape[1], 256, device=x.device)
+            bs = lambda t: t.stride(0) if t.shape[0] > 1 else 0
+            call("ophip_encoder_layer_full_x3_stream", P(x), bs(x), P(src), bs(src), P(y), B, x.shape[1], src.shape[1], P(w, None),
+                 P(ws, None), S)
+            return y
+        for w, name in zip(Wc, self.loftr_coarse.layer_names):
+            if name == "self":
+                x0, x1 = layer(x0, x0, w), layer(x1, x1, w)
+            else:
+                x0 = layer(x0, x1, w)                  # image 0 against image 1
+                x1 = layer(x1, x0, w)                  # image 1 against the UPDATED image 0
+        if x1.shape[0] != V:                           # no cross layer: the query's rows are still shared
+            x1 = x1.expand(V, -1, -1).contiguous()
+        return x0, x1
+
     @torch.no_grad()
     def forward(self, data, **kwargs):
         if self.training:
@@ -180,22 +231,12 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             shared1 = fc1.shape[0] == 1 and V > 1
         L0, L1 = hw0_c[0] * hw0_c[1], hw1_c[0] * hw1_c[1]
 
-        # ---- coarse transformer: self = one two-stream launch; cross = two one-stream launches (sequential semantics) -------------------
-        x0 = fc0.contiguous()
-        x1 = (fc1.expand(V, -1, -1) if shared1 else fc1).contiguous()
-        ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(V, L0, L1), dtype=torch.uint8, device=dev)
-        for li, name in enumerate(self.loftr_coarse.layer_names):
-            w = Wb["coarse"][li]
-            if name == "self":
-                b0, b1 = torch.empty_like(x0), torch.empty_like(x1)
-                call("ophip_encoder_layer_x3w8", P(x0), P(x1), P(b0), P(b1), V, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None), S)
-                x0, x1 = b0, b1
-            else:
-                n0 = torch.empty_like(x0)              # image 0 against image 1
-                call("ophip_encoder_layer_x3w8_streams", P(x0), P(x1), P(n0), None, V, L0, L1, P(w, None), 1, 1, P(ws, None), S)
-                n1 = torch.empty_like(x1)              # image 1 against the UPDATED image 0
-                call("ophip_encoder_layer_x3w8_streams", P(n0), P(x1), None, P(n1), V, L0, L1, P(w, None), 1, 2, P(ws, None), S)
-                x0, x1 = n0, n1
+        # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
+        #      full: one one-stream launch per image and layer, the shared query read with batch stride 0 ---------------------------
+        if self.coarse_full:
+            x0, x1 = self._coarse_full(Wb["coarse"], fc0.contiguous(), fc1.contiguous(), V, L0, L1)
+        else:
+            x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, shared1, V, L0, L1)
 
         # ---- coarse matching between the two grids -----------------------------------------------------------------------------
         mc = self.config["match_coarse"]
@@ -243,7 +284,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         def fine_layer(x, src, w):
             q, k, v = lin(x, w["q"], 128), lin(src, w["k"], 128), lin(src, w["v"], 128)
             msg = torch.empty(T, 128, device=dev)
-            call("ophip_fine2_attention", P(q), P(k), P(v), K, WW, WW, P(msg), S)
+            call("ophip_fine2_full_attention" if self.fine_full else "ophip_fine2_attention", P(q), P(k), P(v), K, WW, WW, P(msg), S)
             m = lin(msg, w["m"], 128)
             call("ophip_rows_layernorm128", P(m), P(w["norm1_weight"]), P(w["norm1_bias"]), None, T, P(m), S)
             h = lin(x.view(T, 128), w["w0"], 256, xb=m, relu=True)

@@ -8,7 +8,11 @@ Prints one JSON line per item, HIP-event times (median of ``--iters`` after ``--
     product are NOT counted), and beside it the reference's composition in torch f32 on the same device
     (``einsum`` -> ``softmax`` -> ``einsum``, linear_attention.py:82-93);
   * one whole layer (``ophip_encoder_layer_full_x3``, both streams, self and cross) at c2;
-  * ``forward_features`` of a c2 frame with both encoders full, with the coarse one alone full, and with the default linear ones.
+  * ``forward_features`` of a c2 frame with both encoders full, with the coarse one alone full, and with the default linear ones;
+  * the detector's LoFTR shapes (``--items detector`` for these alone): the one-stream layer (``ophip_encoder_layer_full_x3_stream``) on a
+    512 x 512 view's 4096 coarse tokens (self), 4096 against a 1920 x 1440 frame's 43 200 (cross), the frame's own self layer (the one the
+    shared-query path runs once instead of once per view), and the window attention (``ophip_fine2_full_attention``) over 1000 matches at
+    W = 9 and 11 beside the linear one (``ophip_fine2_attention``).
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from onepose_st_amd import hip, packing  # noqa: E402
 from onepose_st_amd.config import default_config  # noqa: E402
 from onepose_st_amd.model import OnePosePlus_model  # noqa: E402
-from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_state_dict  # noqa: E402
+from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_loftr_state_dict, make_synthetic_state_dict  # noqa: E402
 
 
 def timed(fn, iters, warmup):
@@ -56,9 +60,47 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--items", choices=("all", "c2", "detector"), default="all")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hip.load()
+    if args.items in ("all", "c2"):
+        c2_items(args, dev)
+    if args.items in ("all", "detector"):
+        detector_items(args, dev)
+    print(json.dumps({"device": hip.device_info(), "build_stamp": hip.load().ophip_build_stamp().decode()}))
+
+
+def detector_items(args, dev):
+    S = hip.stream_handle
+    g = torch.Generator().manual_seed(1)
+    sd = make_synthetic_loftr_state_dict(0)
+    w = packing.pack_coarse_layer(sd, "loftr_coarse.layers.1.").to(dev)
+    for name, L, Sk in (("view_self", 4096, 4096), ("view_vs_frame_cross", 4096, 43200), ("frame_self", 43200, 43200)):
+        x = torch.randn(1, L, 256, generator=g).to(dev)
+        src = x if name.endswith("self") else torch.randn(1, Sk, 256, generator=g).to(dev)
+        y = torch.empty_like(x)
+        ws = torch.empty(hip.load().ophip_encoder_full_stream_workspace_bytes(1, L, Sk), dtype=torch.uint8, device=dev)
+        us = timed(lambda: hip.call("ophip_encoder_layer_full_x3_stream", hip.ptr(x), 0, hip.ptr(src), 0, hip.ptr(y), 1, L, Sk, hip.ptr(w),
+                                    hip.ptr(ws, None), S()), args.iters, args.warmup)
+        print(json.dumps({"item": "loftr_layer_full_stream", "shape": name, "L": L, "S": Sk, "us": round(us, 1),
+                          "attention_tflops_algorithmic_whole_layer": round(4.0 * L * Sk * 256 / us * 1e-6, 1)}))
+        del x, src, y, ws
+        torch.cuda.empty_cache()
+    K = 1000
+    for W in (9, 11):
+        WW = W * W
+        q, k, v = (torch.randn(K, WW, 128, generator=g).to(dev) for _ in range(3))
+        msg = torch.empty_like(q)
+        row = {"item": "loftr_fine_window_attention", "K": K, "W": W}
+        for kname in ("ophip_fine2_full_attention", "ophip_fine2_attention"):
+            row[kname.replace("ophip_fine2_", "") + "_us"] = round(timed(
+                lambda: hip.call(kname, hip.ptr(q), hip.ptr(k), hip.ptr(v), K, WW, WW, hip.ptr(msg), S()), args.iters, args.warmup), 1)
+        row["full_gflops_algorithmic"] = round(4.0 * K * WW * WW * 128 / row["full_attention_us"] * 1e-3, 1)
+        print(json.dumps(row))
+
+
+def c2_items(args, dev):
     S = hip.stream_handle
     g = torch.Generator().manual_seed(0)
     shapes = [("3d_self", 7000, 7000), ("2d_self", 4800, 4800), ("3d_cross", 7000, 4800), ("2d_cross", 4800, 7000)]
@@ -109,7 +151,6 @@ def main():
             m.forward_features(data, d["feat_c"], d["feat_f"], inp["image_hw"])
         us = timed(run, max(3, args.iters // 2), 2)
         print(json.dumps({"item": "forward_features_c2", "coarse_attention": coarse, "fine_attention": fine, "us": round(us, 1)}))
-    print(json.dumps({"device": hip.device_info(), "build_stamp": hip.load().ophip_build_stamp().decode()}))
 
 
 if __name__ == "__main__":
