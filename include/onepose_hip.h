@@ -375,6 +375,24 @@ int ophip_coarse_match_2d(const float* feat0, const float* feat1, const float* p
                           float* conf, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask,
                           int* count, int nsplit, void* stream);
+/* ophip_coarse_match_2d_sinkhorn: the same stage with LoFTR's optimal-transport matching (match_type 'sinkhorn', inference) in place
+ *   of the dual softmax; split-bf16 similarity, f32 everywhere else.  m = L0, n = L1, S = <f0, f1> / C (no temperature):
+ *     Z = [[S, a], [a, a]] with the dustbin row and column a = bin_score; norm = -log(m + n),
+ *     log_mu = [norm x m, log n + norm], log_nu = [norm x n, log m + norm]; u = v = 0, then `iters` (>= 0) times
+ *     u = log_mu - logsumexp_j(Z + v_j), v = log_nu - logsumexp_i(Z + u_i), bins included;
+ *     conf = exp(((S + u_i) + v_j) - norm) (the assignment without its dustbins), written to conf [B][L0][L1] (required).
+ *   prefilter != 0: a row whose argmax over j (dustbin included) is the dustbin column, and a column whose argmax over i is the dustbin
+ *     row, are zeroed.  argmax takes the first maximum and the dustbin is last: it wins only when its exp'd f32 value is STRICTLY greater.
+ *   Then the selection of ophip_coarse_match_2d (threshold, all-sides border, mutual nearest, first-j ties, ordered compaction), same
+ *   outputs.  workspace: ophip_coarse_sinkhorn_workspace_floats(B, L0, L1) floats.  Deterministic.  On return the workspace holds
+ *   the dual potentials from float ophip_coarse_workspace_floats(B, L0, L1) on, rounded up to a 64-byte boundary: u [B][U] then
+ *   v [B][V], U = L0 + 1 and V = L1 + 1 rounded up to multiples of 4, the dustbin's last (conf = exp(((S + u_i) + v_j) - norm)). */
+size_t ophip_coarse_sinkhorn_workspace_floats(int B, int L0, int L1);
+int ophip_coarse_match_2d_sinkhorn(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                                   int B, int L0, int L1, int w0c, int w1c, float bin_score, int iters, int prefilter,
+                                   float thr, int border_rm, float scale, float* conf, float* workspace,
+                                   long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
+                                   float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream);
 int ophip_fine2_gather(const float* feat_cl, int hf, int wf, const long long* cell_ids, int K, int wc, int stride, int W, float* out, void* stream);
 /* the same over a batch of images [B][hf * wf][128]: match k reads image b_ids[k] (feat_bstride floats apart; 0: one image for every match) */
 int ophip_fine2_gather_b(const float* feat_cl, long long feat_bstride, const long long* b_ids, int hf, int wf, const long long* cell_ids,

@@ -1204,6 +1204,18 @@ CoarseWs coarse_ws(int B, int N, int M) {
     return w;
 }
 
+// the selection launch over the row-best records and column maxima in the workspace (coarse_impl; ophip_coarse_select_2d)
+int select_launch(const SelectArgs& se, float* workspace, const CoarseWs& ws, hipStream_t stream) {
+    int* dec = reinterpret_cast<int*>(workspace + ws.seldec);
+    int* wgc = reinterpret_cast<int*>(workspace + ws.selcnt);
+    const int nwg = (int)(((long long)se.B * se.N + SEL_T - 1) / SEL_T);
+    OPHIP_LAUNCH("select", stream, select_decide_kernel, dim3(nwg), dim3(SEL_T), 0, stream, se, dec, wgc);
+    OPHIP_CHECK_LAUNCH();
+    OPHIP_LAUNCH("select_place", stream, select_place_kernel, dim3(nwg), dim3(SEL_T), 0, stream, se, dec, wgc);
+    OPHIP_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" size_t ophip_coarse_workspace_floats(int B, int N, int M) { return coarse_ws(B, N, M).total; }
@@ -1354,17 +1366,47 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
     if (parts & 2) {
         SelectArgs se{conf, rowbest, colmax, keypoints3d, kpts_bstride, B, N, M, sel_nspan, wc, border_rm, border_mode, wi, thr, scale, qscale,
                       b_ids, i_ids, j_ids, mconf, mkpts3d, mkpts_c, m_bids, gt_mask, count};      // (conf == NULL: an exact row tie sets count[1])
-        int* dec = reinterpret_cast<int*>(workspace + ws.seldec);
-        int* wgc = reinterpret_cast<int*>(workspace + ws.selcnt);
-        const int nwg = (int)(((long long)B * N + SEL_T - 1) / SEL_T);
-        OPHIP_LAUNCH("select", stream, select_decide_kernel, dim3(nwg), dim3(SEL_T), 0, stream, se, dec, wgc);
-        OPHIP_CHECK_LAUNCH();
-        OPHIP_LAUNCH("select_place", stream, select_place_kernel, dim3(nwg), dim3(SEL_T), 0, stream, se, dec, wgc);
-        OPHIP_CHECK_LAUNCH();
+        if (int rc = select_launch(se, workspace, ws, stream)) return rc;
     }
     return 0;
 }
 }  // namespace
+
+// Internal (x3w8_internal.h): the pieces of the eager bf16 form that csrc/coarse_sinkhorn.hip reuses.
+int ophip_coarse_sim_store(const float* feat0, const float* feat1, int B, int N, int M, float* conf, float* workspace,
+                           const float** rowstat, float** rowbest, unsigned** colmax_bits, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int ntr = (N + TM - 1) / TM, ntc = (M + TN - 1) / TN;
+    const CoarseWs ws = coarse_ws(B, N, M);
+    char *fa, *fb;
+    frag_plane_ptrs(workspace, B, N, M, &fa, &fb);
+    FragArgs fr{feat0, feat1, fa, fb, N, M, 4 * ntr, 4 * ntc};
+    OPHIP_LAUNCH("frag_planes", stream, frag_planes_kernel, dim3(16 * (ntr + ntc), B), dim3(256), 0, stream, fr);
+    OPHIP_CHECK_LAUNCH();
+    SimFragArgs sf{};
+    sf.a = fa; sf.b = fb; sf.conf = conf; sf.rowpart = workspace + ws.rowpart; sf.colpart = workspace + ws.colpart;
+    sf.N = N; sf.M = M; sf.ntr = ntr; sf.ntc = ntc; sf.temp = 1.0f; sf.stamps = ophip_stamp_buffer();
+    if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(sim_frag_kernel<3, 0>), SIM_FRAG_LDS, "hipFuncSetAttribute(sim_frag)")) return rc;
+    OPHIP_LAUNCH("sim_stats", stream, (sim_frag_kernel<3, 0>), dim3(8 * ((ntr + 7) / 8) * ntc, B), dim3(256), SIM_FRAG_LDS, stream, sf);
+    OPHIP_CHECK_LAUNCH();
+    CombineArgs ca{sf.rowpart, sf.colpart, workspace + ws.rowstat, workspace + ws.colstat, reinterpret_cast<unsigned*>(workspace + ws.colmax),
+                   N, M, ntr, ntc, nullptr, nullptr, nullptr};
+    OPHIP_LAUNCH("stat_combine", stream, stat_combine_kernel, dim3((N + M + 31) / 32, B), dim3(256), 0, stream, ca);
+    OPHIP_CHECK_LAUNCH();
+    *rowstat = workspace + ws.rowstat;
+    *rowbest = workspace + ws.rowbest;
+    *colmax_bits = reinterpret_cast<unsigned*>(workspace + ws.colmax);
+    return 0;
+}
+
+int ophip_coarse_select_2d(const float* conf, int nspan, const float* points0, long long points_bstride, int B, int N, int M, int wi, int wc,
+                           float thr, int border_rm, float scale, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
+                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream) {
+    const CoarseWs ws = coarse_ws(B, N, M);
+    SelectArgs se{conf, workspace + ws.rowbest, workspace + ws.colmax, points0, points_bstride, B, N, M, nspan, wc, border_rm, 1, wi, thr, scale,
+                  nullptr, b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count};
+    return select_launch(se, workspace, ws, (hipStream_t)stream);
+}
 
 extern "C" int ophip_coarse_frag_planes(float* workspace, int B, int N, int M, void** planes3d, void** planes2d) {
     if (!workspace || !planes3d || !planes2d || B < 1 || N < 1 || M < 1) return ophip_bad_arg(__func__, "bad argument");

@@ -20,3 +20,13 @@ int ophip_x3w8_layer_bs(const float* x3d, long long x3d_bs, const float* x2d, fl
 // coarse matching, eager form in the bf16 modes: true = statistics pass + a second tile pass that writes every confidence once
 // (csrc/coarse_match.hip ophip_coarse_two_pass: by matrix size / OPHIP_COARSE_TWO_PASS); false = similarity store + in-place conversion pass
 bool ophip_coarse_two_pass(int B, int N, int M);
+
+// the eager split-bf16 similarity of csrc/coarse_match.hip with temperature 1 (frag_planes, sim_frag_kernel<3, 0>, stat_combine):
+// S = <f0, f1> / C into conf [B][N][M], the merged row (max, sum exp) in *rowstat [B][N][2], column maxima cleared; *rowbest / *colmax_bits
+// are the workspace's row-best records and column maxima that ophip_coarse_select_2d reads.  workspace: ophip_coarse_workspace_floats
+int ophip_coarse_sim_store(const float* feat0, const float* feat1, int B, int N, int M, float* conf, float* workspace,
+                           const float** rowstat, float** rowbest, unsigned** colmax_bits, void* stream);
+// ophip_coarse_match_2d's selection (border on all four sides of both grids) over those records, nspan per row
+int ophip_coarse_select_2d(const float* conf, int nspan, const float* points0, long long points_bstride, int B, int N, int M, int wi, int wc,
+                           float thr, int border_rm, float scale, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
+                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream);

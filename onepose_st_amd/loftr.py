@@ -23,6 +23,10 @@ definition (``oracle/loftr_oracle.py`` restates it on the CPU; parity unpinned).
 the f32 layer block), a shared query image is passed with batch stride 0 instead of being copied V times and its layer-0 self layer runs
 once; the fine layers call ``ophip_fine2_full_attention`` (W x W windows, softmax) in place of the linear attention.
 
+``match_coarse.match_type`` = ``"sinkhorn"`` (the config's other option) swaps the dual softmax for optimal transport with a dustbin
+(LoFTR's ``CoarseMatching`` sinkhorn branch, SuperGlue's ``log_optimal_transport``, ``skh_iters`` iterations, ``skh_prefilter``):
+``ophip_coarse_match_2d_sinkhorn``.  Such a model has one more parameter, ``coarse_matching.bin_score`` (0-d, ``skh_init_bin_score``).
+
 Masks / scales / provided coarse matches (``mask0``, ``scale0``, ``mkpts0_c`` inputs) and the feature-extraction kwargs are the
 SfM pipeline's (out of scope) and raise ``NotImplementedError``.  No CPU fallback.
 """
@@ -85,8 +89,15 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             if c["attention"] not in ("linear", "full"):
                 raise NotImplementedError(f"{enc}.attention: linear or full")
         self.coarse_full, self.fine_full = cc["attention"] == "full", cf["attention"] == "full"
-        if mc["match_type"] != "dual_softmax":
-            raise NotImplementedError("match_coarse.match_type: dual_softmax")
+        if mc["match_type"] not in ("dual_softmax", "sinkhorn"):
+            raise NotImplementedError("match_coarse.match_type: dual_softmax or sinkhorn")
+        self.sinkhorn = mc["match_type"] == "sinkhorn"
+        if self.sinkhorn:
+            iters = mc["skh_iters"]
+            if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+                raise ValueError("match_coarse.skh_iters: an int >= 0")
+            if mc.get("sparse_spvs", False):
+                raise NotImplementedError("match_coarse.sparse_spvs: training output (conf_matrix_with_bin)")
         if cc["temp_bug_fix"]:
             raise NotImplementedError("temp_bug_fix: the reference's detector config runs the original (floor-division) position table")
         if config["fine_concat_coarse_feat"]:
@@ -102,6 +113,9 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                                                       "block_dims": list(config["resnetfpn"]["block_dims"]), "output_layers": [3, 1]}})
         self.loftr_coarse = _Encoder(cc)
         self.loftr_fine = _Encoder(cf)
+        if self.sinkhorn:                              # the reference's CoarseMatching holds bin_score in the sinkhorn form only
+            self.coarse_matching = nn.Module()
+            self.coarse_matching.bin_score = nn.Parameter(torch.tensor(float(mc["skh_init_bin_score"]), requires_grad=True))
         self._packed = None
         self._pe = {}
         # optional ``hook(fc0 [1, L0, 256], ff0 [hf0 * wf0, 128], fc1, ff1) -> the same four``: the backbone-output boundary (coarse rows
@@ -129,6 +143,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                 "coarse": [(packing.pack_coarse_layer if self.coarse_full else packing.pack_coarse_layer_x3w8)(sd, f"loftr_coarse.layers.{i}.").to(device)
                            for i in range(len(self.loftr_coarse.layer_names))],
                 "fine": fine,
+                "bin_score": float(sd["coarse_matching.bin_score"]) if self.sinkhorn else None,
             })
         return self._packed[1]
 
@@ -245,14 +260,20 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
         cap = V * L0
         conf = torch.empty(V, L0, L1, device=dev)
-        cws = torch.empty(hip.load().ophip_coarse_workspace_floats(V, L0, L1), device=dev)
+        ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
+        cws = torch.empty(ws_floats(V, L0, L1), device=dev)
         ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
         mconf, mk0, mk1c = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
         gt_mask = torch.empty(cap, dtype=torch.bool, device=dev)
         count = torch.zeros(4, dtype=torch.int32, device=dev)
-        call("ophip_coarse_match_2d", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]), float(mc["thr"]),
-             int(mc["border_rm"]), float(scale), P(conf), P(cws), P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64),
-             P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64), P(gt_mask, torch.bool), P(count, torch.int32), 3, S)
+        outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
+                P(gt_mask, torch.bool), P(count, torch.int32))
+        if self.sinkhorn:
+            call("ophip_coarse_match_2d_sinkhorn", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"], int(mc["skh_iters"]),
+                 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, S)
+        else:
+            call("ophip_coarse_match_2d", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]), float(mc["thr"]),
+                 int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, S)
         K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
         b_ids, i_ids, j_ids = ids[0][:K], ids[1][:K], ids[2][:K]
         mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
