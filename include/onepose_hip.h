@@ -404,6 +404,41 @@ int ophip_rows_layernorm128(const float* x, const float* gamma, const float* bet
 int ophip_fine2_match(const float* f0, const float* f1, const float* mkpts1_c, int K, int W, float scale, float* expec_f, float* mkpts1_f,
                       void* stream);
 
+/* The SfM calls of the same matcher (loftr_for_sfm/loftr.py:79-167: the SfM coarse matcher passes scale0 / scale1, the refinement and
+ * feature extractor passes COLMAP's coarse matches mkpts0_c / mkpts1_c and asks for backbone features at the refined keypoints):
+ *   ophip_fine2_match_scaled  ophip_fine2_match with per-pair scales: mkpts1_f = mkpts1_c + (expectation * (W / 2)) * (scale * scale1[b])
+ *                             (scale = image h / fine h; scale1 [B][2] applied as given, component 0 on x; scale1_bstride floats between
+ *                             pairs, 0 = one pair of scales for all), each product rounded in f32, the sum in the keypoints' dtype:
+ *                             mkpts1_c / mkpts1_f are float, or double when mk_double != 0
+ *   ophip_loftr_coarse_ids    the fine-only branch's cell ids of provided matches, both images in one launch: clip mkpts*_c IN PLACE
+ *                             (x to [0, w_i - 2], y to [0, h_i - 2]), divide by coarse_scale * scale[0][[1, 0]] (scale NULL: 1), round half
+ *                             to even, id = y * w_c + x truncated to int64 -> i_ids / j_ids [K].  Keypoints [K][2] float, or double
+ *                             (mk*_double).  Ids outside [0, h_c * w_c) (and NaN keypoints) are counted into *bad_count (zeroed by the
+ *                             call): the caller must not gather with them.  An x that rounds to w_c wraps into the next row, as in the
+ *                             reference.
+ *   ophip_sample_features     sample_feature_from_featuremap: F.grid_sample(align_corners=True, zero padding) of channels-last maps
+ *                             [h * w][C] (C 128 or 256) at keypoints [K][2] (float or double) normalised as
+ *                             ((k - 0.5 + 0.5) / (extent - 1)) * 2 - 1 in their own dtype, extent = scale[0 / 1] * (H / W), then cast to
+ *                             float; nearest (round half to even) or bilinear -> out [K][C] f32.  Up to OPHIP_SAMPLE_MAX_JOBS jobs in
+ *                             one launch, one wave per keypoint; map and out 16-byte aligned. */
+#define OPHIP_SAMPLE_MAX_JOBS 4
+typedef struct {
+    const float* map;           /* [h * w][C] channels-last */
+    const void* keypoints;      /* [K][2] (x, y) in image pixels */
+    const float* scale;         /* [2] (h factor, w factor) */
+    float* out;                 /* [K][C] */
+    int h, w, C, K;
+    int H, W;                   /* image size the keypoints refer to (before the scale) */
+    int keypoints_double, nearest;
+} ophip_sample_job;
+int ophip_fine2_match_scaled(const float* f0, const float* f1, const void* mkpts1_c, int mk_double, const long long* b_ids,
+                             const float* scale1, long long scale1_bstride, int K, int W, float scale, float* expec_f, void* mkpts1_f,
+                             void* stream);
+int ophip_loftr_coarse_ids(void* mkpts0, int mk0_double, void* mkpts1, int mk1_double, int K, int h0i, int w0i, int h1i, int w1i,
+                           int h0c, int w0c, int h1c, int w1c, float coarse_scale, const float* scale0, const float* scale1,
+                           long long* i_ids, long long* j_ids, int* bad_count, void* stream);
+int ophip_sample_features(const ophip_sample_job* jobs, int n_jobs, void* stream);
+
 /* Coarse encoder layer with FULL (softmax) attention (loftr_coarse.attention = "full": transformer.py:29-38, linear_attention.py:64-95):
  * msg = softmax(Q K^T / sqrt(32)) V per head (8 heads of 32), then the same merge / LayerNorm / MLP / LayerNorm / residual tail as the
  * linear layer.  Same stream wiring and in-place rule as ophip_encoder_layer; wpack is the f32 layer block of ophip_encoder_layer.

@@ -81,9 +81,11 @@ class HipBackbone:
         return out if planes else o32
 
     @torch.no_grad()
-    def forward(self, blocks: dict, image: torch.Tensor, pe_table: torch.Tensor | None = None):
+    def forward(self, blocks: dict, image: torch.Tensor, pe_table: torch.Tensor | None = None, return_coarse_map: bool = False):
         """``image [B, 1, H, W]`` float32 on the HIP device, H and W multiples of 8.  Returns ``(feat_c, feat_f)`` as
-        described in the module docstring; ``pe_table [H/8 * W/8, 256]`` is added to ``feat_c`` when given."""
+        described in the module docstring; ``pe_table [H/8 * W/8, 256]`` is added to ``feat_c`` when given.
+        ``return_coarse_map``: also return the coarse map WITHOUT the positional encoding, ``[B, H/8 * W/8, 256]`` (the map the
+        FPN upsamples; ``feat_c`` itself when no table is given), as a third element."""
         if not image.is_cuda:
             raise hip.HipLibraryError("the HIP backbone needs device tensors (no CPU fallback)")
         hip.load()
@@ -122,4 +124,6 @@ class HipBackbone:
         q1 = self._conv(blocks, "l1out2.0", p1, act=LEAKY)
         feat_f = self._conv(blocks, "l1out2.3", q1, planes=False, f32_channels=blocks["l1out2.3"][2])
         hc, wc, hf, wf = H // 8, W // 8, H // 2, W // 2
+        if return_coarse_map:
+            return feat_c.view(B, hc * wc, C3), feat_f.view(B, hf * wf, feat_f.shape[3]), x3o.view(B, hc * wc, C3)
         return feat_c.view(B, hc * wc, C3), feat_f.view(B, hf * wf, feat_f.shape[3])

@@ -182,13 +182,31 @@ __global__ __launch_bounds__(256) void rows_layernorm_kernel(LnArgs p) {
 // ---- FineMatching: centre token of image 0's window against image 1's window -> heat-map expectation ----------------------------
 struct MatchArgs {
     const float *f0, *f1;       // [K][WW][CF]
-    const float* mk1_c;         // [K][2]
+    const void* mk1_c;          // [K][2] (float; the scaled form: T)
     int K, W;
-    float scale;                // (W / 2) * (image height / fine height)
+    float scale;                // (W / 2) * (image height / fine height); the scaled form: image height / fine height
     float* expec;               // [K][3]
-    float* mk1_f;               // [K][2]
+    void* mk1_f;                // [K][2] (as mk1_c)
+    const long long* b_ids;     // the scaled form: [K] pair of every match
+    const float* scale1;        // the scaled form: [B][2] per-pair scales, component 0 multiplies x (applied as given)
+    long long scale1_bs;        // floats between pairs' scales (0: one pair of scales for every match)
 };
 
+// mkpts1_f = mkpts1_c + (coords * (W // 2)) * (scale * scale1[b_ids]) (fine_matching.py, 'scale0' in data): each product rounded in
+// f32 as torch does, the sum in the keypoints' dtype; no FMA, so that the per-pair form matches the reference bit for bit
+template <typename T>
+__device__ __forceinline__ void fine2_match_store_scaled(const MatchArgs& p, int m, float ex, float ey) {
+#pragma clang fp contract(off)
+    const float* s = p.scale1 + (size_t)p.b_ids[m] * p.scale1_bs;
+    const float half = (float)(p.W / 2);
+    const float dx = (ex * half) * (p.scale * s[0]), dy = (ey * half) * (p.scale * s[1]);
+    const T* mk = static_cast<const T*>(p.mk1_c);
+    T* out = static_cast<T*>(p.mk1_f);
+    out[2 * m] = mk[2 * m] + (T)dx;
+    out[2 * m + 1] = mk[2 * m + 1] + (T)dy;
+}
+
+template <typename T, bool SCALED>
 __global__ __launch_bounds__(128) void fine2_match_kernel(MatchArgs p) {
     __shared__ float sim[128];
     __shared__ float cen[CF];
@@ -220,8 +238,14 @@ __global__ __launch_bounds__(128) void fine2_match_kernel(MatchArgs p) {
             const float vx = ex2 - ex * ex, vy = ey2 - ey * ey;
             p.expec[3 * m] = ex; p.expec[3 * m + 1] = ey;
             p.expec[3 * m + 2] = sqrtf(fmaxf(vx, 1e-10f)) + sqrtf(fmaxf(vy, 1e-10f));
-            p.mk1_f[2 * m] = p.mk1_c[2 * m] + ex * p.scale;
-            p.mk1_f[2 * m + 1] = p.mk1_c[2 * m + 1] + ey * p.scale;
+            if constexpr (SCALED) {
+                fine2_match_store_scaled<T>(p, m, ex, ey);
+            } else {
+                const float* mk1_c = static_cast<const float*>(p.mk1_c);
+                float* mk1_f = static_cast<float*>(p.mk1_f);
+                mk1_f[2 * m] = mk1_c[2 * m] + ex * p.scale;
+                mk1_f[2 * m + 1] = mk1_c[2 * m + 1] + ey * p.scale;
+            }
         }
     }
 }
@@ -308,8 +332,23 @@ extern "C" int ophip_fine2_match(const float* f0, const float* f1, const float* 
     if (K < 0 || W < 3 || (W & 1) == 0 || W * W > 128) return ophip_bad_arg(__func__, "bad sizes (odd window, 3 .. 11)");
     if (K == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
-    MatchArgs a{f0, f1, mkpts1_c, K, W, scale, expec_f, mkpts1_f};
-    OPHIP_LAUNCH("fine2_match", stream, fine2_match_kernel, dim3(K), dim3(128), 0, stream, a);
+    MatchArgs a{f0, f1, mkpts1_c, K, W, scale, expec_f, mkpts1_f, nullptr, nullptr, 0};
+    OPHIP_LAUNCH("fine2_match", stream, (fine2_match_kernel<float, false>), dim3(K), dim3(128), 0, stream, a);
+    OPHIP_CHECK_LAUNCH();
+    return 0;
+}
+
+// FineMatching with per-pair scales (the SfM matcher: 'scale0' in data) and float or double keypoints (mkpts1_f in mkpts1_c's dtype)
+extern "C" int ophip_fine2_match_scaled(const float* f0, const float* f1, const void* mkpts1_c, int mk_double, const long long* b_ids,
+                                        const float* scale1, long long scale1_bstride, int K, int W, float scale, float* expec_f,
+                                        void* mkpts1_f, void* stream_) {
+    if (!f0 || !f1 || !mkpts1_c || !expec_f || !mkpts1_f || !b_ids || !scale1) return ophip_bad_arg(__func__, "null pointer");
+    if (K < 0 || W < 3 || (W & 1) == 0 || W * W > 128 || scale1_bstride < 0) return ophip_bad_arg(__func__, "bad sizes (odd window, 3 .. 11)");
+    if (K == 0) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    MatchArgs a{f0, f1, mkpts1_c, K, W, scale, expec_f, mkpts1_f, b_ids, scale1, scale1_bstride};
+    if (mk_double) OPHIP_LAUNCH("fine2_match", stream, (fine2_match_kernel<double, true>), dim3(K), dim3(128), 0, stream, a);
+    else OPHIP_LAUNCH("fine2_match", stream, (fine2_match_kernel<float, true>), dim3(K), dim3(128), 0, stream, a);
     OPHIP_CHECK_LAUNCH();
     return 0;
 }

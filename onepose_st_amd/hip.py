@@ -22,6 +22,15 @@ c_ll = ctypes.c_longlong
 
 
 
+class SampleJob(ctypes.Structure):
+    """``ophip_sample_job`` (include/onepose_hip.h): one map / keypoint set of ``ophip_sample_features``"""
+    _fields_ = [("map", ctypes.c_void_p), ("keypoints", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("h", c_i), ("w", c_i), ("C", c_i), ("K", c_i), ("H", c_i), ("W", c_i), ("keypoints_double", c_i), ("nearest", c_i)]
+
+
+SAMPLE_MAX_JOBS = 4     # OPHIP_SAMPLE_MAX_JOBS
+
+
 class FrameDesc(ctypes.Structure):
     """``ophip_frame_desc`` (include/onepose_hip.h)"""
     _fields_ = [("B", c_i), ("N", c_i), ("M", c_i), ("hc", c_i), ("wc", c_i), ("hf", c_i), ("wf", c_i), ("cf", c_i),
@@ -137,6 +146,11 @@ _SIGNATURES = {
     "ophip_encoder_full_stream_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "ophip_encoder_layer_full_x3_stream": (c_i, [c_f, c_ll, c_f, c_ll, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
     "ophip_fine2_full_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
+    "ophip_fine2_match_scaled": (c_i, [c_f, c_f, ctypes.c_void_p, c_i, c_f, c_f, c_ll, c_i, c_i, ctypes.c_float, c_f, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "ophip_loftr_coarse_ids": (c_i, [ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_float,
+                                     c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
+    "ophip_sample_features": (c_i, [ctypes.POINTER(SampleJob), c_i, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -27,8 +27,18 @@ once; the fine layers call ``ophip_fine2_full_attention`` (W x W windows, softma
 (LoFTR's ``CoarseMatching`` sinkhorn branch, SuperGlue's ``log_optimal_transport``, ``skh_iters`` iterations, ``skh_prefilter``):
 ``ophip_coarse_match_2d_sinkhorn``.  Such a model has one more parameter, ``coarse_matching.bin_score`` (0-d, ``skh_init_bin_score``).
 
-Masks / scales / provided coarse matches (``mask0``, ``scale0``, ``mkpts0_c`` inputs) and the feature-extraction kwargs are the
-SfM pipeline's (out of scope) and raise ``NotImplementedError``.  No CPU fallback.
+The SfM calls (``loftr_for_sfm/loftr.py:79-167``):
+
+* ``scale0`` / ``scale1`` (float32 ``[V, 2]``, ``scale1`` also ``[1, 2]`` when ``image1`` has batch 1; the reference's [h, w] factors,
+  applied as given on the coarse path and in FineMatching): ``mkpts*_c`` times ``scale[b]`` on the device, ``ophip_fine2_match_scaled``;
+* provided coarse matches ``mkpts0_c`` / ``mkpts1_c`` (float32 / float64 ``[K, 2]``, one pair): the fine-only branch --
+  ``ophip_loftr_coarse_ids`` clips the caller's tensors in place and rounds them to cells (``IndexError`` for an id past the grid when
+  the fine stage runs), no coarse transformer, ``mconf`` int64 ones, no ``conf_matrix``;
+* ``extract_coarse_feature`` / ``extract_fine_feature``: ``feat_coarse_b_{0,1} [K, 256]`` (nearest) and ``feat_ext{0,1} [K, 128]``
+  (bilinear) sampled from the backbone maps before the positional encoding at ``mkpts*_f``, one ``ophip_sample_features`` launch.
+
+Padding masks (``mask0`` / ``mask1``), malformed scale / keypoint tensors, a tensor without its partner, V > 1 with provided matches or
+extraction, and coarse extraction with a ``feature_hook`` raise ``NotImplementedError`` before anything runs.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -198,18 +208,52 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             x1 = x1.expand(V, -1, -1).contiguous()
         return x0, x1
 
+    def _check_inputs(self, data, kwargs):
+        """the input forms outside what the kernels cover raise before anything runs; -> (fine_only, has_scales, extract_c, extract_f)"""
+        for k in ("mask0", "mask1"):
+            if k in data:
+                raise NotImplementedError(f"'{k}' input: padding masks are not supported")
+        V, V1 = data["image0"].size(0), data["image1"].size(0)
+        ext_c, ext_f = bool(kwargs.get("extract_coarse_feature", False)), bool(kwargs.get("extract_fine_feature", False))
+        has_s = "scale0" in data
+        if has_s != ("scale1" in data):
+            raise NotImplementedError("'scale0' and 'scale1' come together")
+        if has_s:
+            for k, rows in (("scale0", (V,)), ("scale1", (V, 1) if V1 == 1 else (V,))):
+                t = data[k]
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 2 or t.shape[0] not in rows:
+                    raise NotImplementedError(f"'{k}': a float32 tensor [{V}, 2] ([1, 2] for scale1 when image1 has batch 1)")
+        fine_only = "mkpts0_c" in data
+        if fine_only != ("mkpts1_c" in data):
+            raise NotImplementedError("'mkpts0_c' and 'mkpts1_c' come together")
+        if fine_only:
+            k0, k1 = data["mkpts0_c"], data["mkpts1_c"]
+            for t in (k0, k1):
+                if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.float64) or t.dim() != 2 or t.shape[1] != 2:
+                    raise NotImplementedError("provided coarse matches: float32 / float64 tensors [K, 2]")
+            if k0.shape[0] != k1.shape[0]:
+                raise NotImplementedError("'mkpts0_c' and 'mkpts1_c' must hold the same number of matches")
+            if V != 1 or V1 != 1:
+                raise NotImplementedError("provided coarse matches: one pair per call (the reference's b_ids are all 0)")
+        if ext_c or ext_f:
+            if V != 1 or V1 != 1:
+                raise NotImplementedError("feature extraction: one pair per call (the reference squeezes scale0 to [2])")
+            if ext_c and self.feature_hook is not None:
+                raise NotImplementedError("extract_coarse_feature with a feature_hook: the hook's coarse rows carry the positional "
+                                          "encoding, the reference samples the map before it")
+            if not has_s:
+                raise KeyError("scale0")
+        tensors = [data["image0"], data["image1"]] + [data[k] for k in ("scale0", "scale1", "mkpts0_c", "mkpts1_c") if k in data]
+        if not all(t.is_cuda for t in tensors):
+            raise hip.HipLibraryError("LoFTR_for_OnePose_Plus runs on the HIP device only (no CPU fallback)")
+        return fine_only, has_s, ext_c, ext_f
+
     @torch.no_grad()
     def forward(self, data, **kwargs):
         if self.training:
             raise NotImplementedError("inference only")
-        if kwargs.get("extract_coarse_feature") or kwargs.get("extract_fine_feature"):
-            raise NotImplementedError("feature extraction kwargs belong to the SfM pipeline (out of scope)")
-        for k in ("mask0", "mask1", "scale0", "scale1", "mkpts0_c", "mkpts1_c"):
-            if k in data:
-                raise NotImplementedError(f"'{k}' input: not used by the object detector (local_feature_2D_detector.py:93-94)")
+        fine_only, has_s, ext_c, ext_f = self._check_inputs(data, kwargs)
         img0, img1 = data["image0"], data["image1"]
-        if not img0.is_cuda or not img1.is_cuda:
-            raise hip.HipLibraryError("LoFTR_for_OnePose_Plus runs on the HIP device only (no CPU fallback)")
         V = img0.size(0)
         if img1.size(0) not in (1, V):
             raise ValueError(f"image1: batch {img1.size(0)} against image0's {V} (expected 1 -- one query for every pair -- or {V})")
@@ -223,17 +267,19 @@ class LoFTR_for_OnePose_Plus(nn.Module):
 
         def features(img):
             H, W = img.shape[2:]
-            fc, ff = bbk.forward(Wb["backbone"], img, self._pe_table(H // 8, W // 8, dev))
-            return fc, ff, (H // 8, W // 8), (H // 2, W // 2)
+            fc, ff, fm = bbk.forward(Wb["backbone"], img, self._pe_table(H // 8, W // 8, dev), return_coarse_map=True)
+            return fc, ff, fm, (H // 8, W // 8), (H // 2, W // 2)
         if img0.shape[2:] == img1.shape[2:]:
-            fc, ff, hwc, hwf = features(torch.cat([img0, img1], 0))
-            fc0, fc1, ff0, ff1 = fc[:V], fc[V:], ff[:V], ff[V:]
+            fc, ff, fm, hwc, hwf = features(torch.cat([img0, img1], 0))
+            fc0, fc1, ff0, ff1, fm0, fm1 = fc[:V], fc[V:], ff[:V], ff[V:], fm[:V], fm[V:]
             hw0_c = hw1_c = hwc
             hw0_f = hw1_f = hwf
         else:
-            fc0, ff0, hw0_c, hw0_f = features(img0)
-            fc1, ff1, hw1_c, hw1_f = features(img1)
+            fc0, ff0, fm0, hw0_c, hw0_f = features(img0)
+            fc1, ff1, fm1, hw1_c, hw1_f = features(img1)
         data.update({"hw0_c": torch.Size(hw0_c), "hw1_c": torch.Size(hw1_c), "hw0_f": torch.Size(hw0_f), "hw1_f": torch.Size(hw1_f)})
+        if kwargs.get("_debug"):                       # the backbone's maps before the positional encoding / the hook
+            data.update({"_bb_c0": fm0, "_bb_c1": fm1, "_bb_f0": ff0, "_bb_f1": ff1, "_enc_c0": fc0, "_enc_c1": fc1})
         if self.feature_hook is not None:
             # one pair: the fine maps without the batch axis (the hook's form since round 3); a batch: everything with it
             if V == 1:
@@ -245,49 +291,84 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                 raise ValueError("feature_hook: batch sizes of the returned features do not match the call")
             shared1 = fc1.shape[0] == 1 and V > 1
         L0, L1 = hw0_c[0] * hw0_c[1], hw1_c[0] * hw1_c[1]
-
-        # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
-        #      full: one one-stream launch per image and layer, the shared query read with batch stride 0 ---------------------------
-        if self.coarse_full:
-            x0, x1 = self._coarse_full(Wb["coarse"], fc0.contiguous(), fc1.contiguous(), V, L0, L1)
-        else:
-            x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, shared1, V, L0, L1)
-
-        # ---- coarse matching between the two grids -----------------------------------------------------------------------------
-        mc = self.config["match_coarse"]
         scale = img0.shape[2] / hw0_c[0]
-        ii = torch.arange(L0, device=dev)
-        pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
-        cap = V * L0
-        conf = torch.empty(V, L0, L1, device=dev)
-        ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
-        cws = torch.empty(ws_floats(V, L0, L1), device=dev)
-        ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
-        mconf, mk0, mk1c = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-        gt_mask = torch.empty(cap, dtype=torch.bool, device=dev)
-        count = torch.zeros(4, dtype=torch.int32, device=dev)
-        outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
-                P(gt_mask, torch.bool), P(count, torch.int32))
-        if self.sinkhorn:
-            call("ophip_coarse_match_2d_sinkhorn", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"], int(mc["skh_iters"]),
-                 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, S)
+        s0 = data["scale0"].contiguous() if has_s else None
+        s1 = data["scale1"].contiguous() if has_s else None
+
+        if fine_only:
+            # ---- provided coarse matches (loftr.py:79-115): clip in place, round to cells; no coarse transformer, no matching -----------
+            mk0c, mk1c = data["mkpts0_c"], data["mkpts1_c"]
+            K = mk0c.shape[0]
+            b_ids = torch.zeros(K, dtype=torch.int64, device=dev)
+            i_ids, j_ids = torch.empty(K, dtype=torch.int64, device=dev), torch.empty(K, dtype=torch.int64, device=dev)
+            bad = torch.empty(1, dtype=torch.int32, device=dev)
+            a0, a1 = mk0c.contiguous(), mk1c.contiguous()
+            call("ophip_loftr_coarse_ids", P(a0, None), int(a0.dtype == torch.float64), P(a1, None), int(a1.dtype == torch.float64), K,
+                 img0.shape[2], img0.shape[3], img1.shape[2], img1.shape[3], hw0_c[0], hw0_c[1], hw1_c[0], hw1_c[1], float(scale),
+                 P(s0), P(s1), P(i_ids, torch.int64), P(j_ids, torch.int64), P(bad, torch.int32), S)
+            for a, t in ((a0, mk0c), (a1, mk1c)):
+                if a.data_ptr() != t.data_ptr():
+                    t.copy_(a)
+            nbad = int(bad.item()) if self.enable_fine_matching else 0      # only the fine stage indexes the maps with the ids
+            if nbad:
+                raise IndexError(f"{nbad} provided coarse keypoint(s) round to a cell outside the coarse grid")
+            data.update({"m_bids": b_ids, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "mconf": torch.ones_like(b_ids)})
+            x0 = x1 = None
         else:
-            call("ophip_coarse_match_2d", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]), float(mc["thr"]),
-                 int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, S)
-        K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
-        b_ids, i_ids, j_ids = ids[0][:K], ids[1][:K], ids[2][:K]
-        mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
-        data.update({"conf_matrix": conf, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "m_bids": ids[3][:K], "gt_mask": gt_mask[:K],
-                     "mconf": mconf[:K], "mkpts0_c": mk0c, "mkpts1_c": mk1c})
-        if not self.enable_fine_matching:
+            # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
+            #      full: one one-stream launch per image and layer, the shared query read with batch stride 0 -----------------------
+            if self.coarse_full:
+                x0, x1 = self._coarse_full(Wb["coarse"], fc0.contiguous(), fc1.contiguous(), V, L0, L1)
+            else:
+                x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, shared1, V, L0, L1)
+
+            # ---- coarse matching between the two grids -------------------------------------------------------------------------
+            mc = self.config["match_coarse"]
+            ii = torch.arange(L0, device=dev)
+            pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
+            cap = V * L0
+            conf = torch.empty(V, L0, L1, device=dev)
+            ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
+            cws = torch.empty(ws_floats(V, L0, L1), device=dev)
+            ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
+            mconf, mk0, mk1c = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
+            gt_mask = torch.empty(cap, dtype=torch.bool, device=dev)
+            count = torch.zeros(4, dtype=torch.int32, device=dev)
+            outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
+                    P(gt_mask, torch.bool), P(count, torch.int32))
+            if self.sinkhorn:
+                call("ophip_coarse_match_2d_sinkhorn", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"], int(mc["skh_iters"]),
+                     1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, S)
+            else:
+                call("ophip_coarse_match_2d", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]), float(mc["thr"]),
+                     int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, S)
+            K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
+            b_ids, i_ids, j_ids = ids[0][:K], ids[1][:K], ids[2][:K]
+            mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
+            if has_s:                                          # get_coarse_match: cell * (scale * scale0[b_ids]); scale = 8 is a power of two
+                mk0c = mk0c * s0[b_ids]
+                mk1c = mk1c * (s1[b_ids] if s1.shape[0] > 1 else s1)
+            data.update({"conf_matrix": conf, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "m_bids": ids[3][:K], "gt_mask": gt_mask[:K],
+                         "mconf": mconf[:K], "mkpts0_c": mk0c, "mkpts1_c": mk1c})
+        if self.enable_fine_matching:
+            self._fine(Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, img0.shape[2], s1,
+                       scaled=has_s or fine_only, debug=kwargs.get("_debug"))
+        else:
             data.update({"mkpts0_f": mk0c, "mkpts1_f": mk1c})
-            return
+        if kwargs.get("_debug") and x0 is not None:
+            data["_feat_c0"], data["_feat_c1"] = x0, x1
+        if ext_c or ext_f:
+            self._extract(data, ext_c, ext_f, fm0, fm1, ff0, ff1, hw0_c, hw1_c, hw0_f, hw1_f, s0, s1)
+
+    def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug):
+        """fine stage (windows on both images, two-stream fine transformer, correlation + soft-argmax) on the matches' cells"""
+        call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        dev = ff0.device
         Wf = int(self.config["fine_window_size"])
         WW = Wf * Wf
         if K == 0:
             data.update({"expec_f": torch.empty(0, 3, device=dev), "mkpts0_f": mk0c, "mkpts1_f": mk1c})
             return
-        # ---- fine stage: windows on both images, two-stream fine transformer, correlation + soft-argmax ------------------------
         stride = hw0_f[0] // hw0_c[0]
         f0, f1 = torch.empty(K, WW, 128, device=dev), torch.empty(K, WW, 128, device=dev)
         ff0c, ff1c = ff0.contiguous(), ff1.contiguous()          # [V or 1][hf * wf][128] channels-last
@@ -320,11 +401,45 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             else:
                 f0 = fine_layer(f0, f1, w)
                 f1 = fine_layer(f1, f0, w)
-        expec, mk1f = torch.empty(K, 3, device=dev), torch.empty(K, 2, device=dev)
-        call("ophip_fine2_match", P(f0), P(f1), P(mk1c), K, Wf, float((Wf // 2) * (img0.shape[2] / hw0_f[0])), P(expec), P(mk1f), S)
+        expec = torch.empty(K, 3, device=dev)
+        if scaled:
+            # FineMatching with 'scale0' in data: mkpts1_c + coords * (W // 2) * (scale * scale1[b_ids]), in mkpts1_c's dtype.  The
+            # fine-only branch without scales uses the plain scale: the same arithmetic with unit scales
+            s1 = s1 if s1 is not None else torch.ones(1, 2, device=dev)
+            mk1c_ = mk1c.contiguous()
+            mk1f = torch.empty(K, 2, dtype=mk1c.dtype, device=dev)
+            call("ophip_fine2_match_scaled", P(f0), P(f1), P(mk1c_, None), int(mk1c.dtype == torch.float64), P(b_ids, torch.int64), P(s1),
+                 2 if s1.shape[0] > 1 else 0, K, Wf, float(h0i / hw0_f[0]), P(expec), P(mk1f, None), S)
+        else:
+            mk1f = torch.empty(K, 2, device=dev)
+            call("ophip_fine2_match", P(f0), P(f1), P(mk1c), K, Wf, float((Wf // 2) * (h0i / hw0_f[0])), P(expec), P(mk1f), S)
         data.update({"expec_f": expec, "mkpts0_f": mk0c, "mkpts1_f": mk1f})
-        if kwargs.get("_debug"):
-            data["_fine_f0"], data["_fine_f1"], data["_feat_c0"], data["_feat_c1"] = f0, f1, x0, x1
+        if debug:
+            data["_fine_f0"], data["_fine_f1"] = f0, f1
+
+    def _extract(self, data, ext_c, ext_f, fm0, fm1, ff0, ff1, hw0_c, hw1_c, hw0_f, hw1_f, s0, s1):
+        """loftr.py:131-167: backbone features at mkpts*_f -- the coarse map before the positional encoding (nearest) and the fine map
+        (bilinear), keypoints normalised by scale * hw_i; one ``ophip_sample_features`` launch for all of them"""
+        dev = fm0.device
+        jobs, outs = [], {}
+        hw0_i, hw1_i = data["hw0_i"], data["hw1_i"]
+        k0, k1 = data["mkpts0_f"].contiguous(), data["mkpts1_f"].contiguous()
+        todo = []
+        if ext_c:
+            todo += [("feat_coarse_b_0", fm0, hw0_c, 256, k0, s0, hw0_i, 1), ("feat_coarse_b_1", fm1, hw1_c, 256, k1, s1, hw1_i, 1)]
+        if ext_f:
+            todo += [("feat_ext0", ff0, hw0_f, 128, k0, s0, hw0_i, 0), ("feat_ext1", ff1, hw1_f, 128, k1, s1, hw1_i, 0)]
+        for name, fmap, hw, C, kp, sc, hw_i, nearest in todo:
+            fmap = fmap.contiguous()
+            if tuple(fmap.shape[-2:]) != (hw[0] * hw[1], C):
+                raise ValueError(f"{name}: map of shape {tuple(fmap.shape)}, expected [{hw[0] * hw[1]}, {C}]")
+            out = torch.empty(kp.shape[0], C, device=dev)
+            outs[name] = (out, fmap, kp, sc)            # keep the operands alive until the launch is enqueued
+            jobs.append(hip.SampleJob(fmap.data_ptr(), kp.data_ptr(), sc.data_ptr(), out.data_ptr(), hw[0], hw[1], C, kp.shape[0],
+                                      hw_i[0], hw_i[1], int(kp.dtype == torch.float64), nearest))
+        arr = (hip.SampleJob * len(jobs))(*jobs)
+        hip.call("ophip_sample_features", arr, len(jobs), hip.stream_handle())
+        data.update({name: o[0] for name, o in outs.items()})
 
 
 def build_2D_match_model(args: dict) -> LoFTR_for_OnePose_Plus:
