@@ -489,6 +489,37 @@ int ophip_fine2_full_attention(const float* q, const float* k, const float* v, i
  * bilinear resize by S / (x1 - x0) about the crop centre, zero border, rounded to uint8 levels). */
 int ophip_crop_resize_gray(const unsigned char* image, int H, int W, int x0, int y0, int x1, int y1, int S, float* out, void* stream);
 
+/* The keypoint-free SfM post-optimisation's depth refinement (post_optimization/optimizer/optimizer.py:221-236 driving
+ * first_order_solver.py:6-172 with residual.py:6-78 / residual_utils.py:3-52), float64 throughout:
+ *   ophip_postopt_workspace_bytes  bytes of the refine workspace for L residual rows, P tracks and max_steps steps (0: bad sizes)
+ *   ophip_postopt_refine           P tracks, track p owning rows track_offsets[p] .. track_offsets[p + 1] - 1 (offsets [P + 1], every track
+ *                                  at least one row, offsets[P] == L).  Per row: intrinsic0 / intrinsic1 [L][3][3], mkpts0_c, mkpts1_f
+ *                                  [L][2], left_idx / right_idx [L] into angle_axis [F][6] (so3_log_map(R) | t of each frame's
+ *                                  world-to-camera pose).  A prep kernel folds every row into h(d) = d * a + b (pose0 inverted through
+ *                                  pytorch3d's so3_exp_map, a general 3x3 inverse and so3_log_map; AngleAxisRotatePoint; + 1e-4 on z);
+ *                                  then max_steps step kernels are enqueued with no host synchronisation.  Step i evaluates
+ *                                  r = h[0:2] / h[2] - mkpts1_f at the current depths, writes loss[i] = sum(0.5 r^2), and updates depth
+ *                                  [P] IN PLACE with torch.optim.Adam's single-tensor arithmetic (beta1, beta2, eps; step_table [max_steps][2]
+ *                                  holds step_size = lr / (1 - beta1^(i+1)) and (1 - beta2^(i+1)) ** 0.5 as Python computes them).  For
+ *                                  i >= 1 it stops once (loss[i-1] - loss[i]) / loss[i-1] < 1e-4 and i > 0.2 * max_steps (NaN never stops):
+ *                                  later steps exit at once.  *steps_run = steps executed; the reference's final residual is
+ *                                  loss[*steps_run - 1].  residuals (optional, [L][2], 16-byte aligned): the residuals of the last
+ *                                  evaluated depths.  Frame indices outside [0, F) yield NaN rows.  workspace 256-byte aligned.
+ *   ophip_postopt_points_from_depth  the caller's depth-to-world update (dataset/coarse_colmap_dataset.py:353-380): points [N][3] =
+ *                                  inv(T) applied to K^-1 ([x, y, 1] * depth), T = [[R, t], [0, 0, 0, 1]] inverted as a general 4x4;
+ *                                  keypoints [N][2], depth [N], frame_idx [N] into K / R [F][3][3], t [F][3]
+ *   ophip_postopt_project_points   its reprojection (coarse_colmap_dataset.py:404-419): keypoints [N][2] = xy / (z + 1e-4) of
+ *                                  K (R X + t), X = points [N][3].  Frame indices outside [0, F) yield NaN. */
+size_t ophip_postopt_workspace_bytes(long long L, int P, int max_steps);
+int ophip_postopt_refine(double* depth, const long long* track_offsets, int P, long long L, const double* intrinsic0, const double* intrinsic1,
+                         const double* mkpts0_c, const double* mkpts1_f, const long long* left_idx, const long long* right_idx,
+                         const double* angle_axis, int F, const double* step_table, int max_steps, double beta1, double beta2, double eps,
+                         double* loss, int* steps_run, double* residuals, void* workspace, size_t workspace_bytes, void* stream);
+int ophip_postopt_points_from_depth(const double* keypoints, const double* depth, const long long* frame_idx, int N, const double* K,
+                                    const double* R, const double* t, int F, double* points, void* stream);
+int ophip_postopt_project_points(const double* points, const long long* frame_idx, int N, const double* K, const double* R, const double* t,
+                                 int F, double* keypoints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,15 @@ _SIGNATURES = {
     "ophip_loftr_coarse_ids": (c_i, [ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_float,
                                      c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
     "ophip_sample_features": (c_i, [ctypes.POINTER(SampleJob), c_i, ctypes.c_void_p]),
+    "ophip_postopt_workspace_bytes": (ctypes.c_size_t, [c_ll, c_i, c_i]),
+    "ophip_postopt_refine": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, c_ll, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, c_i,
+                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "ophip_postopt_points_from_depth": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p]),
+    "ophip_postopt_project_points": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i,
+                                           ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from .backbone import build_backbone
@@ -242,3 +243,80 @@ HARD_PROFILE = dict(noise=0.1, noise_hi=4.0, wrong_frac=0.35)
 
 def workload_kwargs(name: str) -> dict:
     return dict(HARD_PROFILE) if name.endswith("_hard") else {}
+
+
+# ----------------------------------------------------------------------------------------------
+# SfM post-optimisation tracks
+# ----------------------------------------------------------------------------------------------
+
+def _rotation_in(gen, lo: float, hi: float) -> torch.Tensor:
+    """A random rotation whose angle lies in [lo, hi] (Rodrigues, float64)."""
+    axis = torch.randn(3, generator=gen, dtype=torch.float64)
+    axis = axis / axis.norm()
+    ang = lo + float(torch.rand(1, generator=gen, dtype=torch.float64)) * (hi - lo)
+    kx = torch.tensor([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]], dtype=torch.float64)
+    return torch.eye(3, dtype=torch.float64) + math.sin(ang) * kx + (1 - math.cos(ang)) * (kx @ kx)
+
+
+def make_synthetic_sfm_tracks(seed: int = 0, n_frames: int = 12, n_tracks: int = 200, mean_len: int = 12, n_single: int = 3,
+                              long_len: int = 1200, noise_px: float = 0.5, depth_noise: float = 0.03) -> dict:
+    """Flat inputs of the SfM depth refinement (post_optimization/optimizer/optimizer.py after its padding removal), on the CPU.
+
+    ``n_frames`` cameras ring a unit-cube object at distance ~3 with world-to-camera rotations of angle in [0.05, pi - 0.05] (the range
+    where the restated pytorch3d maps agree with every release); each track is a random point of the cube seen in a reference frame
+    and matched into random other frames (``n_query`` rows, mean ``mean_len``; the first ``n_single`` tracks have one row, the next one
+    ``long_len`` rows when ``long_len`` > 0).  ``mkpts1_f`` is the projection plus Gaussian noise of ``noise_px``, the depths are the
+    true ones times (1 + ``depth_noise`` N(0, 1)).
+
+    Returns the aggregated dict keys (``depth`` [P, 1], ``n_query`` [P], ``intrinsic0`` / ``intrinsic1`` [L, 3, 3], ``mkpts0_c`` /
+    ``mkpts1_c`` / ``mkpts1_f`` [L, 2], ``left_colmap_ids`` / ``right_colmap_ids`` [L], ``point_cloud_id`` [P]) plus ``frame_poses``
+    {colmap id: [R, t]} (numpy), per-frame ``K`` / ``R`` [F, 3, 3], ``t`` [F, 3], ``angle_axis_to_world`` [F, 6],
+    ``left_pose_idx`` / ``right_pose_idx`` [L], ``points`` [P, 3] and ``depth_true`` [P, 1]."""
+    from .postopt import convert_pose2angleAxis
+
+    assert n_frames >= 2 and n_tracks >= n_single + (1 if long_len > 0 else 0) + 1
+    gen = torch.Generator().manual_seed(int(seed))
+    f64 = torch.float64
+
+    def u(*shape, lo=0.0, hi=1.0):
+        return lo + torch.rand(*shape, generator=gen, dtype=f64) * (hi - lo)
+
+    R = torch.stack([_rotation_in(gen, 0.05, math.pi - 0.05) for _ in range(n_frames)])
+    t = torch.stack([u(n_frames, lo=-0.2, hi=0.2), u(n_frames, lo=-0.2, hi=0.2), u(n_frames, lo=2.7, hi=3.3)], 1)
+    K = torch.zeros(n_frames, 3, 3, dtype=f64)
+    K[:, 0, 0] = u(n_frames, lo=480.0, hi=560.0)
+    K[:, 1, 1] = K[:, 0, 0] * u(n_frames, lo=0.98, hi=1.02)
+    K[:, 0, 2] = u(n_frames, lo=310.0, hi=330.0)
+    K[:, 1, 2] = u(n_frames, lo=230.0, hi=250.0)
+    K[:, 2, 2] = 1.0
+    P = n_tracks
+    X = u(P, 3, lo=-0.5, hi=0.5)
+    nq = torch.randint(1, 2 * mean_len, (P,), generator=gen)
+    nq[:n_single] = 1
+    if long_len > 0:
+        nq[n_single] = long_len
+    L = int(nq.sum())
+    track = torch.repeat_interleave(torch.arange(P), nq)
+    f0 = torch.randint(0, n_frames, (P,), generator=gen)
+    left = f0[track]
+    right = torch.randint(0, n_frames - 1, (L,), generator=gen)
+    right = right + (right >= left).long()                     # any other frame, with replacement
+
+    def project(Xw, f):
+        c = (R[f] @ Xw[:, :, None]).squeeze(-1) + t[f]
+        h = (K[f] @ c[:, :, None]).squeeze(-1)
+        return h[:, :2] / h[:, 2:], c[:, 2:]
+
+    kp0, z0 = project(X, f0)
+    mk0 = (kp0 + 0.25 * torch.randn(P, 2, generator=gen, dtype=f64))[track]
+    kp1, _ = project(X[track], right)
+    mk1f = kp1 + noise_px * torch.randn(L, 2, generator=gen, dtype=f64)
+    depth = z0 * (1 + depth_noise * torch.randn(P, 1, generator=gen, dtype=f64))
+    ids = [10 + 3 * f for f in range(n_frames)]                 # colmap ids are not frame indices
+    frame_poses = {ids[f]: [R[f].numpy().copy(), t[f].numpy().copy()] for f in range(n_frames)}
+    aa = torch.from_numpy(np.concatenate([convert_pose2angleAxis(frame_poses[i]) for i in ids]))
+    idt = torch.tensor(ids, dtype=torch.int64)
+    return {"depth": depth, "n_query": nq.long(), "intrinsic0": K[left].clone(), "intrinsic1": K[right].clone(), "mkpts0_c": mk0,
+            "mkpts1_c": torch.round(mk1f / 8) * 8, "mkpts1_f": mk1f, "left_colmap_ids": idt[left], "right_colmap_ids": idt[right],
+            "point_cloud_id": 100 + 2 * torch.arange(P), "frame_poses": frame_poses, "K": K, "R": R, "t": t,
+            "angle_axis_to_world": aa, "left_pose_idx": left, "right_pose_idx": right, "points": X, "depth_true": z0}

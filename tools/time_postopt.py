@@ -1,0 +1,85 @@
+"""Time the SfM depth refinement on the device against the reference's form of it.
+
+    python tools/time_postopt.py [--tracks 5000,20000,100000] [--mean-len 20] [--ref-steps 20] [--iters 3]
+
+For each track count P (synthetic tracks of mean length ``--mean-len``, plus three single-row tracks and one of 1 200 rows), prints one
+JSON line:
+  * ``refine_ms``: HIP-event time of one ``postopt.refine_depths`` call (prep, every step, the read-back; median of ``--iters``) and
+    ``per_step_us`` = refine_ms / steps run;
+  * ``step_kernel_us``: the device time of one ``postopt_step`` launch (``ophip_timing_select``: each launch's own begin and end),
+    averaged over a run of exactly the steps that do work, and ``step_GBps`` = the bytes one step must move (64 per row, 64 per
+    track) over that time;
+  * ``ref_step_us``: one step of the oracle's autograd + ``torch.optim.Adam`` loop moved to the same GPU (the reference's form,
+    ``first_order_solver.py``), averaged over ``--ref-steps`` steps, and ``ref_total_ms`` = that times the steps run.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from onepose_st_amd import hip, postopt  # noqa: E402
+from onepose_st_amd.synthetic import make_synthetic_sfm_tracks  # noqa: E402
+from tests import postopt_oracle as po  # noqa: E402
+
+ROW_KEYS = ("depth", "n_query", "intrinsic0", "intrinsic1", "mkpts0_c", "mkpts1_f", "left_pose_idx", "right_pose_idx",
+            "angle_axis_to_world")
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tracks", default="5000,20000,100000")
+    ap.add_argument("--mean-len", type=int, default=20)
+    ap.add_argument("--ref-steps", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=3)
+    args = ap.parse_args()
+    hip.load()
+    dev = torch.device("cuda:0")
+    for P in (int(x) for x in args.tracks.split(",")):
+        data = make_synthetic_sfm_tracks(0, n_frames=40, n_tracks=P, mean_len=args.mean_len)
+        d = {k: data[k].to(dev) for k in ROW_KEYS}
+        L = int(data["n_query"].sum())
+
+        def call(max_steps=postopt.MAX_STEPS):
+            return postopt.refine_depths(*(d[k] for k in ROW_KEYS), max_steps=max_steps)
+
+        call()                                                          # warm-up
+        runs = [event_ms(call) for _ in range(args.iters)]
+        ms = statistics.median(r[0] for r in runs)
+        steps = runs[0][1]["steps"]
+        hip.timing_select("postopt_step")
+        call(steps)                                                     # every launch does work
+        n, kms = hip.timing_read()
+        hip.timing_select("")
+        step_us = kms * 1e3 / max(n, 1)
+        step_bytes = 64 * L + 64 * P
+        # the reference's form on the same GPU: autograd through the residual + torch.optim.Adam, one loss read per step
+        ref = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in data.items()}
+        po.solve_literal(ref, max_steps=2)
+        rms, _ = event_ms(lambda: po.solve_literal(ref, max_steps=args.ref_steps))
+        ref_step_us = rms * 1e3 / args.ref_steps
+        print(json.dumps({"P": P, "L": L, "mean_len": round(L / P, 2), "steps": steps, "refine_ms": round(ms, 3),
+                          "per_step_us": round(ms * 1e3 / steps, 2), "step_kernel_us": round(step_us, 2), "step_launches": n,
+                          "step_bytes": step_bytes, "step_GBps": round(step_bytes / (step_us * 1e-6) / 1e9, 1),
+                          "ref_step_us": round(ref_step_us, 1), "ref_total_ms": round(ref_step_us * steps / 1e3, 1),
+                          "speedup_per_step": round(ref_step_us / (ms * 1e3 / steps), 1)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
