@@ -1,6 +1,6 @@
 """Benchmark of the 2D-3D matching hot path (BASELINE.json metric: query frames/sec @ 7k x 4800, d256).
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload c2|c1|c4] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload c2|c1|c4] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One process per GPU over RCCL: for N > 1 either ``torch.distributed.run`` starts the ranks, or -- when ``python bench.py
 --gpus N`` is run directly -- this process starts them itself as children (``onepose_st_amd/launch.py``; the parent imports
@@ -14,16 +14,21 @@ weights + the 3D object block and broadcasts them once (RCCL) before the timed r
 frames ("scaling": "weak").  Each rank pins itself to its own slice of the host's CPUs and sizes its PnP pool from that
 slice (``onepose_st_amd/hostsize.py``).
 
+A plain run does what its headline needs and nothing else: it sets up, warms up, times the K steps, writes --dump-outputs
+and prints the line.  Everything else it can measure runs only with ``--full`` (``extra_measurements``): the side regions
+(lazy conf_matrix, the other PnP policy, matcher only, object cache, dependent sequence, no hot steps), the per-kernel regions of
+the conf stage, ``roofline.alone``, the PnP pool's ceiling, the BASELINE side legs and the CPU baseline.
+
 Rank 0 prints ONE JSON line with the driver's contract fields plus
   "roofline"      dominant kernel (attn_apply: fused Q-proj + linear attention + merge + MLP + 2 LayerNorms + the next layer's
                   K/V reduce), algorithmic FLOPs per launch / average launch duration from HIP events (dispatch timestamps of
                   every 11th launch of that kernel inside the timed region), against the dense bf16 MFMA peak (2.5 PFLOP/s);
                   "traffic" / "mfma_busy..." come from the committed counter pass and are printed only when that pass was
-                  taken on the library build that is running (source hash recorded in the pmc file)
-  "cpu_baseline"  the oracle (CPU restatement of the reference, torch fp32) timed on this box's host cores on a
+                  taken on the library build that is running (source hash recorded in the pmc file); "alone" with --full
+  "cpu_baseline"  with --full: the oracle (CPU restatement of the reference, torch fp32) timed on this box's host cores on a
                   bounded sample of the same workload (rank 0, N = 1 only)
-  "host"          this rank's CPU slice, PnP threads, the pool's measured ceiling (frames/s of RANSAC alone on recorded matches)
-                  and "host_bound": true when that ceiling is below the matcher-only rate.
+  "host"          this rank's CPU slice, PnP threads; with --full the pool's measured ceiling (frames/s of RANSAC alone on
+                  recorded matches) and "host_bound": true when that ceiling is below the matcher-only rate.
 """
 from __future__ import annotations
 
@@ -149,7 +154,24 @@ def rank_report(rows, world: int, frames_expected: int, poses_expected: int = -1
             "slowest_over_fastest": (min(vals) / max(vals)) if vals else None, "per_rank": per}
 
 
-def main():
+def extra_measurements(args, rank: int, world: int) -> dict:
+    """Which measurements beside the headline this rank takes: none without --full; with it, all of them, less what
+    --main-region-only / --no-side-legs / --no-cpu-baseline leave out and what the run's shape does not allow"""
+    full = bool(args.full)
+    return {
+        # further timed regions of the same K steps: lazy conf_matrix, the other PnP policy, matcher only, object cache, dependent
+        # sequence (one rank, one frame per step), no hot steps
+        "side_regions": full and not args.main_region_only,
+        "stage_regions": full and args.roofline_kernel == "conf",          # one region per N x M kernel of the conf stage, each bracketed
+        "roofline_alone": full and args.roofline_kernel == "attn_apply",   # eight frames one at a time, every launch bracketed
+        "pnp_ceiling": full,                                               # the PnP pool alone on recorded matches
+        "side_legs": (full and not args.main_region_only and not args.no_side_legs and rank == 0 and world == 1 and args.workload == "c2"
+                      and args.batch == 1),                                # BASELINE configs 3 and 4, c2_hard, fine bf16: child processes
+        "cpu_baseline": full and not args.no_cpu_baseline and rank == 0 and world == 1,
+    }
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -159,9 +181,14 @@ def main():
     ap.add_argument("--frames", type=int, default=4, help="distinct synthetic frames per rank (cycled)")
     ap.add_argument("--precision", default=os.environ.get("OPHIP_PRECISION", "bf16x3"), choices=["f32", "bf16x3", "bf16"],
                     help="matrix arithmetic of the encoder kernels (see DESIGN.md section 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beside the headline (bench.extra_measurements): side regions, per-kernel regions of the conf "
+                         "stage, roofline.alone, the PnP pool's ceiling, the BASELINE side legs and the CPU baseline.  Off: the run sets up, warms up, "
+                         "times the K steps, writes --dump-outputs and prints the line")
     ap.add_argument("--main-region-only", action="store_true",
-                    help="skip the side measurements (other PnP policy, matcher only, object cache): the process then runs the contract's region "
-                         "alone -- what `tools/box.sh stats` traces, so that the rocprofv3 averages describe the same conditions as the line")
+                    help="with --full: skip the side regions (other PnP policy, matcher only, object cache, ...) and the side legs: the process then "
+                         "runs the contract's region alone -- what `tools/box.sh stats` traces, so that the rocprofv3 averages describe the same "
+                         "conditions as the line")
     ap.add_argument("--inputs-behind", action="store_true",
                     help="queue the input kernels (PE, transposes, keypoint encoding) behind the previous frame on the compute stream instead of "
                          "on a side stream (the feature maps and the object block are resident and complete here, so the side stream is legitimate)")
@@ -185,20 +212,25 @@ def main():
     ap.add_argument("--pnp-threads", type=int, default=0, help="host threads of the PnP pool (0: this rank's CPU slice minus 2 feeder cores, hostsize.pnp_threads)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank uses cuda:0 (one-GPU box, with --dist-backend gloo)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--roofline-kernel", default="attn_apply", choices=["attn_apply", "conf"],
                     help="which kernel carries the start / stop events inside the timed region and fills `roofline`: attn_apply (MFMA-bound, the "
                          "headline's) or conf (HBM-bound: the dual-softmax product pass over the N x M matrix; what the c4 side leg reports)")
     ap.add_argument("--no-side-legs", action="store_true",
-                    help="skip the BASELINE config 3 (32 frames per step) and config 4 (15k x 19 200) side legs that a default c2 run appends to its line")
-    ap.add_argument("--cpu-seconds", type=float, default=40.0, help="budget of the CPU baseline leg (all-core, full-forward and single-thread samples)")
+                    help="with --full: skip the BASELINE config 3 (32 frames per step) and config 4 (15k x 19 200) side legs that a c2 run appends to its line")
+    ap.add_argument("--cpu-seconds", type=float, default=40.0, help="budget of the CPU baseline leg (all-core, full-forward and single-thread samples; --full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the contract's region computed in its last step (rank 0's frames: match lists, "
                          "conf_matrix or a fixed sample of its rows, poses) as DIR/<name>.npy in float32 / float64, at most 64 MB in all "
                          "(bench.output_arrays); the inputs depend on the arguments alone, so two builds compare output for output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     # ---- N > 1 without a launcher: this process becomes the driver and starts one child per GPU (it never touches the GPU
     #      itself and never exec's; the reference fans out from its driver too, inference_OnePosePlus.py:81-98) --------------
@@ -214,6 +246,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    extra = extra_measurements(args, rank, world)
     # this rank's slice of the host: pinned before any thread pool exists (PnP workers and torch's intra-op threads inherit it)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     n_mask = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 0
@@ -532,10 +565,10 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0, lat
 
-    # side measurements first (the other PnP policy, the matcher alone), the contract's region last with the kernel timing on
+    # side measurements first (--full: the other PnP policy, the matcher alone, ...), the contract's region last with the kernel timing on
     other = {"reference": "adaptive", "adaptive": "reference"}[args.pnp_policy]
     dt_other = dt_matcher = dt_cached = dt_lazy = lazy_reruns = dt_nohot = dt_dep = lat_dep = dt_dep_cached = None
-    if not args.main_region_only and args.precision != "f32":
+    if extra["side_regions"] and args.precision != "f32":
         # the mode in which conf_matrix is not requested, reported beside the headline (which stays eager: the reference
         # writes the matrix every frame).  config["hip_conf_matrix"] = "lazy": nothing N x M is stored, match lists bit-identical
         cfg_lazy = dict(cfg)
@@ -552,7 +585,7 @@ def main():
         lazy_reruns = model_lazy.lazy_reruns
         model = model_eager
         del model_lazy
-    if not args.main_region_only:
+    if extra["side_regions"]:
         dt_other = timed_region(pools[other]) if pools else None
         dt_matcher = timed_region(None)
         model.cache_object = True                       # per-object cache (config["hip_cache_object"]): keypoint encoding, first layer's 3D rows, layer 1's
@@ -624,7 +657,7 @@ def main():
         # sim_stats (statistics only) + sim_conf (tiles again, every confidence written once) and no conf launch.
         if launches:
             stage_kernels["conf"] = kern_ms / launches
-        for nm in ("sim_stats", "sim_conf", "stat_combine"):
+        for nm in ("sim_stats", "sim_conf", "stat_combine") if extra["stage_regions"] else ():
             hip.timing_select(nm, every=1)
             timed_region(pools.get(args.pnp_policy))
             n_, ms_ = hip.timing_read()
@@ -637,7 +670,7 @@ def main():
     # touch): `roofline.achieved` stays what the contract asks for -- the launch time inside the timed region -- and `roofline.alone` says
     # what the kernel does when nothing shares the chip.
     alone_launches, alone_ms = 0, 0.0
-    if args.roofline_kernel == "attn_apply":
+    if extra["roofline_alone"]:
         torch.cuda.synchronize()
         hip.timing_select(args.roofline_kernel, every=1)
         for i in range(8):
@@ -654,7 +687,7 @@ def main():
     # when that ceiling is below the matcher's rate, `value` is a host number and the line says so ("host_bound")
     pnp_ceiling = None
     own_rate = 0.0
-    if pools and last_host[0] is not None and last_host[0]["K"] > 0:
+    if extra["pnp_ceiling"] and pools and last_host[0] is not None and last_host[0]["K"] > 0:
         pl, hst = pools[args.pnp_policy], last_host[0]
         sel = slice(None) if B == 1 else (hst["b_ids"] == 0)
         p2, p3 = hst["mkpts_2d"][sel], hst["mkpts_3d_db"][sel]
@@ -741,7 +774,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
-        "setup_steps_untimed": setup_steps + (1 if args.main_region_only else (5 if args.precision != "f32" else 4)) * (args.warmup + HOT_STEPS),      # settle blocks before the W warm-up steps + the warm-ups (and hot steps) of the side regions
+        "setup_steps_untimed": setup_steps + (1 if not extra["side_regions"] else (5 if args.precision != "f32" else 4)) * (args.warmup + HOT_STEPS),      # settle blocks before the W warm-up steps + the warm-ups (and hot steps) of the side regions
         "hot_steps_untimed_before_each_timed_region": HOT_STEPS,      # matcher-only frames that bring the GPU out of its post-idle clock transient (see timed_region)
         "ms_per_step": dt / args.steps * 1e3,
         "value_matcher_only": (frames_total / dt_matcher) if dt_matcher else None,
@@ -857,12 +890,12 @@ def main():
 
     # ---- side legs: BASELINE configs 3 and 4 on this GPU, each in a child process of its own (same script, its own sizes), untimed by the
     #      headline: `value` above is config 2's and is final before they start ----------------------------------------------------------
-    if rank == 0 and world == 1 and not args.main_region_only and not args.no_side_legs and args.workload == "c2" and B == 1:
+    if extra["side_legs"]:
         import subprocess
 
-        def side_leg(extra, timeout=240, env=None):
-            cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--main-region-only", "--no-side-legs",
-                   "--precision", args.precision] + extra
+        def side_leg(leg_args, timeout=240, env=None):
+            cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--main-region-only", "--no-side-legs",
+                   "--precision", args.precision] + leg_args
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=(dict(os.environ) | env) if env else None)
                 line = [ln for ln in p.stdout.splitlines() if ln.lstrip().startswith("{")]
@@ -900,7 +933,7 @@ def main():
                                                                                                      "conf_kernel": c4.get("roofline")},
         }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if extra["cpu_baseline"]:
         from oracle import onepose_oracle as orc          # cpu_baseline leg only
         import statistics
 
