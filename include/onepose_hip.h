@@ -119,6 +119,18 @@ int ophip_encoder_layer_x3w8(const float* x3d, const float* x2d, float* y3d, flo
  * that neither runs nor is attended to may be NULL.  Replaces transformer.py:65-94 on one stream. */
 int ophip_encoder_layer_x3w8_streams(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
                                      const void* wpack, int is_cross, int streams, void* workspace, void* stream);
+/* ..._masks / ..._streams_masks: ophip_encoder_layer_x3w8 / ..._streams with a padding mask on EACH stream (LoFTR's mask0 / mask1,
+ * flattened: loftr_module/transformer.py LocalFeatureTransformer.forward with masks): mask0 [B][L3d] for the first stream, mask1 [B][L2d]
+ * for the second, bytes 1 = real cell, 0 = padding; either may be NULL (that stream unmasked).  A stream's mask zeroes phi(K) and V of its
+ * padded rows where it is a source (kv_mask) and phi(Q) where it is a query (q_mask: the padded row's message is 0; the row still goes
+ * through merge, LayerNorm, MLP and residual); v_length stays the padded length.  Their own instantiation of the kernels: the plain and
+ * the query-masked layers keep their code. */
+int ophip_encoder_layer_x3w8_masks(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
+                                   const void* wpack, const void* wpack_next, int is_cross, int kv_from_prev, int slot,
+                                   void* workspace, const unsigned char* mask0, const unsigned char* mask1, void* stream);
+int ophip_encoder_layer_x3w8_streams_masks(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
+                                           const void* wpack, int is_cross, int streams, void* workspace,
+                                           const unsigned char* mask0, const unsigned char* mask1, void* stream);
 /* The K / V half of a layer that projects its own K, V (the FIRST layer of a frame; transformer.py:65-94 k_proj / v_proj +
  * linear_attention.py:49-57): K, V projections of both streams -> phi(K)^T V / Ksum slabs -> their fixed-order sum into the workspace.
  * It reads the layer's input rows only, so a frame pipeline issues it as soon as those exist -- beside whatever the previous frame
@@ -375,6 +387,17 @@ int ophip_coarse_match_2d(const float* feat0, const float* feat1, const float* p
                           float* conf, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask,
                           int* count, int nsplit, void* stream);
+/* ophip_coarse_match_2d_masked: ophip_coarse_match_2d with LoFTR's padding masks mask0 [B][L0], mask1 [B][L1] (data["mask*"].flatten(-2),
+ *   bytes 1 = real cell; both required; nsplit 1 or 3):
+ *   sim.masked_fill_(~(mask0[:, :, None] & mask1[:, None, :]), -1e9) -- SET, not added -- before the dual softmax (a pair with one padded
+ *   cell gets confidence 0, a pair of two padded cells about 1 / (L0 L1)); the border is mask_border_with_padding: the first border_rm rows
+ *   and columns of both grids, then per pair b everything from (valid extent - border_rm) on, extents h = max_x sum_y mask[b],
+ *   w = max_y sum_x mask[b] taken on the device, Python slice starts (a negative start counts from the end of the padded grid). */
+int ophip_coarse_match_2d_masked(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                                 int B, int L0, int L1, int w0c, int w1c, double temperature, float thr, int border_rm, float scale,
+                                 float* conf, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
+                                 float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask,
+                                 int* count, int nsplit, const unsigned char* mask0, const unsigned char* mask1, void* stream);
 /* ophip_coarse_match_2d_sinkhorn: the same stage with LoFTR's optimal-transport matching (match_type 'sinkhorn', inference) in place
  *   of the dual softmax; split-bf16 similarity, f32 everywhere else.  m = L0, n = L1, S = <f0, f1> / C (no temperature):
  *     Z = [[S, a], [a, a]] with the dustbin row and column a = bin_score; norm = -log(m + n),
@@ -393,6 +416,15 @@ int ophip_coarse_match_2d_sinkhorn(const float* feat0, const float* feat1, const
                                    float thr, int border_rm, float scale, float* conf, float* workspace,
                                    long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
                                    float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream);
+/* ..._masked: with LoFTR's padding masks as ophip_coarse_match_2d_masked (S filled with -1e9, border from the valid extents); the
+ *   transport itself is unchanged, so norm and the dustbin masses use the PADDED m = L0, n = L1 (not invariant under padding, as in the
+ *   reference). */
+int ophip_coarse_match_2d_sinkhorn_masked(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                                          int B, int L0, int L1, int w0c, int w1c, float bin_score, int iters, int prefilter,
+                                          float thr, int border_rm, float scale, float* conf, float* workspace,
+                                          long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
+                                          float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count,
+                                          const unsigned char* mask0, const unsigned char* mask1, void* stream);
 int ophip_fine2_gather(const float* feat_cl, int hf, int wf, const long long* cell_ids, int K, int wc, int stride, int W, float* out, void* stream);
 /* the same over a batch of images [B][hf * wf][128]: match k reads image b_ids[k] (feat_bstride floats apart; 0: one image for every match) */
 int ophip_fine2_gather_b(const float* feat_cl, long long feat_bstride, const long long* b_ids, int hf, int wf, const long long* cell_ids,

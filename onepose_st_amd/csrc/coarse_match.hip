@@ -284,6 +284,10 @@ struct SimFragArgs {
     unsigned* colmax_bits;       // [B][M]
     float thr, logthr_lo;        // strict threshold; logf(thr) - 1e-3: conservative prefilter on the exponent (saves the exponential)
     const unsigned char* colmask;   // see SimArgs
+    // LoFTR's padding masks (loftr/utils/coarse_matching.py: sim_matrix.masked_fill_(~(mask0[..., None] * mask1[:, None]), -1e9)):
+    // fill0 [B][N] rows, fill1 [B][M] columns, 1 = real cell; an entry whose row or column is padding is SET to -1e9.  NULL: none (both or neither)
+    const unsigned char* fill0;
+    const unsigned char* fill1;
 };
 
 // XCD-aware tile of this block: label x = blockIdx.x % 8 owns row tiles [r0, r1) (sizes differ by at most one) and walks
@@ -396,6 +400,29 @@ __global__ __launch_bounds__(256) OPHIP_WAVES_PER_SIMD(1, 2) void sim_frag_kerne
             pad[y] = (col < p.M && !p.colmask[(size_t)b * p.M + col]) ? -1e9f : 0.f;
         }
     }
+    if (p.fill0) {                                    // masked_fill: the entry becomes exactly -1e9 (cells past the matrix edge stay as they are)
+        const unsigned char* m0 = p.fill0 + (size_t)b * p.N;
+        const unsigned char* m1 = p.fill1 + (size_t)b * p.M;
+        bool cok[2];
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+            const int col = j0 + 64 * wc + 32 * y + r;
+            cok[y] = col >= p.M || m1[col] != 0;
+        }
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int row = i0 + 64 * wr + 32 * x + acc_row(reg, h);
+                const bool rok = row >= p.N || m0[row] != 0;
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    const float sv = (rok && cok[y]) ? acc[x][y][reg] * inv_temp : -1e9f;
+                    St[(64 * wr + 32 * x + acc_row(reg, h)) * FLD + 64 * wc + 32 * y + r] = sv;
+                    vmax = fmaxf(vmax, sv);
+                }
+            }
+    } else {
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -406,6 +433,7 @@ __global__ __launch_bounds__(256) OPHIP_WAVES_PER_SIMD(1, 2) void sim_frag_kerne
                 St[(64 * wr + 32 * x + acc_row(reg, h)) * FLD + 64 * wc + 32 * y + r] = sv;
                 vmax = fmaxf(vmax, sv);
             }
+    }
     if (MODE >= 2) {
         unsigned long long* bestk = reinterpret_cast<unsigned long long*>(smem + SIM_FRAG_STAGE);     // [128] (value bits << 32) | ~j : max = best value, lowest j
         int* tiecnt = reinterpret_cast<int*>(bestk + 128);                                             // [128]
@@ -1065,6 +1093,8 @@ struct SelectArgs {
     long long* m_bids;          // optional second copy of b_ids (the reference's 'm_bids')
     unsigned char* gt_mask;     // optional mconf == 0 flags (the reference's 'gt_mask')
     int* count;
+    const int* plim;            // border_mode 2 (LoFTR's mask_border_with_padding): [B][4] exclusive row / column limits of grid 0, then of
+                                // grid 1, per pair (pad_limits_kernel); the first `border` rows and columns are cleared as in mode 1
 };
 
 // Selection in two small kernels (round 4; the single 8 x 1024-thread kernel of round 3 needed whole CUs, which beside the previous
@@ -1103,15 +1133,20 @@ __global__ __launch_bounds__(SEL_T) void select_decide_kernel(SelectArgs p, int*
                 else if (v2 == v) { j = min(j, j2); c += c2; }
             }
         }
+        const int* lim = p.border_mode == 2 ? p.plim + 4 * b : nullptr;
         auto inside = [&](int jj) {
             const int jy = jj / p.wc, jx = jj % p.wc;
             if (p.border_mode == 0) return (jy >= p.border) && (jx >= p.border);
+            if (p.border_mode == 2) return jy >= p.border && jx >= p.border && jy < lim[2] && jx < lim[3];
             return jy >= p.border && jx >= p.border && jy < p.M / p.wc - p.border && jx < p.wc - p.border;
         };
         bool i_ok = true;
         if (p.border_mode == 1) {
             const int iy = i / p.wi, ix = i % p.wi;
             i_ok = iy >= p.border && ix >= p.border && iy < p.N / p.wi - p.border && ix < p.wi - p.border;
+        } else if (p.border_mode == 2) {
+            const int iy = i / p.wi, ix = i % p.wi;
+            i_ok = iy >= p.border && ix >= p.border && iy < lim[0] && ix < lim[1];
         }
         if (v > p.thr && i_ok) {
             const float* cmx = p.colmax + (size_t)b * p.M;
@@ -1176,12 +1211,50 @@ __global__ __launch_bounds__(SEL_T) void select_place_kernel(SelectArgs p, const
     if (blockIdx.x == gridDim.x - 1 && tid == 0) *p.count = base + (wpre[0] + wpre[1]) + (wpre[2] + wpre[3]);
 }
 
+// LoFTR's mask_border_with_padding (loftr/utils/coarse_matching.py), the part after the first `bd` rows / columns: per pair b and grid g
+// (0: mask0 [B][h0][w0], 1: mask1 [B][h1][w1]) the valid extents h = max_x sum_y m, w = max_y sum_x m, and the border clears rows from
+// h - bd and columns from w - bd on -- Python slice starts: a negative one counts from the end of the padded grid (and stops at 0).
+// -> lim[b][2 g] / lim[b][2 g + 1]: the first cleared row / column (bd <= 0: nothing is cleared, the grid's height / width).
+// Workgroup (b, g); integer sums and maxima only.
+__global__ __launch_bounds__(256) void pad_limits_kernel(const unsigned char* __restrict__ m0, const unsigned char* __restrict__ m1, int h0, int w0,
+                                                         int h1, int w1, int bd, int* __restrict__ lim) {
+    __shared__ int red[2];
+    const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const int H = g ? h1 : h0, W = g ? w1 : w0;
+    const unsigned char* m = g ? m1 + (size_t)b * h1 * w1 : m0 + (size_t)b * h0 * w0;
+    if (tid < 2) red[tid] = 0;
+    __syncthreads();
+    int hmax = 0, wmax = 0;
+    for (int x = tid; x < W; x += 256) {
+        int c = 0;
+        for (int y = 0; y < H; ++y) c += m[(size_t)y * W + x] != 0;
+        hmax = max(hmax, c);
+    }
+    for (int y = tid; y < H; y += 256) {
+        int c = 0;
+        for (int x = 0; x < W; ++x) c += m[(size_t)y * W + x] != 0;
+        wmax = max(wmax, c);
+    }
+    atomicMax(red, hmax);
+    atomicMax(red + 1, wmax);
+    __syncthreads();
+    if (tid == 0) {
+        auto start = [&](int e, int n) {
+            if (bd <= 0) return n;
+            const int s0 = e - bd;
+            return s0 >= 0 ? min(s0, n) : max(0, n + s0);
+        };
+        lim[4 * b + 2 * g] = start(red[0], H);
+        lim[4 * b + 2 * g + 1] = start(red[1], W);
+    }
+}
+
 inline int conf_nspan(int M) { return (M + 1024 * CONF_U - 1) / (1024 * CONF_U); }
 inline int conf_spanw(int M) { const int ns = conf_nspan(M); return (((M + ns - 1) / ns) + 3) / 4 * 4; }
 
 // workspace map (floats), shared by the sizing helper, coarse_impl and the fragment-plane accessor
 struct CoarseWs {
-    size_t rowpart, colpart, rowstat, colstat, rowbest, colmax, rowlog, collog, seldec, selcnt, planes, total;
+    size_t rowpart, colpart, rowstat, colstat, rowbest, colmax, rowlog, collog, seldec, selcnt, planes, plim, total;
     int nspan_cap;                                   // row-best records per row: conf_kernel's spans or (lazy form) the column tiles
 };
 CoarseWs coarse_ws(int B, int N, int M) {
@@ -1200,8 +1273,19 @@ CoarseWs coarse_ws(int B, int N, int M) {
     w.seldec = f; f += (size_t)B * N;                                   // select_decide: chosen j (int) or -1 per 3D point
     w.selcnt = f; f += ((size_t)B * N + SEL_T - 1) / SEL_T + 4;        // ... and the matches per workgroup
     w.planes = f; f += (size_t)B * (ntr + ntc) * TM * C + 64;      // fragment planes of both inputs (hi + lo bf16 = 4 bytes per element), rows padded to 128
+    w.plim = f; f += (size_t)B * 4;                                    // border_mode 2: the per-pair limits (pad_limits_kernel)
     w.total = f + 64;
     return w;
+}
+
+// border_mode 2: the per-pair limits of select_decide from the two padding masks (grids h0 x wi and h1 x wc), into the workspace
+int pad_limits_launch(const unsigned char* mask0, const unsigned char* mask1, int B, int N, int M, int wi, int wc, int border, float* workspace,
+                      const CoarseWs& ws, const int** plim, hipStream_t stream) {
+    int* lim = reinterpret_cast<int*>(workspace + ws.plim);
+    OPHIP_LAUNCH("pad_limits", stream, pad_limits_kernel, dim3(B, 2), dim3(256), 0, stream, mask0, mask1, N / wi, wi, M / wc, wc, border, lim);
+    OPHIP_CHECK_LAUNCH();
+    *plim = lim;
+    return 0;
 }
 
 // the selection launch over the row-best records and column maxima in the workspace (coarse_impl; ophip_coarse_select_2d)
@@ -1254,7 +1338,8 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
                 int B, int N, int M, int wc, double temperature, float thr, int border_rm, float scale,
                 float* conf, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
                 float* mconf, float* mkpts3d, float* mkpts_c, long long* m_bids, unsigned char* gt_mask,
-                int* count, int nsplit, void* stream_, const unsigned char* qmask = nullptr, const float* qscale = nullptr) {
+                int* count, int nsplit, void* stream_, const unsigned char* qmask = nullptr, const float* qscale = nullptr,
+                const unsigned char* fill0 = nullptr, const unsigned char* fill1 = nullptr) {
     if (!feat3d || !feat2d || !keypoints3d || !workspace || !b_ids || !i_ids || !j_ids || !mconf || !mkpts3d || !mkpts_c || !count)
         return ophip_bad_arg(__func__, "null pointer");
     const bool lazy = conf == nullptr;               // conf_matrix not requested: nothing N x M is stored (bf16 modes)
@@ -1265,6 +1350,8 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
     if (nsplit != 0 && nsplit != 1 && nsplit != 3) return ophip_bad_arg(__func__, "nsplit must be 0 (exact f32), 1 (bf16) or 3 (split bf16)");
     if (planes_ready && nsplit == 0) return ophip_bad_arg(__func__, "fragment planes are an input of the bf16 modes only");
     if (lazy && nsplit == 0) return ophip_bad_arg(__func__, "conf == NULL (lazy conf_matrix) needs a bf16 mode: the exact-f32 mode always materialises it");
+    if ((fill0 == nullptr) != (fill1 == nullptr)) return ophip_bad_arg(__func__, "padding masks come together");
+    if (fill0 && (nsplit == 0 || border_mode != 1 || qmask)) return ophip_bad_arg(__func__, "padding masks: LoFTR's 2D-2D form in a bf16 mode");
     hipStream_t stream = (hipStream_t)stream_;
     // rows per conf workgroup: OPHIP_CONF_ROWS_RT (a multiple of 2 * CONF_RB up to CONF_ROWS_MAX), default CONF_ROWS
     static const int conf_rows = [] {
@@ -1303,6 +1390,7 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
         }
         sf = SimFragArgs{fa_, fb_, conf, rowpart, colpart, N, M, ntr, ntc, (float)(temperature + temp_eps), ophip_stamp_buffer(),
                          rowstat, colstat, rowlog, collog, rowbest, reinterpret_cast<unsigned*>(colmax), thr, logf(thr) - 1e-3f, qmask};
+        sf.fill0 = fill0; sf.fill1 = fill1;
 #define OPHIP_SIM_CASE(NS_, MODE_, NAME_)                                                                                          \
         {                                                                                                                          \
             if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(sim_frag_kernel<NS_, MODE_>), SIM_FRAG_LDS, "hipFuncSetAttribute(sim_frag)")) return rc; \
@@ -1314,7 +1402,7 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
         // workgroups take 154 of a CU's 160 KB of LDS and 480 of 512 registers per lane: the next frame's input kernels (the fine map's
         // transpose needs 17 KB of LDS), which used to run BESIDE the similarity tiles, now wait for them.
         const char* tile_env = getenv("OPHIP_SIM_TILE");          // (read per call: tests compare the two tile kernels in one process)
-        const bool tile3 = tile_env && tile_env[0] == '3';
+        const bool tile3 = tile_env && tile_env[0] == '3' && !fill0;          // (the three-per-CU kernel has no padding-mask fill)
 #define OPHIP_SIM3_CASE(NS_, MODE_)                                                                                                \
         {                                                                                                                          \
             if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(sim_frag3_kernel<NS_, MODE_>), SIM_F3_LDS, "hipFuncSetAttribute(sim_frag3)")) return rc; \
@@ -1366,6 +1454,10 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
     if (parts & 2) {
         SelectArgs se{conf, rowbest, colmax, keypoints3d, kpts_bstride, B, N, M, sel_nspan, wc, border_rm, border_mode, wi, thr, scale, qscale,
                       b_ids, i_ids, j_ids, mconf, mkpts3d, mkpts_c, m_bids, gt_mask, count};      // (conf == NULL: an exact row tie sets count[1])
+        if (fill0) {
+            se.border_mode = 2;
+            if (int rc = pad_limits_launch(fill0, fill1, B, N, M, wi, wc, border_rm, workspace, ws, &se.plim, stream)) return rc;
+        }
         if (int rc = select_launch(se, workspace, ws, stream)) return rc;
     }
     return 0;
@@ -1374,7 +1466,8 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
 
 // Internal (x3w8_internal.h): the pieces of the eager bf16 form that csrc/coarse_sinkhorn.hip reuses.
 int ophip_coarse_sim_store(const float* feat0, const float* feat1, int B, int N, int M, float* conf, float* workspace,
-                           const float** rowstat, float** rowbest, unsigned** colmax_bits, void* stream_) {
+                           const float** rowstat, float** rowbest, unsigned** colmax_bits, void* stream_,
+                           const unsigned char* mask0, const unsigned char* mask1) {
     hipStream_t stream = (hipStream_t)stream_;
     const int ntr = (N + TM - 1) / TM, ntc = (M + TN - 1) / TN;
     const CoarseWs ws = coarse_ws(B, N, M);
@@ -1386,6 +1479,7 @@ int ophip_coarse_sim_store(const float* feat0, const float* feat1, int B, int N,
     SimFragArgs sf{};
     sf.a = fa; sf.b = fb; sf.conf = conf; sf.rowpart = workspace + ws.rowpart; sf.colpart = workspace + ws.colpart;
     sf.N = N; sf.M = M; sf.ntr = ntr; sf.ntc = ntc; sf.temp = 1.0f; sf.stamps = ophip_stamp_buffer();
+    sf.fill0 = mask0; sf.fill1 = mask1;
     if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(sim_frag_kernel<3, 0>), SIM_FRAG_LDS, "hipFuncSetAttribute(sim_frag)")) return rc;
     OPHIP_LAUNCH("sim_stats", stream, (sim_frag_kernel<3, 0>), dim3(8 * ((ntr + 7) / 8) * ntc, B), dim3(256), SIM_FRAG_LDS, stream, sf);
     OPHIP_CHECK_LAUNCH();
@@ -1401,10 +1495,15 @@ int ophip_coarse_sim_store(const float* feat0, const float* feat1, int B, int N,
 
 int ophip_coarse_select_2d(const float* conf, int nspan, const float* points0, long long points_bstride, int B, int N, int M, int wi, int wc,
                            float thr, int border_rm, float scale, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
-                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream) {
+                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream,
+                           const unsigned char* mask0, const unsigned char* mask1) {
     const CoarseWs ws = coarse_ws(B, N, M);
     SelectArgs se{conf, workspace + ws.rowbest, workspace + ws.colmax, points0, points_bstride, B, N, M, nspan, wc, border_rm, 1, wi, thr, scale,
                   nullptr, b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count};
+    if (mask0) {
+        se.border_mode = 2;
+        if (int rc = pad_limits_launch(mask0, mask1, B, N, M, wi, wc, border_rm, workspace, ws, &se.plim, (hipStream_t)stream)) return rc;
+    }
     return select_launch(se, workspace, ws, (hipStream_t)stream);
 }
 
@@ -1474,4 +1573,22 @@ extern "C" int ophip_coarse_match_2d(const float* feat0, const float* feat1, con
                                      int* count, int nsplit, void* stream) {
     return coarse_impl(3, 1, w0c, 0.0, feat0, feat1, points0, points_bstride, B, L0, L1, w1c, temperature, thr, border_rm, scale, conf, workspace,
                        b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count, nsplit, stream);
+}
+
+// ophip_coarse_match_2d with LoFTR's padding masks (mask0 / mask1 given: loftr/utils/coarse_matching.py, inference).  mask0 [B][L0],
+// mask1 [B][L1] (data["mask*"].flatten(-2); 1 = real cell, 0 = padding; both required):
+//   * sim = <f0, f1> / C / temperature, then sim.masked_fill_(~(mask0[:, :, None] & mask1[:, None, :]), -1e9) -- the entry is SET to -1e9
+//     in the similarity tiles, in the statistics pass and in every pass that writes or re-derives a confidence; the dual softmax follows
+//     unchanged (a pair with one padded cell gets 0, a pair of two padded cells about 1 / (L0 L1));
+//   * mask_border_with_padding replaces mask_border: the first border_rm rows / columns of both grids, then per pair everything from the
+//     valid extent minus border_rm on (pad_limits_kernel: the extents come from the masks on the device, no host synchronisation).
+// A bf16 mode (nsplit 1 or 3); the tile kernel is always sim_frag_kernel.  Other arguments as ophip_coarse_match_2d.
+extern "C" int ophip_coarse_match_2d_masked(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                                            int B, int L0, int L1, int w0c, int w1c, double temperature, float thr, int border_rm, float scale,
+                                            float* conf, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
+                                            float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask,
+                                            int* count, int nsplit, const unsigned char* mask0, const unsigned char* mask1, void* stream) {
+    if (!mask0 || !mask1) return ophip_bad_arg(__func__, "null mask (use ophip_coarse_match_2d)");
+    return coarse_impl(3, 1, w0c, 0.0, feat0, feat1, points0, points_bstride, B, L0, L1, w1c, temperature, thr, border_rm, scale, conf, workspace,
+                       b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count, nsplit, stream, nullptr, nullptr, mask0, mask1);
 }

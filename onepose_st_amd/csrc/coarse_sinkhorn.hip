@@ -378,11 +378,13 @@ extern "C" size_t ophip_coarse_sinkhorn_workspace_floats(int B, int L0, int L1) 
     return ophip_coarse_workspace_floats(B, L0, L1) + skh_ws(B, L0, L1).total;
 }
 
-extern "C" int ophip_coarse_match_2d_sinkhorn(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
-                                              int B, int L0, int L1, int w0c, int w1c, float bin_score, int iters, int prefilter,
-                                              float thr, int border_rm, float scale, float* conf, float* workspace,
-                                              long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
-                                              float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream_) {
+namespace {
+int sinkhorn_impl(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                  int B, int L0, int L1, int w0c, int w1c, float bin_score, int iters, int prefilter,
+                  float thr, int border_rm, float scale, float* conf, float* workspace,
+                  long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
+                  float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream_,
+                  const unsigned char* mask0, const unsigned char* mask1) {
     if (!feat0 || !feat1 || !points0 || !conf || !workspace || !b_ids || !i_ids || !j_ids || !mconf || !mkpts0 || !mkpts1_c || !count)
         return ophip_bad_arg(__func__, "null pointer (conf is required)");
     if (B < 1 || L0 < 1 || L1 < 1 || w0c < 1 || w1c < 1 || L0 % w0c != 0 || L1 % w1c != 0)
@@ -399,7 +401,7 @@ extern "C" int ophip_coarse_match_2d_sinkhorn(const float* feat0, const float* f
     const float* rowstat;
     float* rowbest;
     unsigned* colmax_bits;
-    if (int rc = ophip_coarse_sim_store(feat0, feat1, B, N, M, conf, workspace, &rowstat, &rowbest, &colmax_bits, stream)) return rc;
+    if (int rc = ophip_coarse_sim_store(feat0, feat1, B, N, M, conf, workspace, &rowstat, &rowbest, &colmax_bits, stream, mask0, mask1)) return rc;
 
     // the reference's f32 marginals: norm = -log(m + n), log_mu = [norm x m, log n + norm], log_nu = [norm x n, log m + norm]
     const float fm = (float)N, fn = (float)M;
@@ -435,5 +437,31 @@ extern "C" int ophip_coarse_match_2d_sinkhorn(const float* feat0, const float* f
     else OPHIP_LAUNCH("skh_final", stream, skh_final_kernel<false>, fin_grid, dim3(256), 0, stream, a, fa);
     OPHIP_CHECK_LAUNCH();
     return ophip_coarse_select_2d(conf, 1, points0, points_bstride, B, N, M, w0c, w1c, thr, border_rm, scale, workspace,
-                                  b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count, stream);
+                                  b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count, stream, mask0, mask1);
+}
+}  // namespace
+
+extern "C" int ophip_coarse_match_2d_sinkhorn(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                                              int B, int L0, int L1, int w0c, int w1c, float bin_score, int iters, int prefilter,
+                                              float thr, int border_rm, float scale, float* conf, float* workspace,
+                                              long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
+                                              float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream) {
+    return sinkhorn_impl(feat0, feat1, points0, points_bstride, B, L0, L1, w0c, w1c, bin_score, iters, prefilter, thr, border_rm, scale,
+                         conf, workspace, b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count, stream, nullptr, nullptr);
+}
+
+// ophip_coarse_match_2d_sinkhorn with LoFTR's padding masks mask0 [B][L0] / mask1 [B][L1] (1 = real cell; both required): S =
+// <f0, f1> / C with S.masked_fill_(~(mask0[:, :, None] & mask1[:, None, :]), -1e9) in the similarity tiles, then the unchanged
+// log_optimal_transport -- its norm = -log(m + n) and dustbin masses use the PADDED m = L0, n = L1, so the output is not invariant under
+// padding (the reference's behaviour) -- and the prefilter; the selection's border follows each pair's valid extent (mask_border_with_padding,
+// as ophip_coarse_match_2d_masked).
+extern "C" int ophip_coarse_match_2d_sinkhorn_masked(const float* feat0, const float* feat1, const float* points0, long long points_bstride,
+                                                     int B, int L0, int L1, int w0c, int w1c, float bin_score, int iters, int prefilter,
+                                                     float thr, int border_rm, float scale, float* conf, float* workspace,
+                                                     long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0,
+                                                     float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count,
+                                                     const unsigned char* mask0, const unsigned char* mask1, void* stream) {
+    if (!mask0 || !mask1) return ophip_bad_arg(__func__, "null mask (use ophip_coarse_match_2d_sinkhorn)");
+    return sinkhorn_impl(feat0, feat1, points0, points_bstride, B, L0, L1, w0c, w1c, bin_score, iters, prefilter, thr, border_rm, scale,
+                         conf, workspace, b_ids, i_ids, j_ids, mconf, mkpts0, mkpts1_c, m_bids, gt_mask, count, stream, mask0, mask1);
 }

@@ -46,6 +46,7 @@ struct EncW8Args {
     char* frag[2];             // optional: the output rows also as the similarity kernel's operand fragments (csrc/coarse_match.hip:
     int frag_rows[2];          // frag_planes layout, rows padded to frag_rows = a multiple of 128); NULL: not written
     const unsigned char* mask2d;   // MASKED kernels: [B][L[1]] 1 = real cell, 0 = padding of the 2D stream (linear_attention.py:49-53)
+    const unsigned char* mask3d;   // MASKED + BOTH kernels: [B][L[0]] the first stream's mask (NULL: none); mask2d is then the second's (NULL: none)
 };
 
 __device__ __forceinline__ int stash_off(int row, int chunk) { return row * (C * 4) + ((chunk ^ (row & 15)) << 4); }
@@ -132,7 +133,9 @@ __device__ __forceinline__ void kv_tail(Ring& ring, const WStream& wsk, const ch
     }
 }
 
-template <bool ONLY_KV, bool MASKED = false>
+// MASKED: the second stream carries a padding mask (mask2d, OnePose++'s query mask).  MASKED + BOTH: each stream its own mask or none
+// (mask3d, mask2d: LoFTR's mask0 / mask1) -- its own instantiation, so that the two above keep their code and their rounding.
+template <bool ONLY_KV, bool MASKED = false, bool BOTH = false>
 __global__ __launch_bounds__(512) OPHIP_WAVES_PER_SIMD(2, 2) void enc_x3w8_kernel(EncW8Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* XH = smem;
@@ -149,7 +152,8 @@ __global__ __launch_bounds__(512) OPHIP_WAVES_PER_SIMD(2, 2) void enc_x3w8_kerne
     const int lt = s ? tile - a.tiles[0] : tile;
     const int L = a.L[s], tok0 = lt * TOK;
     const float* xg = a.x[s] + (size_t)b * a.xbs[s];
-    const unsigned char* mk = (MASKED && s == 1) ? a.mask2d + (size_t)b * L : nullptr;
+    const unsigned char* smk = s ? a.mask2d : a.mask3d;          // (BOTH only)
+    const unsigned char* mk = BOTH ? (smk ? smk + (size_t)b * L : nullptr) : (MASKED && s == 1) ? a.mask2d + (size_t)b * L : nullptr;
     const int wg = blockIdx.y * gridDim.x + blockIdx.x;
     float* slab = a.partial + ((size_t)b * (a.tiles[0] + a.tiles[1]) + tile) * KV_PART_FLOATS;
     const int fwu = __builtin_amdgcn_readfirstlane(fw);
@@ -477,6 +481,8 @@ struct X3Opts {
     long long kv3d_bs = 0;
     void* kv_out = nullptr;
     long long kv_out_bs = 0;
+    bool both_masks = false;       // the MASKED + BOTH instantiation: mask3d for the first stream, layer_x3w8's mask2d for the second (either NULL)
+    const unsigned char* mask3d = nullptr;
 };
 
 // kv_mode: 0 = this call projects its own K, V (kv_reduce), sums the slabs (kv_sum) and applies; 1 = the slabs are there (the previous
@@ -516,7 +522,11 @@ int layer_x3w8(const float* x3d, const float* x2d, float* y3d, float* y2d, int B
     const float* ln = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wpack) + (size_t)NW * (MAIN_FRAGS + KV_FRAGS) * 1024);
     if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(enc_x3w8_kernel<false>), LDS_BYTES, "hipFuncSetAttribute(enc_x3w8)")) return rc;
     if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(enc_x3w8_kernel<true>), LDS_BYTES, "hipFuncSetAttribute(enc_x3w8 kv)")) return rc;
-    if (mask2d) {
+    const bool both = opt.both_masks;
+    if (both) {
+        if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(enc_x3w8_kernel<false, true, true>), LDS_BYTES, "hipFuncSetAttribute(enc_x3w8 masks)")) return rc;
+        if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(enc_x3w8_kernel<true, true, true>), LDS_BYTES, "hipFuncSetAttribute(enc_x3w8 kv masks)")) return rc;
+    } else if (mask2d) {
         if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(enc_x3w8_kernel<false, true>), LDS_BYTES, "hipFuncSetAttribute(enc_x3w8 masked)")) return rc;
         if (int rc = ophip_lds_attr(reinterpret_cast<const void*>(enc_x3w8_kernel<true, true>), LDS_BYTES, "hipFuncSetAttribute(enc_x3w8 kv masked)")) return rc;
     }
@@ -536,6 +546,7 @@ int layer_x3w8(const float* x3d, const float* x2d, float* y3d, float* y2d, int B
     aa.frag[0] = static_cast<char*>(frag3d); aa.frag[1] = static_cast<char*>(frag2d);
     aa.frag_rows[0] = (L3d + 127) / 128 * 128; aa.frag_rows[1] = (L2d + 127) / 128 * 128;
     aa.mask2d = mask2d;
+    aa.mask3d = both ? opt.mask3d : nullptr;
     if (kv_mode == 0 && !sum_only) {
         EncW8Args ka = aa;
         ka.kv[0] = ka.kv[1] = nullptr;
@@ -545,7 +556,8 @@ int layer_x3w8(const float* x3d, const float* x2d, float* y3d, float* y2d, int B
         ka.stamps = nullptr;
         ka.tiles[0] = (src & 1) ? t3 : 0; ka.tiles[1] = (src & 2) ? t2 : 0;
         const int kt = ka.tiles[0] + ka.tiles[1];
-        if (mask2d) { OPHIP_LAUNCH("kv_reduce", stream, (enc_x3w8_kernel<true, true>), dim3(kt, B), dim3(512), LDS_BYTES, stream, ka); }
+        if (both) { OPHIP_LAUNCH("kv_reduce", stream, (enc_x3w8_kernel<true, true, true>), dim3(kt, B), dim3(512), LDS_BYTES, stream, ka); }
+        else if (mask2d) { OPHIP_LAUNCH("kv_reduce", stream, (enc_x3w8_kernel<true, true>), dim3(kt, B), dim3(512), LDS_BYTES, stream, ka); }
         else { OPHIP_LAUNCH("kv_reduce", stream, enc_x3w8_kernel<true>, dim3(kt, B), dim3(512), LDS_BYTES, stream, ka); }
         OPHIP_CHECK_LAUNCH();
     }
@@ -574,7 +586,8 @@ int layer_x3w8(const float* x3d, const float* x2d, float* y3d, float* y2d, int B
     aa.wkv = nullptr;
     aa.partial = partial_next;
     if (wpack_next) aa.wkv = reinterpret_cast<const bf16x8*>(wpack_next) + (size_t)NW * MAIN_FRAGS * 64;
-    if (mask2d) { OPHIP_LAUNCH("attn_apply", stream, (enc_x3w8_kernel<false, true>), dim3(rt3 + rt2, B), dim3(512), LDS_BYTES, stream, aa); }
+    if (both) { OPHIP_LAUNCH("attn_apply", stream, (enc_x3w8_kernel<false, true, true>), dim3(rt3 + rt2, B), dim3(512), LDS_BYTES, stream, aa); }
+    else if (mask2d) { OPHIP_LAUNCH("attn_apply", stream, (enc_x3w8_kernel<false, true>), dim3(rt3 + rt2, B), dim3(512), LDS_BYTES, stream, aa); }
     else { OPHIP_LAUNCH("attn_apply", stream, enc_x3w8_kernel<false>, dim3(rt3 + rt2, B), dim3(512), LDS_BYTES, stream, aa); }
     OPHIP_CHECK_LAUNCH();
     return 0;
@@ -684,4 +697,32 @@ extern "C" int ophip_encoder_layer_x3w8_streams(const float* x3d, const float* x
     X3Opts o;
     o.streams = streams;
     return layer_x3w8(x3d, x2d, y3d, y2d, B, L3d, L2d, wpack, nullptr, is_cross, 0, 0, workspace, stream, nullptr, nullptr, nullptr, false, o);
+}
+
+// The layer with a padding mask on EACH stream (LoFTR's mask0 / mask1 = data["mask*"].flatten(-2), loftr/loftr_module/transformer.py
+// LocalFeatureTransformer.forward): mask0 [B][L3d] for the first stream, mask1 [B][L2d] for the second, 1 = real cell, 0 = padding; either
+// may be NULL (that stream unmasked).  A stream's mask acts where the stream is a SOURCE (kv_reduce and the fused tail: phi(K) and with it
+// its K^T V / Ksum terms are zero for a padded row -- kv_mask) and where it is a QUERY (attn_apply: phi(Q) = 0, so the padded row's message
+// is 0 -- q_mask); the padded rows still go through merge, LayerNorm, MLP and residual.  v_length stays the padded length.  Other
+// arguments as ophip_encoder_layer_x3w8.  Runs the MASKED + BOTH instantiation of the kernels (not bit-identical to the plain layer).
+extern "C" int ophip_encoder_layer_x3w8_masks(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
+                                              const void* wpack, const void* wpack_next, int is_cross, int kv_from_prev, int slot,
+                                              void* workspace, const unsigned char* mask0, const unsigned char* mask1, void* stream) {
+    X3Opts o;
+    o.both_masks = true;
+    o.mask3d = mask0;
+    return layer_x3w8(x3d, x2d, y3d, y2d, B, L3d, L2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace, stream, nullptr, nullptr, mask1, false, o);
+}
+
+// ophip_encoder_layer_x3w8_streams with the two padding masks of ophip_encoder_layer_x3w8_masks (either may be NULL).  In a one-stream
+// cross launch the other stream is the source: its mask drops its padded rows from K / V, the running stream's mask zeroes phi(Q).
+extern "C" int ophip_encoder_layer_x3w8_streams_masks(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
+                                                      const void* wpack, int is_cross, int streams, void* workspace,
+                                                      const unsigned char* mask0, const unsigned char* mask1, void* stream) {
+    if (streams < 1 || streams > 3) return ophip_bad_arg(__func__, "streams must be 1, 2 or 3");
+    X3Opts o;
+    o.streams = streams;
+    o.both_masks = true;
+    o.mask3d = mask0;
+    return layer_x3w8(x3d, x2d, y3d, y2d, B, L3d, L2d, wpack, nullptr, is_cross, 0, 0, workspace, stream, nullptr, nullptr, mask1, false, o);
 }

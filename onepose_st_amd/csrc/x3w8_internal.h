@@ -25,8 +25,12 @@ bool ophip_coarse_two_pass(int B, int N, int M);
 // S = <f0, f1> / C into conf [B][N][M], the merged row (max, sum exp) in *rowstat [B][N][2], column maxima cleared; *rowbest / *colmax_bits
 // are the workspace's row-best records and column maxima that ophip_coarse_select_2d reads.  workspace: ophip_coarse_workspace_floats
 int ophip_coarse_sim_store(const float* feat0, const float* feat1, int B, int N, int M, float* conf, float* workspace,
-                           const float** rowstat, float** rowbest, unsigned** colmax_bits, void* stream);
-// ophip_coarse_match_2d's selection (border on all four sides of both grids) over those records, nspan per row
+                           const float** rowstat, float** rowbest, unsigned** colmax_bits, void* stream,
+                           const unsigned char* mask0 = nullptr, const unsigned char* mask1 = nullptr);
+// (mask0 [B][N] / mask1 [B][M], both or neither: LoFTR's padding masks, the similarity entries of a padded row or column set to -1e9)
+// ophip_coarse_match_2d's selection (border on all four sides of both grids) over those records, nspan per row; with mask0 / mask1 the
+// border follows each pair's valid extent (mask_border_with_padding, as ophip_coarse_match_2d_masked)
 int ophip_coarse_select_2d(const float* conf, int nspan, const float* points0, long long points_bstride, int B, int N, int M, int wi, int wc,
                            float thr, int border_rm, float scale, float* workspace, long long* b_ids, long long* i_ids, long long* j_ids,
-                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream);
+                           float* mconf, float* mkpts0, float* mkpts1_c, long long* m_bids, unsigned char* gt_mask, int* count, void* stream,
+                           const unsigned char* mask0 = nullptr, const unsigned char* mask1 = nullptr);

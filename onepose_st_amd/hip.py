@@ -95,6 +95,8 @@ _SIGNATURES = {
     "ophip_encoder_x3w8_wpack_bytes": (ctypes.c_size_t, []),
     "ophip_encoder_layer_x3w8": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
     "ophip_encoder_layer_x3w8_streams": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_f, ctypes.c_void_p]),
+    "ophip_encoder_layer_x3w8_masks": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, ctypes.c_void_p]),
+    "ophip_encoder_layer_x3w8_streams_masks": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_f, c_f, c_f, ctypes.c_void_p]),
     "ophip_encoder_kv_first_x3w8": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_f, ctypes.c_void_p]),
     "ophip_encoder_layer_x3w8_frag": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "ophip_coarse_frag_planes": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
@@ -121,9 +123,14 @@ _SIGNATURES = {
                                             c_f, c_f, c_i, ctypes.c_uint, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
     "ophip_coarse_match_2d": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
                                     c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
+    "ophip_coarse_match_2d_masked": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
+                                           c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, ctypes.c_void_p]),
     "ophip_coarse_sinkhorn_workspace_floats": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "ophip_coarse_match_2d_sinkhorn": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_i, c_i, ctypes.c_float, c_i,
                                              ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
+    "ophip_coarse_match_2d_sinkhorn_masked": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_i, c_i, ctypes.c_float, c_i,
+                                                    ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
+                                                    ctypes.c_void_p]),
     "ophip_fine2_gather": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
     "ophip_fine2_gather_b": (c_i, [c_f, c_ll, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
     "ophip_rows_linear_wpack_bytes": (ctypes.c_size_t, [c_i, c_i]),

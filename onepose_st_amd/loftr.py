@@ -37,8 +37,19 @@ The SfM calls (``loftr_for_sfm/loftr.py:79-167``):
 * ``extract_coarse_feature`` / ``extract_fine_feature``: ``feat_coarse_b_{0,1} [K, 256]`` (nearest) and ``feat_ext{0,1} [K, 128]``
   (bilinear) sampled from the backbone maps before the positional encoding at ``mkpts*_f``, one ``ophip_sample_features`` launch.
 
-Padding masks (``mask0`` / ``mask1``), malformed scale / keypoint tensors, a tensor without its partner, V > 1 with provided matches or
-extraction, and coarse extraction with a ``feature_hook`` raise ``NotImplementedError`` before anything runs.  No CPU fallback.
+Padding masks ``mask0`` / ``mask1`` (``loftr_for_sfm/loftr.py:38-42, 72-78``): ``torch.bool`` ``[V, h0c, w0c]`` and
+``[V1, h1c, w1c]`` at coarse resolution (``True`` = a real cell; ``V1`` = image1's batch, a batch-1 ``mask1`` is repeated for every pair),
+on the device, both or neither.  They mask both streams of every coarse layer (``ophip_encoder_layer_x3w8_masks`` /
+``ophip_encoder_layer_x3w8_streams_masks``: phi(K), V of padded source rows and phi(Q) of padded query rows are zero, ``v_length`` stays
+the padded length), fill the similarity with -1e9 where either cell is padding and take the border from each pair's valid extent
+(``ophip_coarse_match_2d_masked`` / ``ophip_coarse_match_2d_sinkhorn_masked``, ``mask_border_with_padding``).  The fine stage, the
+scales, extraction and the fine-only branch (which ignores them, as the reference does) are unchanged.  With ``coarse.attention =
+"full"`` masks raise: the published ``FullAttention`` fills a padded query row with -inf, its softmax is NaN, and the NaN reaches every
+row one layer later.
+
+Malformed masks (a lone mask, another dtype, image-resolution masks, a wrong batch or grid), malformed scale / keypoint tensors, a tensor
+without its partner, V > 1 with provided matches or extraction, and coarse extraction with a ``feature_hook`` raise
+``NotImplementedError`` before anything runs.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -165,21 +176,25 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         return self._pe[k]
 
     # ------------------------------------------------------------------------------------------
-    def _coarse_linear(self, Wc, fc0, fc1, shared1, V, L0, L1):
+    def _coarse_linear(self, Wc, fc0, fc1, shared1, V, L0, L1, masks=None):
+        """``masks``: None or the flattened padding masks ``(m0 [V, L0], m1 [V, L1])`` (bool, contiguous; a shared query's mask already
+        repeated with its rows)"""
         call, P, S = hip.call, hip.ptr, hip.stream_handle()
         x0 = fc0.contiguous()
         x1 = (fc1.expand(V, -1, -1) if shared1 else fc1).contiguous()
         ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(V, L0, L1), dtype=torch.uint8, device=x0.device)
+        mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
+        sfx = "" if masks is None else "_masks"
         for w, name in zip(Wc, self.loftr_coarse.layer_names):
             if name == "self":
                 b0, b1 = torch.empty_like(x0), torch.empty_like(x1)
-                call("ophip_encoder_layer_x3w8", P(x0), P(x1), P(b0), P(b1), V, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None), S)
+                call("ophip_encoder_layer_x3w8" + sfx, P(x0), P(x1), P(b0), P(b1), V, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None), *mk, S)
                 x0, x1 = b0, b1
             else:
                 n0 = torch.empty_like(x0)              # image 0 against image 1
-                call("ophip_encoder_layer_x3w8_streams", P(x0), P(x1), P(n0), None, V, L0, L1, P(w, None), 1, 1, P(ws, None), S)
+                call("ophip_encoder_layer_x3w8_streams" + sfx, P(x0), P(x1), P(n0), None, V, L0, L1, P(w, None), 1, 1, P(ws, None), *mk, S)
                 n1 = torch.empty_like(x1)              # image 1 against the UPDATED image 0
-                call("ophip_encoder_layer_x3w8_streams", P(n0), P(x1), None, P(n1), V, L0, L1, P(w, None), 1, 2, P(ws, None), S)
+                call("ophip_encoder_layer_x3w8_streams" + sfx, P(n0), P(x1), None, P(n1), V, L0, L1, P(w, None), 1, 2, P(ws, None), *mk, S)
                 x0, x1 = n0, n1
         return x0, x1
 
@@ -210,10 +225,19 @@ class LoFTR_for_OnePose_Plus(nn.Module):
 
     def _check_inputs(self, data, kwargs):
         """the input forms outside what the kernels cover raise before anything runs; -> (fine_only, has_scales, extract_c, extract_f)"""
-        for k in ("mask0", "mask1"):
-            if k in data:
-                raise NotImplementedError(f"'{k}' input: padding masks are not supported")
         V, V1 = data["image0"].size(0), data["image1"].size(0)
+        has_m = "mask0" in data
+        if has_m != ("mask1" in data):
+            raise NotImplementedError("'mask0' and 'mask1' come together")
+        if has_m:
+            for k, img, rows in (("mask0", data["image0"], V), ("mask1", data["image1"], V1)):
+                t = data[k]
+                grid = (rows, img.shape[2] // 8, img.shape[3] // 8)
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.bool or tuple(t.shape) != grid:
+                    raise NotImplementedError(f"'{k}': a torch.bool tensor {list(grid)} at coarse resolution (H / 8 x W / 8)")
+            if self.coarse_full:
+                raise NotImplementedError("padding masks with coarse.attention 'full': the published FullAttention fills a padded query row "
+                                          "with -inf, its softmax is NaN and the NaN reaches every row one layer later")
         ext_c, ext_f = bool(kwargs.get("extract_coarse_feature", False)), bool(kwargs.get("extract_fine_feature", False))
         has_s = "scale0" in data
         if has_s != ("scale1" in data):
@@ -243,7 +267,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                                           "encoding, the reference samples the map before it")
             if not has_s:
                 raise KeyError("scale0")
-        tensors = [data["image0"], data["image1"]] + [data[k] for k in ("scale0", "scale1", "mkpts0_c", "mkpts1_c") if k in data]
+        tensors = [data["image0"], data["image1"]] + [data[k] for k in ("scale0", "scale1", "mkpts0_c", "mkpts1_c", "mask0", "mask1") if k in data]
         if not all(t.is_cuda for t in tensors):
             raise hip.HipLibraryError("LoFTR_for_OnePose_Plus runs on the HIP device only (no CPU fallback)")
         return fine_only, has_s, ext_c, ext_f
@@ -317,10 +341,14 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         else:
             # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
             #      full: one one-stream launch per image and layer, the shared query read with batch stride 0 -----------------------
+            masks = None
+            if "mask0" in data:                        # flattened, the query's repeated for every pair (read only: never written)
+                m1 = data["mask1"].reshape(-1, L1)
+                masks = (data["mask0"].reshape(V, L0).contiguous(), (m1.expand(V, -1) if m1.shape[0] != V else m1).contiguous())
             if self.coarse_full:
                 x0, x1 = self._coarse_full(Wb["coarse"], fc0.contiguous(), fc1.contiguous(), V, L0, L1)
             else:
-                x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, shared1, V, L0, L1)
+                x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, shared1, V, L0, L1, masks)
 
             # ---- coarse matching between the two grids -------------------------------------------------------------------------
             mc = self.config["match_coarse"]
@@ -336,12 +364,15 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             count = torch.zeros(4, dtype=torch.int32, device=dev)
             outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
                     P(gt_mask, torch.bool), P(count, torch.int32))
+            mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
+            sfx = "" if masks is None else "_masked"
             if self.sinkhorn:
-                call("ophip_coarse_match_2d_sinkhorn", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"], int(mc["skh_iters"]),
-                     1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, S)
+                call("ophip_coarse_match_2d_sinkhorn" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"],
+                     int(mc["skh_iters"]), 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws),
+                     *outs, *mk, S)
             else:
-                call("ophip_coarse_match_2d", P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]), float(mc["thr"]),
-                     int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, S)
+                call("ophip_coarse_match_2d" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]),
+                     float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, *mk, S)
             K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
             b_ids, i_ids, j_ids = ids[0][:K], ids[1][:K], ids[2][:K]
             mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
