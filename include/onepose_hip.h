@@ -552,6 +552,28 @@ int ophip_postopt_points_from_depth(const double* keypoints, const double* depth
 int ophip_postopt_project_points(const double* points, const long long* frame_idx, int N, const double* K, const double* R, const double* t,
                                  int F, double* keypoints, void* stream);
 
+/* The keypoint-free SfM's coarse-match merge (coarse_match/coarse_match.py:141-186, non-Ray branch): Match2Pts2D (coarse_match/utils.py:20-61)
+ * with points2D_worker / agg_groupby_2d (coarse_match_worker.py:87-111, utils.py:5-18), update_matches (coarse_match_worker.py:119-155) and
+ * transform_points2D (:163-183) on flat arrays.  P pairs (pair_images [P][2] = img0, img1 in [0, I), never equal), pair p owning rows
+ * pair_offsets[p] .. pair_offsets[p + 1] - 1 (pair_offsets [P + 1], non-decreasing, 0 .. T); per row mkpts0 / mkpts1 [T][2] and mconf [T]
+ * float32.  Row t gives the observations (img0, int(mkpts0[t]), mconf[t]) and (img1, int(mkpts1[t]), mconf[t]), int() truncating toward
+ * zero.  A key's score is the float64 sum of its observations' mconf in ascending row order; keys are ranked per image by score
+ * descending, equal scores in signed (x, y) lexicographic order.  The caller validates (finite values, |int(.)| < 2^20, image indices,
+ * no self-pair, every image observed): a bad image index writes nothing past the outputs, its keys get rank -1.  Deterministic.
+ *   ophip_sfm_points2d_workspace_bytes  bytes of the workspace for T rows and I images (0: bad sizes, 1 <= T <= MAX_ROWS, 1 <= I <= MAX_IMAGES)
+ *   ophip_sfm_points2d_group   expand, stable radix sort of the 2T keys, runs of equal keys; *unique_count (device int) = U, the number of
+ *                              distinct (image, x, y) keys, which sizes the outputs of the second call
+ *   ophip_sfm_points2d_rank    the scores, the ranking, and keypoints [U][2] (x, y) / scores [U] (float32 of the sum) image after image in
+ *                              rank order, kpt_offsets [I + 1] (int64) and match_ids [T][2] (int64: the rank of row t's key in img0, in img1).
+ *                              Same workspace, untouched in between.  workspace 256-byte aligned. */
+#define OPHIP_SFM_POINTS2D_MAX_ROWS ((1LL << 30) - 1)
+#define OPHIP_SFM_POINTS2D_MAX_IMAGES (1 << 22)
+size_t ophip_sfm_points2d_workspace_bytes(long long T, int I);
+int ophip_sfm_points2d_group(const float* mkpts0, const float* mkpts1, const long long* pair_offsets, const long long* pair_images, int P,
+                             long long T, int I, void* workspace, size_t workspace_bytes, int* unique_count, void* stream);
+int ophip_sfm_points2d_rank(const float* mconf, long long T, int I, int U, void* workspace, size_t workspace_bytes, float* keypoints,
+                            float* scores, long long* kpt_offsets, long long* match_ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,11 @@ _SIGNATURES = {
                                               ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p]),
     "ophip_postopt_project_points": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i,
                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "ophip_sfm_points2d_workspace_bytes": (ctypes.c_size_t, [c_ll, c_i]),
+    "ophip_sfm_points2d_group": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, c_ll, c_i, ctypes.c_void_p,
+                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "ophip_sfm_points2d_rank": (c_i, [ctypes.c_void_p, c_ll, c_i, c_i, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
