@@ -12,23 +12,27 @@ import os
 
 import torch
 
-_LIB_PATH = os.environ.get("OPHIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libonepose_hip.so")   # OPHIP_LIB: A/B builds
-_lib = None
-ABI_VERSION = 4         # include/onepose_hip.h OPHIP_ABI_VERSION: what FrameDesc / FrameLayout / _SIGNATURES below are written for
+from . import cabi
 
-c_f = ctypes.c_void_p      # device float*
+_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+_LIB_PATH = os.environ.get("OPHIP_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_hip.so")   # OPHIP_LIB: A/B builds
+_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_hip.h")             # where csrc/Makefile finds it too
+_lib = None
+# The header is the one place a signature, a structure or a constant of the C ABI is written: an entry point is added there and in its
+# .hip file, nothing here.  (A missing header leaves the tables empty and load() says so.)
+_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
+ABI_VERSION = _HEADER.defines.get("OPHIP_ABI_VERSION")                  # what the FrameDesc / FrameLayout mirrors below are written for
+SAMPLE_MAX_JOBS = _HEADER.defines.get("OPHIP_SAMPLE_MAX_JOBS")
+COARSE_PLANES_READY = _HEADER.defines.get("OPHIP_COARSE_PLANES_READY")    # or-ed into ophip_coarse_match's nsplit
+
 c_i = ctypes.c_int
 c_ll = ctypes.c_longlong
-
 
 
 class SampleJob(ctypes.Structure):
     """``ophip_sample_job`` (include/onepose_hip.h): one map / keypoint set of ``ophip_sample_features``"""
     _fields_ = [("map", ctypes.c_void_p), ("keypoints", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("out", ctypes.c_void_p),
                 ("h", c_i), ("w", c_i), ("C", c_i), ("K", c_i), ("H", c_i), ("W", c_i), ("keypoints_double", c_i), ("nearest", c_i)]
-
-
-SAMPLE_MAX_JOBS = 4     # OPHIP_SAMPLE_MAX_JOBS
 
 
 class FrameDesc(ctypes.Structure):
@@ -55,124 +59,10 @@ class ObjectCache(ctypes.Structure):
                 ("kv1", ctypes.c_void_p), ("kv1_bs", c_ll), ("ready", ctypes.c_void_p)]
 
 
-_SIGNATURES = {
-    "ophip_abi_version": (c_i, []),
-    "ophip_build_stamp": (ctypes.c_char_p, []),
-    "ophip_last_error": (ctypes.c_char_p, []),
-    "ophip_roctx_enable": (c_i, [c_i]),
-    "ophip_roctx_ranges": (c_ll, []),
-    "ophip_device_info": (c_i, [ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.c_char_p, c_i]),
-    "ophip_timing_select": (c_i, [ctypes.c_char_p]),
-    "ophip_timing_read": (c_i, [ctypes.POINTER(c_i), ctypes.POINTER(ctypes.c_double)]),
-    "ophip_timing_every": (c_i, [c_i]),
-    "ophip_debug_stamps": (c_i, [ctypes.c_void_p]),
-    "ophip_frame_layout": (c_i, [ctypes.POINTER(FrameDesc), c_i, c_i, ctypes.POINTER(FrameLayout)]),
-    "ophip_frame_enqueue": (c_i, [ctypes.POINTER(FrameDesc), ctypes.POINTER(FrameLayout), ctypes.c_void_p,
-                                  c_f, c_f, c_ll, c_ll, c_ll, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_ll, c_f,
-                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.POINTER(c_i)]),
-    "ophip_frame_enqueue_padded": (c_i, [ctypes.POINTER(FrameDesc), ctypes.POINTER(FrameLayout), ctypes.c_void_p,
-                                         c_f, c_f, c_ll, c_ll, c_ll, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_ll, c_f, c_f, c_f,
-                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.POINTER(c_i)]),
-    "ophip_frame_enqueue_object": (c_i, [ctypes.POINTER(FrameDesc), ctypes.POINTER(FrameLayout), ctypes.c_void_p,
-                                         c_f, c_f, c_ll, c_ll, c_ll, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_ll, ctypes.POINTER(ObjectCache), c_f, c_f,
-                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.POINTER(c_i)]),
-    "ophip_encoder_x3w8_kv_block_bytes": (ctypes.c_size_t, []),
-    "ophip_encoder_object_x3w8": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
-    "ophip_frame_wait": (c_i, [c_i]),
-    "ophip_frame_order_after_fine": (c_i, [ctypes.c_void_p]),
-    "ophip_pe_add_transpose": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_void_p]),
-    "ophip_transpose_cl": (c_i, [c_f, c_f, c_i, c_i, c_i, ctypes.c_void_p]),
-    "ophip_kpt_encode": (c_i, [c_f, c_ll, c_f, c_ll, c_f, c_f, c_f, c_i, c_i, ctypes.c_void_p]),
-    "ophip_encoder_workspace_floats": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_encoder_layer": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, ctypes.c_void_p]),
-    "ophip_encoder_bf16_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_encoder_bf16_wpack_bytes": (ctypes.c_size_t, []),
-    "ophip_encoder_layer_bf16": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_encoder_x3w8_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_encoder_x3w8_wpack_bytes": (ctypes.c_size_t, []),
-    "ophip_encoder_layer_x3w8": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_x3w8_streams": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_x3w8_masks": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_x3w8_streams_masks": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_kv_first_x3w8": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_x3w8_frag": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ophip_coarse_frag_planes": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
-    "ophip_coarse_workspace_floats": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_coarse_match": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
-                                 c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
-    "ophip_coarse_match_conf": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
-                                 c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
-    "ophip_coarse_match_select": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
-                                 c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
-    "ophip_fine_refine": (c_i, [c_f, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_f, c_ll, c_ll, c_f, c_f, c_f, c_f, c_i,
-                                c_f, c_f, c_i, ctypes.c_uint, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_fine_bf16_wpack_bytes": (ctypes.c_size_t, [c_i]),
-    "ophip_fine_refine_bf16": (c_i, [c_f, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_f, c_ll, c_ll, c_f, c_f, c_f, c_f, c_i,
-                                     c_f, c_f, c_i, ctypes.c_uint, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_masked": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_bf16_masked": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_layer_x3w8_masked": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_coarse_match_masked": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
-                                        c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_fine_refine_scaled": (c_i, [c_f, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_f, c_ll, c_ll, c_f, c_f, c_f, c_f, c_i,
-                                       c_f, c_f, c_i, ctypes.c_uint, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_fine_refine_bf16_scaled": (c_i, [c_f, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_f, c_ll, c_ll, c_f, c_f, c_f, c_f, c_i,
-                                            c_f, c_f, c_i, ctypes.c_uint, c_i, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_coarse_match_2d": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
-                                    c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
-    "ophip_coarse_match_2d_masked": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_float, c_i, ctypes.c_float,
-                                           c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_coarse_sinkhorn_workspace_floats": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_coarse_match_2d_sinkhorn": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_i, c_i, ctypes.c_float, c_i,
-                                             ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_coarse_match_2d_sinkhorn_masked": (c_i, [c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_i, c_i, ctypes.c_float, c_i,
-                                                    ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
-                                                    ctypes.c_void_p]),
-    "ophip_fine2_gather": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_fine2_gather_b": (c_i, [c_f, c_ll, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_rows_linear_wpack_bytes": (ctypes.c_size_t, [c_i, c_i]),
-    "ophip_rows_linear_x3": (c_i, [c_f, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_fine2_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_rows_layernorm128": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, ctypes.c_void_p]),
-    "ophip_fine2_match": (c_i, [c_f, c_f, c_f, c_i, c_i, ctypes.c_float, c_f, c_f, ctypes.c_void_p]),
-    "ophip_conv_wpack_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_stem_conv7": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_i, ctypes.c_void_p]),
-    "ophip_conv2d_bf16": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_i, c_f,
-                                c_f, c_f, c_f, c_i, c_i, ctypes.c_void_p]),
-    "ophip_crop_resize_gray": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_encoder_full_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_encoder_layer_full_x3": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, ctypes.c_void_p]),
-    "ophip_full_attention_h8d32": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_fine_full_gather": (c_i, [c_f, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_f, c_ll, c_ll, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
-                                     c_f, c_f, ctypes.c_void_p]),
-    "ophip_fine_full_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_fine_full_match": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_float, c_f, c_f, ctypes.c_void_p]),
-    "ophip_encoder_full_stream_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
-    "ophip_encoder_layer_full_x3_stream": (c_i, [c_f, c_ll, c_f, c_ll, c_f, c_i, c_i, c_i, c_f, c_f, ctypes.c_void_p]),
-    "ophip_fine2_full_attention": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, ctypes.c_void_p]),
-    "ophip_fine2_match_scaled": (c_i, [c_f, c_f, ctypes.c_void_p, c_i, c_f, c_f, c_ll, c_i, c_i, ctypes.c_float, c_f, ctypes.c_void_p,
-                                       ctypes.c_void_p]),
-    "ophip_loftr_coarse_ids": (c_i, [ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_float,
-                                     c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p]),
-    "ophip_sample_features": (c_i, [ctypes.POINTER(SampleJob), c_i, ctypes.c_void_p]),
-    "ophip_postopt_workspace_bytes": (ctypes.c_size_t, [c_ll, c_i, c_i]),
-    "ophip_postopt_refine": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, c_ll, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, c_i,
-                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "ophip_postopt_points_from_depth": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p]),
-    "ophip_postopt_project_points": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i,
-                                           ctypes.c_void_p, ctypes.c_void_p]),
-    "ophip_sfm_points2d_workspace_bytes": (ctypes.c_size_t, [c_ll, c_i]),
-    "ophip_sfm_points2d_group": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, c_ll, c_i, ctypes.c_void_p,
-                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "ophip_sfm_points2d_rank": (c_i, [ctypes.c_void_p, c_ll, c_i, c_i, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-}
+_MIRRORS = {"ophip_sample_job": SampleJob, "ophip_frame_desc": FrameDesc, "ophip_frame_layout_t": FrameLayout, "ophip_object_cache": ObjectCache}
+for _name, _fields in _HEADER.structs.items():
+    cabi.check_mirror(_MIRRORS[_name], _name, _fields)
+_SIGNATURES = {name: cabi.signature(proto, _MIRRORS) for name, proto in _HEADER.prototypes.items()}      # name -> (restype, argtypes)
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -193,6 +83,8 @@ def load():
         return _lib
     if not os.path.exists(_LIB_PATH):
         raise HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
+    if not _HEADER.prototypes:
+        raise HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
     lib = ctypes.CDLL(_LIB_PATH)
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)
@@ -228,7 +120,13 @@ def stream_handle():
 
 
 def call(name: str, *args):
-    rc = getattr(load(), name)(*args)
+    """Call an entry point that returns a status and raise on failure.  ctypes accepts surplus arguments silently (a stream handle one
+    slot late would reach C), so the count is checked against the header's prototype first."""
+    fn = getattr(load(), name)
+    params = _HEADER.prototypes[name].params
+    if len(args) != len(params):
+        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
+    rc = fn(*args)
     _check(rc, name)
 
 

@@ -87,7 +87,7 @@ def _encoder_layer_x3w8(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from
 
 def _encoder_layer_x3w8_frag(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace, coarse_workspace):
     """the LAST encoder layer: its rows also land in ``coarse_workspace`` as the similarity kernel's operand fragments
-    (then ``coarse_match(..., nsplit | 0x100)``)"""
+    (then ``coarse_match(..., nsplit | hip.COARSE_PLANES_READY)``)"""
     B, L3, L2 = x3d.shape[0], x3d.shape[1], x2d.shape[1]
     if coarse_workspace.dtype != torch.float32 or coarse_workspace.numel() < hip.load().ophip_coarse_workspace_floats(B, L3, L2):
         raise ValueError("coarse_workspace: ophip_coarse_workspace_floats(B, N, M) float32 elements needed")

@@ -8,7 +8,11 @@ import os
 
 import numpy as np
 
-_LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
+from . import cabi
+
+_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+_LIB_DIR = os.path.join(_PKG_DIR, "lib")
+_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_pnp.h")
 _LIB_PATH = os.path.join(_LIB_DIR, "libonepose_pnp.so")
 _lib = None
 
@@ -31,28 +35,10 @@ def load():
         if not os.path.exists(path):
             raise RuntimeError(f"{path} not found: run __graft_entry__.build()")
         lib = ctypes.CDLL(path)
-        lib.oppnp_ransac.restype = ctypes.c_int
-        lib.oppnp_ransac.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                     ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        lib.oppnp_p3p.restype = ctypes.c_int
-        lib.oppnp_p3p.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.oppnp_pool_create.restype = ctypes.c_void_p
-        lib.oppnp_pool_create.argtypes = [ctypes.c_int]
-        lib.oppnp_pool_destroy.argtypes = [ctypes.c_void_p]
-        lib.oppnp_pool_submit.restype = ctypes.c_longlong
-        lib.oppnp_pool_submit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
-                                          ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int]
-        lib.oppnp_pool_wait_all.restype = ctypes.c_longlong
-        lib.oppnp_pool_wait_all.argtypes = [ctypes.c_void_p]
-        lib.oppnp_pool_result.restype = ctypes.c_int
-        lib.oppnp_pool_result.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        lib.oppnp_estimate_affine2d.restype = ctypes.c_int
-        lib.oppnp_estimate_affine2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
-                                                ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        lib.oppnp_p3p4.restype = None
-        lib.oppnp_p3p4.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        if lib.oppnp_abi_version() != 3:
+        for name, proto in cabi.parse(open(_HEADER_PATH).read()).prototypes.items():       # the header is the one place the signatures are written
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = cabi.signature(proto)
+        if lib.oppnp_abi_version() != 3:         # the header defines no number for it
             raise RuntimeError("libonepose_pnp.so ABI version mismatch")
         _lib = lib
     return _lib

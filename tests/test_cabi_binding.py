@@ -1,0 +1,258 @@
+"""The Python bindings take every C signature, constant and structure layout from ``include/*.h`` (``onepose_st_amd/cabi.py``).
+CPU only: the reader on the real headers and on made-up ones, the structure mirrors, the arity check of ``hip.call``, and three faults
+seeded into copies of the header that the prototypes written out below must catch."""
+import ctypes
+import os
+import re
+
+import pytest
+
+from onepose_st_amd import cabi, hip
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIP_H = open(os.path.join(REPO, "include", "onepose_hip.h")).read()
+PNP_H = open(os.path.join(REPO, "include", "onepose_pnp.h")).read()
+
+LL4 = "long long, long long, long long, long long"
+# (name, return type, parameter types): written from the headers by hand, one of every type the headers use
+WRITTEN_OUT = [
+    ("ophip_coarse_match_masked", "int",
+     "const float*, const float*, const float*, long long, int, int, int, int, double, float, int, float, "
+     "float*, float*, long long*, long long*, long long*, float*, float*, float*, long long*, unsigned char*, "
+     "int*, int, int, const unsigned char*, const float*, void*"),
+    ("ophip_fine_refine_bf16_scaled", "int",
+     f"const float*, {LL4}, int, int, const float*, long long, long long, "
+     "const long long*, const long long*, const long long*, const int*, int, const float*, const void*, int, unsigned, int, int, "
+     "int, int, float, float*, float*, float*, float*, const float*, void*"),
+    ("ophip_frame_enqueue_object", "int",
+     f"const ophip_frame_desc*, const ophip_frame_layout_t*, void*, const float*, const float*, {LL4}, "
+     "const float*, long long, const float*, long long, const float*, long long, long long, const ophip_object_cache*, "
+     "const unsigned char*, const float*, void*, size_t, void*, void*, void*, void*, int*"),
+    ("ophip_postopt_refine", "int",
+     "double*, const long long*, int, long long, const double*, const double*, const double*, const double*, const long long*, "
+     "const long long*, const double*, int, const double*, int, double, double, double, double*, int*, double*, void*, size_t, void*"),
+    ("ophip_sfm_points2d_rank", "int",
+     "const float*, long long, int, int, void*, size_t, float*, float*, long long*, long long*, void*"),
+    ("ophip_device_info", "int", "int*, int*, char*, int"),
+    ("ophip_coarse_frag_planes", "int", "float*, int, int, int, void**, void**"),
+    ("ophip_sample_features", "int", "const ophip_sample_job*, int, void*"),
+    ("ophip_build_stamp", "const char*", ""),
+    ("ophip_roctx_ranges", "long long", ""),
+    ("ophip_postopt_workspace_bytes", "size_t", "long long, int, int"),
+    ("oppnp_pool_result", "int", "void*, long long, double*, int*"),
+    ("oppnp_pool_create", "void*", "int"),
+    ("oppnp_p3p4", "void", "const double*, const double*, double*, int*"),
+    ("oppnp_ransac", "int", "const double*, const float*, const float*, int, double, double, int, int, unsigned long long, int, double*, "
+                            "unsigned char*, int*, int*"),
+]
+
+
+def check_written_out(*headers):
+    protos = {}
+    for h in headers:
+        protos.update(h.prototypes)
+    for name, ret, types in WRITTEN_OUT:
+        if name in protos:
+            p = protos[name]
+            assert (p.name, p.ret, [t for t, _ in p.params]) == (name, ret, types.split(", ") if types else []), name
+
+
+def test_reader_finds_every_prototype_of_both_headers():
+    hh, ph = cabi.parse(HIP_H), cabi.parse(PNP_H)
+    assert list(hh.prototypes) and set(hh.prototypes) == set(re.findall(r"\b(ophip_\w+)\s*\(", HIP_H))     # the expression of test_boundary_cpu
+    assert len(hh.prototypes) == len(hip.EXPORTED_SYMBOLS) == 83
+    assert set(ph.prototypes) == set(re.findall(r"\b(oppnp_\w+)\s*\(", PNP_H)) and len(ph.prototypes) == 10
+    assert all(name in hh.prototypes or name in ph.prototypes for name, _, _ in WRITTEN_OUT)
+    check_written_out(hh, ph)
+    p = hh.prototypes["ophip_coarse_match_masked"]
+    assert [n for _, n in p.params][3:8] == ["kpts_bstride", "B", "N", "M", "wc"] and p.params[-1] == ("void*", "stream")
+    assert hh.defines == {"OPHIP_ABI_VERSION": 4, "OPHIP_COARSE_PLANES_READY": 0x100, "OPHIP_SAMPLE_MAX_JOBS": 4}
+    assert (hip.ABI_VERSION, hip.COARSE_PLANES_READY, hip.SAMPLE_MAX_JOBS) == (4, 0x100, 4)
+    assert ph.defines == {} and ph.structs == {}
+
+
+def test_the_rule_from_c_types_to_ctypes_classes():
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    sig = hip._SIGNATURES
+    assert sig["ophip_device_info"] == (i, [vp, vp, ctypes.c_char_p, i])
+    assert sig["ophip_build_stamp"] == (ctypes.c_char_p, [])
+    assert sig["ophip_coarse_frag_planes"] == (i, [vp, i, i, i, ctypes.POINTER(vp), ctypes.POINTER(vp)])
+    assert sig["ophip_postopt_workspace_bytes"] == (ctypes.c_size_t, [ctypes.c_longlong, i, i])
+    res, args = sig["ophip_frame_enqueue_object"]
+    assert args[0] is ctypes.POINTER(hip.FrameDesc) and args[1] is ctypes.POINTER(hip.FrameLayout) and args[16] is ctypes.POINTER(hip.ObjectCache)
+    assert args[20] is ctypes.c_size_t and args[5] is ctypes.c_longlong and args[-1] is vp and len(args) == 26
+    assert sig["ophip_sample_features"][1][0] is ctypes.POINTER(hip.SampleJob)
+    res, args = sig["ophip_coarse_match_masked"]
+    assert [args[k] for k in (3, 8, 9)] == [ctypes.c_longlong, ctypes.c_double, ctypes.c_float]
+    res, args = sig["ophip_fine_refine_bf16_scaled"]
+    assert args[18] is ctypes.c_uint and len(args) == 30
+    pnp = cabi.parse(PNP_H).prototypes
+    assert cabi.signature(pnp["oppnp_p3p4"]) == (None, [vp, vp, vp, vp])
+    assert cabi.signature(pnp["oppnp_pool_create"]) == (vp, [i])
+    assert cabi.signature(pnp["oppnp_ransac"])[1][8] is ctypes.c_ulonglong
+    with pytest.raises(cabi.HeaderError):
+        cabi.ctype("void")           # only a return type
+
+
+MADE_UP = """
+/* a block comment with a prototype inside: int ophip_not_this(int x); */
+#ifndef X_H
+#define X_H
+#define OPHIP_SOME_FLAG 0x20   // trailing comment
+#define OPHIP_COUNT 12
+#define OPHIP_NOT_A_LITERAL ((1LL << 30) - 1)
+typedef struct ophip_thing {
+    int B, N, M;                 /* a declarator list */
+    const float* pe; long long pe_bs;
+    const void* w[16];           // an array field
+    size_t total,
+           used;
+} ophip_thing;
+int ophip_nothing(void);
+const char*
+ophip_several_lines(const float* a,     /* the first */
+                    long long a_bstride,  // the second
+                    const ophip_thing* thing,
+                    /* nothing here */
+                    unsigned bits, void** out,
+                    void* stream);
+size_t ophip_bytes(int n);   void ophip_two_on_a_line(double x);
+#endif
+"""
+
+
+def test_reader_on_made_up_headers():
+    h = cabi.parse(MADE_UP)
+    assert list(h.prototypes) == ["ophip_nothing", "ophip_several_lines", "ophip_bytes", "ophip_two_on_a_line"]
+    assert h.prototypes["ophip_nothing"] == ("ophip_nothing", "int", ())
+    assert h.prototypes["ophip_several_lines"] == ("ophip_several_lines", "const char*", (
+        ("const float*", "a"), ("long long", "a_bstride"), ("const ophip_thing*", "thing"), ("unsigned", "bits"), ("void**", "out"), ("void*", "stream")))
+    assert h.prototypes["ophip_two_on_a_line"] == ("ophip_two_on_a_line", "void", (("double", "x"),))
+    assert h.defines == {"OPHIP_SOME_FLAG": 0x20, "OPHIP_COUNT": 12}            # integer literals only
+    assert h.structs == {"ophip_thing": (("int", "B", None), ("int", "N", None), ("int", "M", None), ("const float*", "pe", None),
+                                         ("long long", "pe_bs", None), ("const void*", "w", 16), ("size_t", "total", None), ("size_t", "used", None))}
+
+
+@pytest.mark.parametrize("text,line", [
+    ("int ophip_a(int x);\n\nint ophip_fn_pointer(int (*cb)(int), void* stream);\n", 3),      # a parameter it cannot read
+    ("/* two\n lines */\nint ophip_b(struct foo* x);\n", 3),                                   # a type it does not know
+    ("int ophip_c(int);\n", 1),                                                                 # a parameter without a name
+    ("int ophip_d(int x)\n{ return x; }\n", 1),                                                 # not a prototype
+    ("short ophip_e(int x);\n", 1),                                                             # a return type outside the set
+    ("int ophip_f(int x);\n__attribute__((visibility(\"default\"))) int ophip_g(int x);\n", 2),      # a declaration in another form
+])
+def test_reader_fails_loudly(text, line):
+    with pytest.raises(cabi.HeaderError) as e:
+        cabi.parse(text)
+    assert f"line {line}," in str(e.value)
+    assert re.search(r"ophip_[b-g]|ophip_fn_pointer", str(e.value))
+
+
+def test_structure_mirrors_match_the_header():
+    structs = cabi.parse(HIP_H).structs
+    assert set(structs) == set(hip._MIRRORS) == {"ophip_frame_desc", "ophip_frame_layout_t", "ophip_object_cache", "ophip_sample_job"}
+    for name, fields in structs.items():
+        cabi.check_mirror(hip._MIRRORS[name], name, fields)
+    assert len(structs["ophip_frame_layout_t"]) == 22 and ("const void*", "w_coarse", 16) in structs["ophip_frame_desc"]
+
+    def mirror(fields):
+        return type("Mirror", (ctypes.Structure,), {"_fields_": fields})
+
+    good = list(hip.FrameDesc._fields_)
+    cabi.check_mirror(mirror(good), "ophip_frame_desc", structs["ophip_frame_desc"])
+    k = [n for n, _ in good].index("hc")
+    swapped = good[:k] + [good[k + 1], good[k]] + good[k + 2:]                  # same classes, two names in the other order
+    with pytest.raises(cabi.HeaderError, match=r"ophip_frame_desc\.hc"):
+        cabi.check_mirror(mirror(swapped), "ophip_frame_desc", structs["ophip_frame_desc"])
+    for bad, field in ((("temperature", ctypes.c_float), "temperature"), (("w_coarse", ctypes.c_void_p * 8), "w_coarse"),
+                       (("n_fine", ctypes.c_longlong), "n_fine")):
+        with pytest.raises(cabi.HeaderError, match=rf"ophip_frame_desc\.{field}"):
+            cabi.check_mirror(mirror([bad if n == bad[0] else (n, c) for n, c in good]), "ophip_frame_desc", structs["ophip_frame_desc"])
+    with pytest.raises(cabi.HeaderError):
+        cabi.check_mirror(mirror(good[:-1]), "ophip_frame_desc", structs["ophip_frame_desc"])
+    with pytest.raises(cabi.HeaderError):
+        cabi.check_mirror(mirror(good + [("extra", ctypes.c_int)]), "ophip_frame_desc", structs["ophip_frame_desc"])
+
+
+class _StandIn:
+    """in place of the library handle: records what would have reached C"""
+
+    def __init__(self):
+        self.entered = []
+
+    def __getattr__(self, name):
+        return lambda *args: self.entered.append((name, args)) or 0
+
+
+def test_call_checks_the_number_of_arguments(monkeypatch):
+    lib = _StandIn()
+    monkeypatch.setattr(hip, "_lib", lib)
+    args = (None, None, None, 1, 2, 3, None)                       # ophip_pe_add_transpose(feat_nchw, pe_nlc, out_nlc, B, C, M, stream)
+    hip.call("ophip_pe_add_transpose", *args)
+    assert lib.entered == [("ophip_pe_add_transpose", args)]
+    for wrong in (args + (None,), args[:-1]):
+        with pytest.raises(TypeError) as e:
+            hip.call("ophip_pe_add_transpose", *wrong)
+        msg = str(e.value)
+        assert "ophip_pe_add_transpose" in msg and "7" in msg and str(len(wrong)) in msg and "feat_nchw, pe_nlc, out_nlc, B, C, M, stream" in msg
+    with pytest.raises(TypeError):
+        hip.call("ophip_frame_wait")
+    with pytest.raises(TypeError):                                  # the spliced kind: an optional pointer too many pushes the stream one slot late
+        hip.call("ophip_encoder_layer_x3w8_streams", *([None] * 12), None)
+    assert len(lib.entered) == 1                                    # nothing else reached the handle
+
+
+def test_call_arity_with_the_real_library():
+    hip.call("ophip_timing_every", 1)                              # host side only
+    with pytest.raises(TypeError):
+        hip.call("ophip_timing_every", 1, 1)
+    with pytest.raises(TypeError):
+        hip.call("ophip_timing_every")
+    assert hip.load().ophip_encoder_workspace_floats(1, 7000, 4800) == (219 + 150 + 2) * 8448      # calls on the handle itself work as before
+
+
+def _seed(old, new, text=HIP_H, count=1):
+    assert text.count(old) >= 1
+    return text.replace(old, new, count)
+
+
+def test_seeded_fault_parameter_type():
+    """``long long kpts_bstride`` -> ``int`` in a copy of the header: the binding would pass a 32-bit stride"""
+    k = HIP_H.index("int ophip_coarse_match_masked(")
+    bad = cabi.parse(HIP_H[:k] + _seed("long long kpts_bstride", "int kpts_bstride", HIP_H[k:]))
+    assert cabi.signature(bad.prototypes["ophip_coarse_match_masked"])[1][3] is ctypes.c_int
+    with pytest.raises(AssertionError, match="ophip_coarse_match_masked"):
+        check_written_out(bad)
+    check_written_out(cabi.parse(HIP_H))
+
+
+def test_seeded_fault_parameter_removed():
+    k = HIP_H.index("int ophip_fine_refine_bf16_scaled(")
+    bad = cabi.parse(HIP_H[:k] + _seed("int encoder_enable, int nsplit,", "int encoder_enable,", HIP_H[k:]))
+    assert len(bad.prototypes["ophip_fine_refine_bf16_scaled"].params) == 29
+    with pytest.raises(AssertionError, match="ophip_fine_refine_bf16_scaled"):
+        check_written_out(bad)
+
+
+def test_seeded_fault_layout_field_moved():
+    bad = cabi.parse(_seed("size_t total, result_bytes;\n    size_t x2d, ffcl,", "size_t total, x2d;\n    size_t result_bytes, ffcl,"))
+    assert len(bad.structs["ophip_frame_layout_t"]) == 22
+    with pytest.raises(cabi.HeaderError, match=r"ophip_frame_layout_t\.x2d"):
+        cabi.check_mirror(hip.FrameLayout, "ophip_frame_layout_t", bad.structs["ophip_frame_layout_t"])
+
+
+def test_missing_header_is_reported_by_load(monkeypatch):
+    monkeypatch.setattr(hip, "_lib", None)
+    monkeypatch.setattr(hip, "_HEADER", cabi.parse(""))
+    monkeypatch.setattr(hip, "_HEADER_PATH", os.path.join(REPO, "include", "no_such_header.h"))
+    with pytest.raises(hip.HipLibraryError, match="no_such_header.h"):
+        hip.load()
+
+
+def test_pnp_binds_from_its_header():
+    from onepose_st_amd import pnp
+    lib = pnp.load()
+    for name, proto in cabi.parse(PNP_H).prototypes.items():
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == cabi.signature(proto), name
+    assert lib.oppnp_pool_destroy.restype is None and lib.oppnp_pool_submit.argtypes[9] is ctypes.c_ulonglong

@@ -243,7 +243,7 @@ def test_encoder_layer_writes_the_similarity_fragments(sd, dev, B, N, hc, wc):
     hip.call("ophip_coarse_frag_planes", hip.ptr(cws_b), B, N, M, ctypes.byref(pa), ctypes.byref(pb))
     hip.call("ophip_encoder_layer_x3w8_frag", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3b), hip.ptr(y2b), B, N, M, hip.ptr(w, None), None, 1, 0, 0,
              hip.ptr(ws, None), pa, pb, hip.stream_handle())
-    got = coarse(0x100, cws_b, y3b, y2b)
+    got = coarse(hip.COARSE_PLANES_READY, cws_b, y3b, y2b)
     assert torch.equal(y3a, y3b) and torch.equal(y2a, y2b)
     assert torch.equal(ref[0], got[0]) and all(torch.equal(a, b) for a, b in zip(ref[1], got[1])) and torch.equal(ref[2], got[2])
 
