@@ -12,6 +12,6 @@ cp -r $root/onepose_st_amd/csrc $tmp/onepose_st_amd/csrc
 cp -r $root/include $tmp/include
 rm -rf $tmp/onepose_st_amd/csrc/build
 [ "$rev" = "-" ] || for f in "$@"; do git -C $root show $rev:onepose_st_amd/csrc/$f > $tmp/onepose_st_amd/csrc/$f; done
-make -C $tmp/onepose_st_amd/csrc -j8 EXTRA="$EXTRA" OUT=$root/onepose_st_amd/lib/variants/libonepose_hip_$name.so > $tmp/build.log 2>&1 || { tail -20 $tmp/build.log; exit 1; }
+make -C $tmp/onepose_st_amd/csrc -j8 EXTRA="$EXTRA" OUT=$root/onepose_st_amd/lib/variants/libonepose_hip_$name.so $root/onepose_st_amd/lib/variants/libonepose_hip_$name.so > $tmp/build.log 2>&1 || { tail -20 $tmp/build.log; exit 1; }
 rm -rf $tmp
 echo built $root/onepose_st_amd/lib/variants/libonepose_hip_$name.so
