@@ -3,15 +3,24 @@
 # = the working tree's csrc with the listed files taken from <git rev>; result: onepose_st_amd/lib/variants/libonepose_hip_<name>.so
 # EXTRA="-D..." in the environment adds compiler flags; <git rev> may be "-" with no files (working tree + EXTRA only).
 # (load it with OPHIP_LIB=<path>; `tools/box.sh <name> ab:R:S:variants` runs variants interleaved on one box).  Variants are scratch: git-ignored like every .so.
+# A first <csrc file> of `sfm` or `sfm_tracks` is a goal, not a file: the variant is then one of libonepose_sfm.so (OPSFM_LIB) or
+# libonepose_sfm_tracks.so (OPSFT_LIB), e.g. the seeded faults of tests/test_gpu_sfm_tracks.py:
+#   EXTRA=-DOPSFT_FAULT_TIE_INITIAL_ORDER tools/build_variant.sh tie - sfm_tracks   -> lib/variants/libonepose_sfm_tracks_tie.so
 set -e
 name=$1; rev=$2; shift 2
 root=$(cd $(dirname $0)/.. && pwd)
+lib=libonepose_hip; var=OUT
+case "$1" in
+  sfm) lib=libonepose_sfm; var=SFM_OUT; shift;;
+  sfm_tracks) lib=libonepose_sfm_tracks; var=SFT_OUT; shift;;
+esac
 tmp=$(mktemp -d)
 mkdir -p $tmp/onepose_st_amd $root/onepose_st_amd/lib/variants
 cp -r $root/onepose_st_amd/csrc $tmp/onepose_st_amd/csrc
 cp -r $root/include $tmp/include
 rm -rf $tmp/onepose_st_amd/csrc/build
 [ "$rev" = "-" ] || for f in "$@"; do git -C $root show $rev:onepose_st_amd/csrc/$f > $tmp/onepose_st_amd/csrc/$f; done
-make -C $tmp/onepose_st_amd/csrc -j8 EXTRA="$EXTRA" OUT=$root/onepose_st_amd/lib/variants/libonepose_hip_$name.so $root/onepose_st_amd/lib/variants/libonepose_hip_$name.so > $tmp/build.log 2>&1 || { tail -20 $tmp/build.log; exit 1; }
+out=$root/onepose_st_amd/lib/variants/${lib}_$name.so
+make -C $tmp/onepose_st_amd/csrc -j8 EXTRA="$EXTRA" $var=$out $out > $tmp/build.log 2>&1 || { tail -20 $tmp/build.log; exit 1; }
 rm -rf $tmp
-echo built $root/onepose_st_amd/lib/variants/libonepose_hip_$name.so
+echo built $out
