@@ -115,6 +115,11 @@ def ptr(t: torch.Tensor | None, dtype=torch.float32):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def bstride(t: torch.Tensor) -> int:
+    """Batch stride in elements; an object block that the batch shares (batch 1, or a stride-0 expand) gives 0."""
+    return 0 if t.shape[0] == 1 or t.stride(0) == 0 else t.stride(0)
+
+
 def stream_handle():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 

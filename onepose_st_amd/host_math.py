@@ -39,6 +39,11 @@ def sinusoid_table(d_model: int, h: int, w: int, max_shape=(256, 256)) -> torch.
     return pe
 
 
+def pe_table(d_model: int, h: int, w: int, max_shape=(256, 256)) -> torch.Tensor:
+    """:func:`sinusoid_table` as the ``[h * w, d_model]`` rows the kernels add to a flattened coarse map."""
+    return sinusoid_table(d_model, h, w, max_shape).flatten(1).t().contiguous()
+
+
 def normalize_keypoints3d(kpts: torch.Tensor) -> torch.Tensor:
     """Centre per batch element, scale by 0.6 x the largest extent of batch element 0
     (``utils/normalize.py:17-28``)."""

@@ -62,6 +62,8 @@ import torch.nn as nn
 from . import hip, host_math, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
+from .params import EncoderParams, load_matcher_checkpoint
+from .rows import rows_encoder_layer
 
 default_cfg = {
     "backbone_type": "ResNetFPN", "resolution": (8, 2), "fine_window_size": 9, "fine_concat_coarse_feat": False,
@@ -71,28 +73,6 @@ default_cfg = {
                      "skh_init_bin_score": 1.0, "skh_prefilter": True, "train_coarse_percent": 0.4, "train_pad_num_gt_min": 200},
     "fine": {"d_model": 128, "d_ffn": 128, "nhead": 8, "layer_names": ["self", "cross"] * 1, "attention": "linear"},
 }
-
-
-class _Layer(nn.Module):
-    """parameter holder with the key layout of LoFTR's ``LoFTREncoderLayer``"""
-
-    def __init__(self, d):
-        super().__init__()
-        self.q_proj, self.k_proj, self.v_proj = (nn.Linear(d, d, bias=False) for _ in range(3))
-        self.merge = nn.Linear(d, d, bias=False)
-        self.mlp = nn.Sequential(nn.Linear(2 * d, 2 * d, bias=False), nn.Identity(), nn.Linear(2 * d, d, bias=False))
-        self.norm1, self.norm2 = nn.LayerNorm(d), nn.LayerNorm(d)
-
-
-class _Encoder(nn.Module):
-    def __init__(self, cfg):
-        super().__init__()
-        self.layer_names = list(cfg["layer_names"])
-        self.d_model, self.nhead = cfg["d_model"], cfg["nhead"]
-        self.layers = nn.ModuleList([_Layer(self.d_model) for _ in self.layer_names])
-        for p in self.parameters():
-            if p.dim() > 1:
-                nn.init.xavier_uniform_(p)
 
 
 class LoFTR_for_OnePose_Plus(nn.Module):
@@ -132,8 +112,8 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         self.backbone = build_backbone({"type": "ResNetFPN", "resolution": [8, 2],
                                         "resnetfpn": {"block_type": "BasicBlock", "initial_dim": config["resnetfpn"]["initial_dim"],
                                                       "block_dims": list(config["resnetfpn"]["block_dims"]), "output_layers": [3, 1]}})
-        self.loftr_coarse = _Encoder(cc)
-        self.loftr_fine = _Encoder(cf)
+        self.loftr_coarse = EncoderParams(cc["layer_names"], cc["d_model"], cc["nhead"])
+        self.loftr_fine = EncoderParams(cf["layer_names"], cf["d_model"], cf["nhead"])
         if self.sinkhorn:                              # the reference's CoarseMatching holds bin_score in the sinkhorn form only
             self.coarse_matching = nn.Module()
             self.coarse_matching.bin_score = nn.Parameter(torch.tensor(float(mc["skh_init_bin_score"]), requires_grad=True))
@@ -151,19 +131,12 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         if self._packed is None or self._packed[0] != key:
             sd = self.state_dict()
             bb = {k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")}
-            fine = []
-            for i in range(len(self.loftr_fine.layer_names)):
-                p = f"loftr_fine.layers.{i}."
-                fine.append({n: packing.pack_linear_x3(sd[p + k]).to(device) for n, k in
-                             (("q", "q_proj.weight"), ("k", "k_proj.weight"), ("v", "v_proj.weight"), ("m", "merge.weight"),
-                              ("w0", "mlp.0.weight"), ("w2", "mlp.2.weight"))})
-                fine[-1].update({n: sd[p + n.replace("_", ".")].detach().float().contiguous().to(device)
-                                 for n in ("norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")})
             self._packed = (key, {
                 "backbone": pack_backbone(bb, device),
                 "coarse": [(packing.pack_coarse_layer if self.coarse_full else packing.pack_coarse_layer_x3w8)(sd, f"loftr_coarse.layers.{i}.").to(device)
                            for i in range(len(self.loftr_coarse.layer_names))],
-                "fine": fine,
+                "fine": [{n: t.to(device) for n, t in packing.pack_fine_layer_full_x3(sd, f"loftr_fine.layers.{i}.").items()}
+                         for i in range(len(self.loftr_fine.layer_names))],
                 "bin_score": float(sd["coarse_matching.bin_score"]) if self.sinkhorn else None,
             })
         return self._packed[1]
@@ -171,8 +144,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
     def _pe_table(self, h, w, device):
         k = (h, w, str(device))
         if k not in self._pe:
-            pe = host_math.sinusoid_table(self.config["coarse"]["d_model"], h, w, (256, 256))        # the floor-division table (temp_bug_fix False)
-            self._pe[k] = pe.flatten(1).t().contiguous().to(device)
+            self._pe[k] = host_math.pe_table(self.config["coarse"]["d_model"], h, w, (256, 256)).to(device)      # the floor-division table (temp_bug_fix False)
         return self._pe[k]
 
     # ------------------------------------------------------------------------------------------
@@ -281,28 +253,53 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         V = img0.size(0)
         if img1.size(0) not in (1, V):
             raise ValueError(f"image1: batch {img1.size(0)} against image0's {V} (expected 1 -- one query for every pair -- or {V})")
-        shared1 = img1.size(0) == 1 and V > 1          # one query image against V views: its features are computed once
         hip.load()
-        call, P, S = hip.call, hip.ptr, hip.stream_handle()
-        dev = img0.device
         data.update({"bs": V, "hw0_i": img0.shape[2:], "hw1_i": img1.shape[2:]})
-        Wb = self._blocks(dev)
+        Wb = self._blocks(img0.device)
+        debug = kwargs.get("_debug")
+        fc0, fc1, ff0, ff1, fm0, fm1, hw0_c, hw1_c, hw0_f, hw1_f = self._features(Wb, data, img0, img1, debug)
+        scale = img0.shape[2] / hw0_c[0]
+        s0, s1 = (data["scale0"].contiguous(), data["scale1"].contiguous()) if has_s else (None, None)
+        x0 = x1 = None
+        if fine_only:
+            mk0c, mk1c = data["mkpts0_c"], data["mkpts1_c"]
+            b_ids, i_ids, j_ids = self._provided_matches(img0.device, mk0c, mk1c, img0.shape[2:], img1.shape[2:], hw0_c, hw1_c, scale, s0, s1)
+            data.update({"m_bids": b_ids, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "mconf": torch.ones_like(b_ids)})
+        else:
+            masks = (data["mask0"], data["mask1"]) if "mask0" in data else None
+            x0, x1, conf, b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0c, mk1c = self._coarse(Wb, fc0, fc1, hw0_c, hw1_c, scale, s0, s1, masks)
+            data.update({"conf_matrix": conf, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "m_bids": m_bids, "gt_mask": gt_mask,
+                         "mconf": mconf, "mkpts0_c": mk0c, "mkpts1_c": mk1c})
+        if self.enable_fine_matching:
+            self._fine(Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, b_ids.shape[0], hw0_c, hw0_f, hw1_c, hw1_f, img0.shape[2], s1,
+                       scaled=has_s or fine_only, debug=debug)
+        else:
+            data.update({"mkpts0_f": mk0c, "mkpts1_f": mk1c})
+        if debug and x0 is not None:
+            data["_feat_c0"], data["_feat_c1"] = x0, x1
+        if ext_c or ext_f:
+            self._extract(data, ext_c, ext_f, fm0, fm1, ff0, ff1, hw0_c, hw1_c, hw0_f, hw1_f, s0, s1)
+
+    def _features(self, Wb, data, img0, img1, debug=False):
+        """backbone (both images in one batch when their sizes agree) and the ``feature_hook`` -> coarse rows with the positional encoding
+        ``fc0, fc1``, fine maps ``ff0, ff1``, coarse maps before the encoding ``fm0, fm1``, and the grids ``hw0_c, hw1_c, hw0_f, hw1_f``;
+        writes the grids into ``data`` (``hw*_c``, ``hw*_f``) and, with ``debug``, the maps as the backbone left them, both ahead of the hook"""
+        V, dev = img0.size(0), img0.device
         bbk = HipBackbone("bf16x3")
 
         def features(img):
             H, W = img.shape[2:]
             fc, ff, fm = bbk.forward(Wb["backbone"], img, self._pe_table(H // 8, W // 8, dev), return_coarse_map=True)
             return fc, ff, fm, (H // 8, W // 8), (H // 2, W // 2)
-        if img0.shape[2:] == img1.shape[2:]:
-            fc, ff, fm, hwc, hwf = features(torch.cat([img0, img1], 0))
+        if img0.shape[2:] == img1.shape[2:]:           # (a batch-1 query against V views: its features are computed once)
+            fc, ff, fm, hw0_c, hw0_f = features(torch.cat([img0, img1], 0))
             fc0, fc1, ff0, ff1, fm0, fm1 = fc[:V], fc[V:], ff[:V], ff[V:], fm[:V], fm[V:]
-            hw0_c = hw1_c = hwc
-            hw0_f = hw1_f = hwf
+            hw1_c, hw1_f = hw0_c, hw0_f
         else:
             fc0, ff0, fm0, hw0_c, hw0_f = features(img0)
             fc1, ff1, fm1, hw1_c, hw1_f = features(img1)
         data.update({"hw0_c": torch.Size(hw0_c), "hw1_c": torch.Size(hw1_c), "hw0_f": torch.Size(hw0_f), "hw1_f": torch.Size(hw1_f)})
-        if kwargs.get("_debug"):                       # the backbone's maps before the positional encoding / the hook
+        if debug:                                      # the backbone's maps before the positional encoding / the hook
             data.update({"_bb_c0": fm0, "_bb_c1": fm1, "_bb_f0": ff0, "_bb_f1": ff1, "_enc_c0": fc0, "_enc_c1": fc1})
         if self.feature_hook is not None:
             # one pair: the fine maps without the batch axis (the hook's form since round 3); a batch: everything with it
@@ -313,83 +310,74 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             ff0, ff1 = (f0h[None] if f0h.dim() == 2 else f0h), (f1h[None] if f1h.dim() == 2 else f1h)
             if fc0.shape[0] != V or fc1.shape[0] not in (1, V) or ff0.shape[0] != V or ff1.shape[0] != fc1.shape[0]:
                 raise ValueError("feature_hook: batch sizes of the returned features do not match the call")
-            shared1 = fc1.shape[0] == 1 and V > 1
+        return fc0, fc1, ff0, ff1, fm0, fm1, hw0_c, hw1_c, hw0_f, hw1_f
+
+    def _provided_matches(self, dev, mk0c, mk1c, hw0_i, hw1_i, hw0_c, hw1_c, scale, s0, s1):
+        """the fine-only branch (loftr.py:79-115): the caller's coarse keypoints clipped IN PLACE and rounded to cells; no coarse
+        transformer, no matching -> ``b_ids`` (zeros), ``i_ids``, ``j_ids``"""
+        call, P = hip.call, hip.ptr
+        K = mk0c.shape[0]
+        b_ids = torch.zeros(K, dtype=torch.int64, device=dev)
+        i_ids, j_ids = torch.empty(K, dtype=torch.int64, device=dev), torch.empty(K, dtype=torch.int64, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        a0, a1 = mk0c.contiguous(), mk1c.contiguous()
+        call("ophip_loftr_coarse_ids", P(a0, None), int(a0.dtype == torch.float64), P(a1, None), int(a1.dtype == torch.float64), K,
+             hw0_i[0], hw0_i[1], hw1_i[0], hw1_i[1], hw0_c[0], hw0_c[1], hw1_c[0], hw1_c[1], float(scale),
+             P(s0), P(s1), P(i_ids, torch.int64), P(j_ids, torch.int64), P(bad, torch.int32), hip.stream_handle())
+        for a, t in ((a0, mk0c), (a1, mk1c)):
+            if a.data_ptr() != t.data_ptr():
+                t.copy_(a)
+        nbad = int(bad.item()) if self.enable_fine_matching else 0      # only the fine stage indexes the maps with the ids
+        if nbad:
+            raise IndexError(f"{nbad} provided coarse keypoint(s) round to a cell outside the coarse grid")
+        return b_ids, i_ids, j_ids
+
+    def _coarse(self, Wb, fc0, fc1, hw0_c, hw1_c, scale, s0, s1, masks):
+        """coarse transformer and coarse matching between the two grids; ``masks``: None or ``(mask0, mask1)`` as the caller gave them
+        -> final rows ``x0, x1``, ``conf_matrix`` and the K matches ``b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mkpts0_c, mkpts1_c``"""
+        call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        V, dev = fc0.shape[0], fc0.device
         L0, L1 = hw0_c[0] * hw0_c[1], hw1_c[0] * hw1_c[1]
-        scale = img0.shape[2] / hw0_c[0]
-        s0 = data["scale0"].contiguous() if has_s else None
-        s1 = data["scale1"].contiguous() if has_s else None
-
-        if fine_only:
-            # ---- provided coarse matches (loftr.py:79-115): clip in place, round to cells; no coarse transformer, no matching -----------
-            mk0c, mk1c = data["mkpts0_c"], data["mkpts1_c"]
-            K = mk0c.shape[0]
-            b_ids = torch.zeros(K, dtype=torch.int64, device=dev)
-            i_ids, j_ids = torch.empty(K, dtype=torch.int64, device=dev), torch.empty(K, dtype=torch.int64, device=dev)
-            bad = torch.empty(1, dtype=torch.int32, device=dev)
-            a0, a1 = mk0c.contiguous(), mk1c.contiguous()
-            call("ophip_loftr_coarse_ids", P(a0, None), int(a0.dtype == torch.float64), P(a1, None), int(a1.dtype == torch.float64), K,
-                 img0.shape[2], img0.shape[3], img1.shape[2], img1.shape[3], hw0_c[0], hw0_c[1], hw1_c[0], hw1_c[1], float(scale),
-                 P(s0), P(s1), P(i_ids, torch.int64), P(j_ids, torch.int64), P(bad, torch.int32), S)
-            for a, t in ((a0, mk0c), (a1, mk1c)):
-                if a.data_ptr() != t.data_ptr():
-                    t.copy_(a)
-            nbad = int(bad.item()) if self.enable_fine_matching else 0      # only the fine stage indexes the maps with the ids
-            if nbad:
-                raise IndexError(f"{nbad} provided coarse keypoint(s) round to a cell outside the coarse grid")
-            data.update({"m_bids": b_ids, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "mconf": torch.ones_like(b_ids)})
-            x0 = x1 = None
+        # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
+        #      full: one one-stream launch per image and layer, the shared query read with batch stride 0 -----------------------
+        if masks is not None:                          # flattened, the query's repeated for every pair (read only: never written)
+            m1 = masks[1].reshape(-1, L1)
+            masks = (masks[0].reshape(V, L0).contiguous(), (m1.expand(V, -1) if m1.shape[0] != V else m1).contiguous())
+        if self.coarse_full:
+            x0, x1 = self._coarse_full(Wb["coarse"], fc0.contiguous(), fc1.contiguous(), V, L0, L1)
         else:
-            # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
-            #      full: one one-stream launch per image and layer, the shared query read with batch stride 0 -----------------------
-            masks = None
-            if "mask0" in data:                        # flattened, the query's repeated for every pair (read only: never written)
-                m1 = data["mask1"].reshape(-1, L1)
-                masks = (data["mask0"].reshape(V, L0).contiguous(), (m1.expand(V, -1) if m1.shape[0] != V else m1).contiguous())
-            if self.coarse_full:
-                x0, x1 = self._coarse_full(Wb["coarse"], fc0.contiguous(), fc1.contiguous(), V, L0, L1)
-            else:
-                x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, shared1, V, L0, L1, masks)
+            x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, fc1.shape[0] == 1 and V > 1, V, L0, L1, masks)
 
-            # ---- coarse matching between the two grids -------------------------------------------------------------------------
-            mc = self.config["match_coarse"]
-            ii = torch.arange(L0, device=dev)
-            pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
-            cap = V * L0
-            conf = torch.empty(V, L0, L1, device=dev)
-            ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
-            cws = torch.empty(ws_floats(V, L0, L1), device=dev)
-            ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
-            mconf, mk0, mk1c = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-            gt_mask = torch.empty(cap, dtype=torch.bool, device=dev)
-            count = torch.zeros(4, dtype=torch.int32, device=dev)
-            outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
-                    P(gt_mask, torch.bool), P(count, torch.int32))
-            mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
-            sfx = "" if masks is None else "_masked"
-            if self.sinkhorn:
-                call("ophip_coarse_match_2d_sinkhorn" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"],
-                     int(mc["skh_iters"]), 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws),
-                     *outs, *mk, S)
-            else:
-                call("ophip_coarse_match_2d" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]),
-                     float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, *mk, S)
-            K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
-            b_ids, i_ids, j_ids = ids[0][:K], ids[1][:K], ids[2][:K]
-            mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
-            if has_s:                                          # get_coarse_match: cell * (scale * scale0[b_ids]); scale = 8 is a power of two
-                mk0c = mk0c * s0[b_ids]
-                mk1c = mk1c * (s1[b_ids] if s1.shape[0] > 1 else s1)
-            data.update({"conf_matrix": conf, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "m_bids": ids[3][:K], "gt_mask": gt_mask[:K],
-                         "mconf": mconf[:K], "mkpts0_c": mk0c, "mkpts1_c": mk1c})
-        if self.enable_fine_matching:
-            self._fine(Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, img0.shape[2], s1,
-                       scaled=has_s or fine_only, debug=kwargs.get("_debug"))
+        # ---- coarse matching between the two grids -------------------------------------------------------------------------
+        mc = self.config["match_coarse"]
+        ii = torch.arange(L0, device=dev)
+        pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
+        cap = V * L0
+        conf = torch.empty(V, L0, L1, device=dev)
+        ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
+        cws = torch.empty(ws_floats(V, L0, L1), device=dev)
+        ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
+        mconf, mk0, mk1c = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
+        gt_mask = torch.empty(cap, dtype=torch.bool, device=dev)
+        count = torch.zeros(4, dtype=torch.int32, device=dev)
+        outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
+                P(gt_mask, torch.bool), P(count, torch.int32))
+        mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
+        sfx = "" if masks is None else "_masked"
+        if self.sinkhorn:
+            call("ophip_coarse_match_2d_sinkhorn" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"],
+                 int(mc["skh_iters"]), 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws),
+                 *outs, *mk, S)
         else:
-            data.update({"mkpts0_f": mk0c, "mkpts1_f": mk1c})
-        if kwargs.get("_debug") and x0 is not None:
-            data["_feat_c0"], data["_feat_c1"] = x0, x1
-        if ext_c or ext_f:
-            self._extract(data, ext_c, ext_f, fm0, fm1, ff0, ff1, hw0_c, hw1_c, hw0_f, hw1_f, s0, s1)
+            call("ophip_coarse_match_2d" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]),
+                 float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, *mk, S)
+        K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
+        b_ids = ids[0][:K]
+        mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
+        if s0 is not None:                                 # get_coarse_match: cell * (scale * scale0[b_ids]); scale = 8 is a power of two
+            mk0c = mk0c * s0[b_ids]
+            mk1c = mk1c * (s1[b_ids] if s1.shape[0] > 1 else s1)
+        return x0, x1, conf, b_ids, ids[1][:K], ids[2][:K], ids[3][:K], gt_mask[:K], mconf[:K], mk0c, mk1c
 
     def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug):
         """fine stage (windows on both images, two-stream fine transformer, correlation + soft-argmax) on the matches' cells"""
@@ -408,25 +396,11 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         call("ophip_fine2_gather_b", P(ff1c), ff1c.stride(0) if ff1c.shape[0] > 1 else 0, P(b_ids, torch.int64), hw1_f[0], hw1_f[1],
              P(j_ids, torch.int64), K, hw1_c[1], hw1_f[0] // hw1_c[0], Wf, P(f1), S)
         T = K * WW
-
-        def lin(xa, w, nout, xb=None, relu=False):
-            y = torch.empty(T, nout, device=dev)
-            call("ophip_rows_linear_x3", P(xa), xa.shape[-1], P(xb), xb.shape[-1] if xb is not None else 0, T, P(w, None), nout, 1 if relu else 0, P(y), S)
-            return y
+        attn = "ophip_fine2_full_attention" if self.fine_full else "ophip_fine2_attention"
 
         def fine_layer(x, src, w):
-            q, k, v = lin(x, w["q"], 128), lin(src, w["k"], 128), lin(src, w["v"], 128)
-            msg = torch.empty(T, 128, device=dev)
-            call("ophip_fine2_full_attention" if self.fine_full else "ophip_fine2_attention", P(q), P(k), P(v), K, WW, WW, P(msg), S)
-            m = lin(msg, w["m"], 128)
-            call("ophip_rows_layernorm128", P(m), P(w["norm1_weight"]), P(w["norm1_bias"]), None, T, P(m), S)
-            h = lin(x.view(T, 128), w["w0"], 256, xb=m, relu=True)
-            o = lin(h, w["w2"], 128)
-            y = torch.empty(K, WW, 128, device=dev)
-            call("ophip_rows_layernorm128", P(o), P(w["norm2_weight"]), P(w["norm2_bias"]), P(x), T, P(y), S)
-            return y
-        for li, name in enumerate(self.loftr_fine.layer_names):
-            w = Wb["fine"][li]
+            return rows_encoder_layer(x, T, src, T, w, lambda q, k, v, msg: call(attn, P(q), P(k), P(v), K, WW, WW, P(msg), S))
+        for w, name in zip(Wb["fine"], self.loftr_fine.layer_names):
             if name == "self":
                 f0, f1 = fine_layer(f0, f0, w), fine_layer(f1, f1, w)
             else:
@@ -481,8 +455,4 @@ def build_2D_match_model(args: dict) -> LoFTR_for_OnePose_Plus:
         raise NotImplementedError
     matcher = LoFTR_for_OnePose_Plus(config=copy.deepcopy(default_cfg))
     state_dict = torch.load(args["weight_path"], map_location="cpu", weights_only=True)["state_dict"]
-    for k in list(state_dict.keys()):
-        state_dict[k.replace("matcher.", "")] = state_dict.pop(k)
-    matcher.load_state_dict(state_dict, strict=True)
-    matcher.eval()
-    return matcher
+    return load_matcher_checkpoint(matcher, state_dict)

@@ -22,9 +22,9 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import math
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -33,33 +33,9 @@ from . import hip, host_math, ops, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .config import encoder_layer_names, validate_config
-
-
-class _LayerParams(nn.Module):
-    """Parameter holder with the key layout of ``LoFTREncoderLayer`` (transformer.py:29-52)."""
-
-    def __init__(self, d):
-        super().__init__()
-        self.q_proj = nn.Linear(d, d, bias=False)
-        self.k_proj = nn.Linear(d, d, bias=False)
-        self.v_proj = nn.Linear(d, d, bias=False)
-        self.merge = nn.Linear(d, d, bias=False)
-        self.mlp = nn.Sequential(nn.Linear(2 * d, 2 * d, bias=False), nn.Identity(), nn.Linear(2 * d, d, bias=False))
-        self.norm1 = nn.LayerNorm(d)
-        self.norm2 = nn.LayerNorm(d)
-
-
-class _EncoderParams(nn.Module):
-    """``LocalFeatureTransformer`` parameter holder (transformer.py:100-131)."""
-
-    def __init__(self, enc_cfg):
-        super().__init__()
-        self.layer_names = encoder_layer_names(enc_cfg)
-        self.d_model, self.nhead = enc_cfg["d_model"], enc_cfg["nhead"]
-        self.layers = nn.ModuleList([_LayerParams(self.d_model) for _ in self.layer_names])
-        for p in self.parameters():
-            if p.dim() > 1:
-                nn.init.xavier_uniform_(p)
+from .hip import bstride
+from .params import EncoderParams, load_matcher_checkpoint
+from .rows import rows_encoder_layer
 
 
 class _KeypointEncoderParams(nn.Module):
@@ -97,6 +73,37 @@ def _current_stream(dev):
     return st
 
 
+_NSPLIT = {"f32": 0, "bf16": 1, "bf16x3": 3}          # hip_precision -> the operand split the matching and fine kernels take
+
+
+def _side_stream(table, key, dev, priority=0, with_event=False):
+    """The side stream ``table`` keeps for ``key``, created on first use.  The tables are keyed on the raw handle of a compute stream, so
+    each holds 16 entries at most and drops its oldest instead of growing for ever.  ``with_event``: the entry is ``[stream, last event]``
+    (the fine streams) and is returned whole."""
+    ent = table.get(key)
+    if ent is None:
+        if len(table) >= 16:
+            table.pop(next(iter(table)))
+        st = torch.cuda.Stream(device=dev, priority=priority)
+        ent = table[key] = [st, None] if with_event else st
+    return ent
+
+
+def _dense(t):
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _per_frame(t):        # [B or 1, ...] dense per frame, without materialising an expand()
+    if t.stride(0) == 0 and t.shape[0] > 1:
+        t = t[:1]
+    return _dense(t)
+
+
+# one ``enqueue_features`` call's checked inputs: sizes, device, the object block dense per frame (batch 1 when the frames share it), the
+# query images' optional padding mask [B, M] uint8 and scale [B, 2], the packed weights
+FrameInputs = namedtuple("FrameInputs", "B N M hc wc hf wf dev kpts_d desc_in_d desc_fine_d qmask qscale W")
+
+
 class _NullProfiler:
     _scope = contextlib.nullcontext()
 
@@ -124,8 +131,8 @@ class OnePosePlus_model(nn.Module):
             if ke["descriptor_dim"] != 256 or list(ke["keypoints_encoder"]) != [32, 64, 128]:
                 raise NotImplementedError("HIP keypoint encoder is specialised for 3->32->64->128->256")
             self.kpt_3d_pos_encoding = _KeypointEncoderParams(3, ke["descriptor_dim"], ke["keypoints_encoder"])
-        self.loftr_coarse = _EncoderParams(cc)
-        self.loftr_fine = _EncoderParams(cf)
+        self.loftr_coarse = EncoderParams(encoder_layer_names(cc), cc["d_model"], cc["nhead"])
+        self.loftr_fine = EncoderParams(encoder_layer_names(cf), cf["d_model"], cf["nhead"])
         self._pe_enable = bool(config["positional_encoding"]["enable"])
         self._pe_shape = tuple(config["positional_encoding"]["pos_emb_shape"])
         # matrix arithmetic of the HIP kernels:
@@ -260,25 +267,22 @@ class OnePosePlus_model(nn.Module):
         params = self._matcher_params()
         key = (str(device), self.precision, tuple([p.data_ptr() for p in params]), tuple([p._version for p in params]))
         sd = {k: v for k, v in self.state_dict().items() if not k.startswith("backbone.")}
-        blocks = {
-            "coarse": [packing.pack_coarse_layer(sd, f"loftr_coarse.layers.{i}.").to(device)
-                       for i in range(len(self.loftr_coarse.layer_names))],
-            "fine": torch.cat([packing.pack_fine_layer(sd, f"loftr_fine.layers.{i}.")
-                               for i in range(len(self.loftr_fine.layer_names))]).to(device),
-        }
+        n_fine = len(self.loftr_fine.layer_names)
+
+        def coarse(pack):
+            return [pack(sd, f"loftr_coarse.layers.{i}.").to(device) for i in range(len(self.loftr_coarse.layer_names))]
+        blocks = {"coarse": coarse(packing.pack_coarse_layer),
+                  "fine": torch.cat([packing.pack_fine_layer(sd, f"loftr_fine.layers.{i}.") for i in range(n_fine)]).to(device)}
         if self.kpt_3d_pos_encoding is not None:
             blocks["kpt"] = packing.pack_keypoint_encoder(sd).to(device)
         if self.precision == "bf16":
-            blocks["coarse_bf16"] = [packing.pack_coarse_layer_bf16(sd, f"loftr_coarse.layers.{i}.").to(device)
-                                     for i in range(len(self.loftr_coarse.layer_names))]
+            blocks["coarse_bf16"] = coarse(packing.pack_coarse_layer_bf16)
         if self.precision == "bf16x3":
-            blocks["coarse_x3"] = [packing.pack_coarse_layer_x3w8(sd, f"loftr_coarse.layers.{i}.").to(device)
-                                   for i in range(len(self.loftr_coarse.layer_names))]
+            blocks["coarse_x3"] = coarse(packing.pack_coarse_layer_x3w8)
         if self.fine_full:
-            blocks["fine_full"] = [{n: t.to(device) for n, t in packing.pack_fine_layer_full_x3(sd, f"loftr_fine.layers.{i}.").items()}
-                                   for i in range(len(self.loftr_fine.layer_names))]
+            blocks["fine_full"] = [{n: t.to(device) for n, t in packing.pack_fine_layer_full_x3(sd, f"loftr_fine.layers.{i}.").items()} for i in range(n_fine)]
         if self.precision != "f32":
-            blocks["fine_bf16"] = packing.pack_fine_layers_bf16(sd, "loftr_fine.layers.", len(self.loftr_fine.layer_names)).to(device)
+            blocks["fine_bf16"] = packing.pack_fine_layers_bf16(sd, "loftr_fine.layers.", n_fine).to(device)
         self._packed = (key, blocks)
         return blocks
 
@@ -292,9 +296,7 @@ class OnePosePlus_model(nn.Module):
     def _pe_table(self, h, w, device):
         k = (h, w, str(device))
         if k not in self._pe_cache:
-            C = self.config["loftr_coarse"]["d_model"]
-            pe = host_math.sinusoid_table(C, h, w, self._pe_shape)              # [C, h, w]
-            self._pe_cache[k] = pe.flatten(1).t().contiguous().to(device)        # [M, C]
+            self._pe_cache[k] = host_math.pe_table(self.config["loftr_coarse"]["d_model"], h, w, self._pe_shape).to(device)        # [M, C]
         return self._pe_cache[k]
 
     # ------------------------------------------------------------------------------------------
@@ -348,6 +350,32 @@ class OnePosePlus_model(nn.Module):
         ``finish()`` exposes as numpy arrays (``pending.host``) for host PnP.  ``inputs_ready=True``: the caller guarantees that
         ``feat_c``, ``feat_f`` and the object block are complete in device memory (nothing that writes them is still queued), so
         the input kernels may run on a side stream ahead of the work already queued on the current one."""
+        fi = self._frame_inputs(data, feat_c, feat_f, image_hw)
+        main = _current_stream(fi.dev)
+        fkey = (str(fi.dev), main.cuda_stream)
+        lazy = self.conf_matrix_mode == "lazy" and not _force_eager
+        # a lazy frame whose selection meets an exact row tie it cannot resolve without the stored row is run again with conf_matrix
+        rerun = (lambda: self.enqueue_features(data, feat_c, feat_f, image_hw, want_fine_debug, host_copy, _pe_applied, False, True)) if lazy else None
+        if (self.frame_call and self.precision == "bf16x3" and not self.coarse_full and not self.fine_full and self.overlap_fine and not _pe_applied and not want_fine_debug
+                and not self.debug and bool(self.config["fine_matching"]["enable"])
+                and (self.kpt_3d_pos_encoding is not None or fi.B == 1 or fi.desc_in_d.shape[0] == fi.B)
+                and len(self.loftr_coarse.layer_names) <= 16):
+            return self._enqueue_frame_call(data, feat_c, feat_f, fi, main, fkey, host_copy, inputs_ready, lazy, rerun)
+        # the same frame stage by stage, every launch issued from Python
+        if fkey in self._frame_call_pending:                          # order this frame's encoder behind the C path's last fine stage
+            self._frame_call_pending.discard(fkey)
+            hip.call("ophip_frame_order_after_fine", ctypes.c_void_p(main.cuda_stream))
+        x2d, x3d, ff, ff_strides = self._input_stage(fi, feat_c, feat_f, main, fkey, _pe_applied, inputs_ready)      # a1, fine map, a2 + a3
+        x3d, x2d = self._coarse_encoder_stage(fi, x3d, x2d, main, fkey)                                              # a4-a6
+        if self.debug:
+            data["_feat3d_c"], data["_feat2d_c"] = x3d, x2d
+        cb, select = self._coarse_matching_stage(data, fi, x3d, x2d, main, lazy)                                     # a7 + a8
+        pend = self._fine_stage(data, fi, cb, select, ff, ff_strides, main, fkey, want_fine_debug, host_copy)      # a9-a11
+        pend._rerun = rerun
+        return pend
+
+    def _frame_inputs(self, data, feat_c, feat_f, image_hw):
+        """Check one call's inputs and gather them as a :class:`FrameInputs`; fills the ``bs`` / ``q_hw_*`` keys of ``data``."""
         if not feat_c.is_cuda:
             raise hip.HipLibraryError("OnePosePlus_model runs on the HIP device only (no CPU fallback): move the "
                                       "model and its inputs to 'cuda'")
@@ -359,12 +387,10 @@ class OnePosePlus_model(nn.Module):
                                 "(the reference's FullAttention indexes the None q_mask of the 3D stream's cross layer, linear_attention.py:85)")
             raise NotImplementedError("query_image_mask with loftr_coarse.attention = 'full'")
         hip.load()
-        lib_call, P = hip.call, hip.ptr
-        cfg = self.config
         dev = feat_c.device
         if image_hw is not None:
             data.update({"bs": feat_c.size(0), "q_hw_i": torch.Size(image_hw)})
-        B, C, hc, wc = feat_c.shape
+        B, _, hc, wc = feat_c.shape
         hf, wf = feat_f.shape[2:]
         M = hc * wc
         data.update({"q_hw_c": feat_c.shape[2:], "q_hw_f": feat_f.shape[2:]})
@@ -373,20 +399,7 @@ class OnePosePlus_model(nn.Module):
         desc_fine = data["descriptors3d_db"]
         desc_in = data["descriptors3d_coarse_db"] if "descriptors3d_coarse_db" in data else desc_fine
         N = kpts.shape[1]
-        f32 = dict(device=dev, dtype=torch.float32)
-
-        def dense(t):
-            return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-        def bstride(t):          # batch stride in elements; expanded (shared) object blocks give 0
-            return 0 if t.shape[0] == 1 or t.stride(0) == 0 else t.stride(0)
-
-        def per_frame(t):        # [B or 1, ...] dense per frame, without materialising an expand()
-            if t.stride(0) == 0 and t.shape[0] > 1:
-                t = t[:1]
-            return dense(t)
-
-        kpts_d, desc_in_d, desc_fine_d = per_frame(kpts), per_frame(desc_in), per_frame(desc_fine)
+        kpts_d, desc_in_d, desc_fine_d = _per_frame(kpts), _per_frame(desc_in), _per_frame(desc_fine)
         for t, name in ((kpts_d, "keypoints3d"), (desc_in_d, "descriptors3d"), (desc_fine_d, "descriptors3d_db")):
             if t.shape[0] not in (1, B):
                 raise ValueError(f"{name}: batch {t.shape[0]} does not match the query batch {B}")
@@ -403,46 +416,20 @@ class OnePosePlus_model(nn.Module):
             if tuple(qs.shape) != (B, 2):
                 raise ValueError(f"query_image_scale: expected shape {(B, 2)} ((h, w) factors per image), got {tuple(qs.shape)}")
             qscale = qs.to(device=dev, dtype=torch.float32).contiguous()
-        PM = lambda: P(qmask, torch.uint8)
+        return FrameInputs(B, N, M, hc, wc, hf, wf, dev, kpts_d, desc_in_d, desc_fine_d, qmask, qscale, W)
 
-        main = _current_stream(dev)
-        S = ctypes.c_void_p(main.cuda_stream)          # (the stage-by-stage path below launches on it)
-        fkey = (str(dev), main.cuda_stream)
-        lazy = self.conf_matrix_mode == "lazy" and not _force_eager
-        # a lazy frame whose selection meets an exact row tie it cannot resolve without the stored row is run again with conf_matrix
-        rerun = (lambda: self.enqueue_features(data, feat_c, feat_f, image_hw, want_fine_debug, host_copy, _pe_applied, False, True)) if lazy else None
-        if (self.frame_call and self.precision == "bf16x3" and not self.coarse_full and not self.fine_full and self.overlap_fine and not _pe_applied and not want_fine_debug
-                and not self.debug and bool(cfg["fine_matching"]["enable"])
-                and (self.kpt_3d_pos_encoding is not None or B == 1 or desc_in_d.shape[0] == B)
-                and len(self.loftr_coarse.layer_names) <= 16):
-            x3d_ext = None
-            shared_batch = B > 1 and kpts_d.shape[0] == 1 and desc_in_d.shape[0] == 1
-            if self.cache_object or shared_batch:
-                # the reference keeps the object block resident across frames (OnePosePlus_inference_dataset.py:157-169): what depends on it
-                # and the weights alone is computed once per (object tensors, weights) and handed to the frame call -- the keypoint encoding
-                # (rows a2 + a3) and, with a first layer of kind "self", that layer's 3D rows and the K^T V | Ksum block of those rows as the
-                # second layer's source (transformer.py:148-159; ophip_encoder_object_x3w8: the frame's own launches on the 3D stream's
-                # workgroups, so a cached frame is bit-identical).  One entry serves the whole batch when it shares one object (config 3).
-                # A batch whose frames share ONE object block (stride-0 expand: BASELINE config 3) takes the same route WITHOUT the cache flag:
-                # the object-only work is then done once per CALL instead of once per frame of the batch -- nothing is kept for the next call
-                # (`keep=False`), so a forward still does all of its own work.
-                x3d_ext = self._object_cache_entry(kpts_d, desc_in_d, W, dev, B, N, main, masked=qmask is not None, keep=self.cache_object)
-            return self._enqueue_frame_call(data, feat_c, feat_f, kpts_d, desc_in_d, desc_fine_d, x3d_ext, W, dev, main, fkey,
-                                            B, N, M, hc, wc, hf, wf, host_copy, inputs_ready, lazy, rerun, qmask, qscale)
-        if fkey in self._frame_call_pending:                          # order this frame's encoder behind the C path's last fine stage
-            self._frame_call_pending.discard(fkey)
-            lib_call("ophip_frame_order_after_fine", ctypes.c_void_p(main.cuda_stream))
-        # The input kernels (a1-a3 + the fine map's transpose) depend on nothing but the caller's tensors.  With ``inputs_ready`` the
-        # caller states that those tensors are complete (no producer still queued on this stream): the kernels then go to a side
-        # stream and start at once -- on the CUs the 246-workgroup encoder of the previous frame leaves idle and beside its coarse
-        # stage -- instead of behind everything queued before; the encoder waits for their event.
+    def _input_stage(self, fi, feat_c, feat_f, main, fkey, _pe_applied, inputs_ready):
+        """Rows a1-a3 and the fine map's transpose -> ``(x2d [B, M, C], x3d [B, N, C], ff, ff_strides)`` (``ff`` None with the fine stage off).
+        They depend on nothing but the caller's tensors.  With ``inputs_ready`` the caller states that those are complete (no producer still
+        queued on this stream): the kernels then go to a side stream and start at once -- on the CUs the 246-workgroup encoder of the previous
+        frame leaves idle and beside its coarse stage -- instead of behind everything queued before; the compute stream waits for their event."""
+        lib_call, P = hip.call, hip.ptr
+        B, N, M, hf, wf, dev = fi.B, fi.N, fi.M, fi.hf, fi.wf, fi.dev
+        C = feat_c.shape[1]
+        f32 = dict(device=dev, dtype=torch.float32)
         prep_ctx, sprep = contextlib.nullcontext(), None
         if inputs_ready and self.overlap_fine and not _pe_applied:
-            if fkey not in self._prep_streams:
-                if len(self._prep_streams) >= 16:
-                    self._prep_streams.pop(next(iter(self._prep_streams)))
-                self._prep_streams[fkey] = torch.cuda.Stream(device=dev)
-            sprep = self._prep_streams[fkey]
+            sprep = _side_stream(self._prep_streams, fkey, dev)
             prep_ctx = torch.cuda.stream(sprep)
         with prep_ctx:
             S_in = hip.stream_handle()
@@ -453,12 +440,12 @@ class OnePosePlus_model(nn.Module):
                     raise ValueError("internal: the HIP backbone's coarse map must be dense channels-last")
             else:
                 x2d = torch.empty(B, M, C, **f32)
-                pe = self._pe_table(hc, wc, dev) if self._pe_enable else None
-                lib_call("ophip_pe_add_transpose", P(dense(feat_c)), P(pe), P(x2d), B, C, M, S_in)
+                pe = self._pe_table(fi.hc, fi.wc, dev) if self._pe_enable else None
+                lib_call("ophip_pe_add_transpose", P(_dense(feat_c)), P(pe), P(x2d), B, C, M, S_in)
             # ---- fine map to channels-last (input kernel of the fine stage; here so that it runs under the previous frame's
             #      fine stage instead of in front of this frame's) ------------------------------------------------------
             ff = ff_strides = None
-            if bool(cfg["fine_matching"]["enable"]):
+            if bool(self.config["fine_matching"]["enable"]):
                 ff = feat_f if feat_f.dtype == torch.float32 else feat_f.float()
                 if ff.stride(1) == 1:                      # channels-last memory already: strides as they are
                     ff_strides = (ff.stride(0), 1, ff.stride(2), ff.stride(3))
@@ -468,23 +455,14 @@ class OnePosePlus_model(nn.Module):
                     lib_call("ophip_transpose_cl", P(ff), P(ff_cl), B, ff.shape[1], hf * wf, S_in)
                     ff, ff_strides = ff_cl, (hf * wf * ff_cl.shape[2], 1, wf * ff_cl.shape[2], ff_cl.shape[2])
             # ---- a2 + a3: keypoint encoding (frame-invariant: depends on the object block only) -------------------
-            x3d = None
-            ckey = None
             if self.cache_object:
                 # the reference keeps the object block resident across frames (OnePosePlus_inference_dataset.py:157-169); its encoding
                 # is recomputed only when the tensors (or the weights) change
-                ent = self._object_cache_entry(kpts_d, desc_in_d, W, dev, B, N, torch.cuda.current_stream(dev))
+                ent = self._object_cache_entry(fi, torch.cuda.current_stream(dev))
                 torch.cuda.current_stream(dev).wait_event(ent["ev"])
                 x3d = ent["x3d"] if ent["x3d"].shape[0] == B else ent["x3d"].expand(B, -1, -1).contiguous()
-            if x3d is None:
-                x3d = torch.empty(B, N, C, **f32)
-                if self.kpt_3d_pos_encoding is not None:
-                    stats = torch.empty(4 * B + 4, **f32)
-                    lib_call("ophip_kpt_encode", P(kpts_d), bstride(kpts_d), P(desc_in_d), bstride(desc_in_d), P(W["kpt"]),
-                             P(stats), P(x3d), B, N, S_in)
-                else:
-                    src = desc_in_d if desc_in_d.shape[0] == B else desc_in_d.expand(B, -1, -1).contiguous()
-                    lib_call("ophip_transpose_cl", P(src), P(x3d), B, C, N, S_in)
+            else:
+                x3d = self._encode_keypoints(fi, B)
             if sprep is not None:
                 prep_done = torch.cuda.Event()
                 prep_done.record()
@@ -493,206 +471,206 @@ class OnePosePlus_model(nn.Module):
             for t in (x2d, x3d, ff):                     # allocated from s_prep's pool, used on the compute / fine streams from here on
                 if t is not None:
                     t.record_stream(main)
-        # ---- a4-a6: coarse encoder ----------------------------------------------------------------
-        y3d, y2d = torch.empty_like(x3d), torch.empty_like(x2d)
-        z3d = torch.empty_like(x3d) if self.cache_object else x3d          # a cached encoding is read-only: ping-pong between y and z
+        return x2d, x3d, ff, ff_strides
 
-        def wait_previous_fine():                                 # the previous frame's fine stage is done
-            if self.overlap_fine and fkey in self._fine_streams and self._fine_streams[fkey][1] is not None:
-                main.wait_event(self._fine_streams[fkey][1])
-        if self.precision == "f32":
-            wait_previous_fine()
-            ws = torch.empty(hip.load().ophip_encoder_workspace_floats(B, N, M), **f32)
-            for li, name in enumerate(self.loftr_coarse.layer_names):
-                if qmask is None:
-                    lib_call("ophip_encoder_layer", P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]),
-                             1 if name == "cross" else 0, P(ws), S)
-                else:
-                    lib_call("ophip_encoder_layer_masked", P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]),
-                             1 if name == "cross" else 0, P(ws), PM(), S)
-                x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
-        elif self.coarse_full:
-            # full (softmax) attention: projections, split-bf16 flash attention, tail (csrc/encoder_full.hip)
-            ws = torch.empty(hip.load().ophip_encoder_full_workspace_bytes(B, N, M), device=dev, dtype=torch.uint8)
-            for li, name in enumerate(self.loftr_coarse.layer_names):
-                if li == 0:
-                    wait_previous_fine()
-                lib_call("ophip_encoder_layer_full_x3", P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]),
-                         1 if name == "cross" else 0, P(ws, None), S)
-                x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
-        elif self.precision == "bf16x3":
-            # 16-token tiles, one eight-wave workgroup per CU, per-wave weight streams (csrc/encoder_x3w8.hip)
-            entry = "ophip_encoder_layer_x3w8"
-            ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, N, M), device=dev, dtype=torch.uint8)
-            names_c = self.loftr_coarse.layer_names
-            for li, name in enumerate(names_c):
-                nxt = W["coarse_x3"][li + 1] if li + 1 < len(names_c) else None
-                if li == 0:
-                    wait_previous_fine()
-                lib_call(entry + ("_masked" if qmask is not None else ""), P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse_x3"][li], None), P(nxt, None),
-                         1 if name == "cross" else 0, 1 if li > 0 else 0, li & 1, P(ws, None), *((PM(),) if qmask is not None else ()), S)
-                x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
+    def _encode_keypoints(self, fi, Bo):
+        """Rows a2 + a3 on the current stream: the object block's keypoint encoding ``[Bo, N, 256]``; ``Bo`` = 1 for one object shared by
+        the batch, else B."""
+        lib_call, P, kpts_d, desc_in_d = hip.call, hip.ptr, fi.kpts_d, fi.desc_in_d
+        x3d = torch.empty(Bo, fi.N, 256, device=fi.dev, dtype=torch.float32)
+        if self.kpt_3d_pos_encoding is not None:
+            stats = torch.empty(4 * Bo + 4, device=fi.dev, dtype=torch.float32)
+            lib_call("ophip_kpt_encode", P(kpts_d), bstride(kpts_d), P(desc_in_d), bstride(desc_in_d), P(fi.W["kpt"]),
+                     P(stats), P(x3d), Bo, fi.N, hip.stream_handle())
         else:
-            nsplit = 1                                            # plain-bf16 mode
-            ws = torch.empty(hip.load().ophip_encoder_bf16_workspace_bytes(B, N, M), device=dev, dtype=torch.uint8)
-            names_c = self.loftr_coarse.layer_names
-            for li, name in enumerate(names_c):
-                # layer li's attn_apply also emits layer li+1's K/V partial slabs from the on-chip output tile
-                nxt = W["coarse_bf16"][li + 1] if li + 1 < len(names_c) else None
-                if li == 0:
-                    wait_previous_fine()                          # attn_apply, the roofline kernel, never shares the chip with fine
-                lib_call("ophip_encoder_layer_bf16" + ("_masked" if qmask is not None else ""), P(x3d), P(x2d), P(y3d), P(y2d), B, N, M,
-                         P(W["coarse_bf16"][li], None), P(nxt, None),
-                         nsplit, 1 if name == "cross" else 0, 1 if li > 0 else 0, li & 1, P(ws, None), *((PM(),) if qmask is not None else ()), S)
-                x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
-        if self.debug:
-            data["_feat3d_c"], data["_feat2d_c"] = x3d, x2d
-        # ---- a7 + a8: coarse matching -----------------------------------------------------------
-        cm = cfg["coarse_matching"]
+            src = desc_in_d if desc_in_d.shape[0] == Bo else desc_in_d.expand(Bo, -1, -1).contiguous()
+            lib_call("ophip_transpose_cl", P(src), P(x3d), Bo, 256, fi.N, hip.stream_handle())
+        return x3d
+
+    def _coarse_layer_launch(self, fi, S):
+        """The coarse encoder layer in this model's arithmetic mode: ``launch(li, name, x3d, x2d, y3d, y2d)`` runs layer ``li`` (``name``
+        "self" or "cross") from the x rows into the y rows on stream ``S``.  A mode is its workspace, entry point and argument tuple."""
+        lib, lib_call, P = hip.load(), hip.call, hip.ptr
+        B, N, M, W = fi.B, fi.N, fi.M, fi.W
+        names = self.loftr_coarse.layer_names
+        sfx, pm = ("", ()) if fi.qmask is None else ("_masked", (P(fi.qmask, torch.uint8),))
+        u8 = dict(device=fi.dev, dtype=torch.uint8)
+        if self.precision == "f32" or self.coarse_full:
+            # exact f32 (csrc/encoder.hip), or full (softmax) attention: projections, split-bf16 flash attention, tail
+            # (csrc/encoder_full.hip; its entry point takes no mask); both read the f32 layer block
+            if self.precision == "f32":
+                entry, ws, mask = "ophip_encoder_layer" + sfx, torch.empty(lib.ophip_encoder_workspace_floats(B, N, M), device=fi.dev, dtype=torch.float32), pm
+            else:
+                entry, ws, mask = "ophip_encoder_layer_full_x3", torch.empty(lib.ophip_encoder_full_workspace_bytes(B, N, M), **u8), ()
+
+            def launch(li, name, x3d, x2d, y3d, y2d):
+                lib_call(entry, P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]), 1 if name == "cross" else 0, P(ws, None), *mask, S)
+        else:
+            # "bf16x3": 16-token tiles, one eight-wave workgroup per CU, per-wave weight streams (csrc/encoder_x3w8.hip); "bf16": the plain-bf16
+            # kernel with nsplit 1.  Layer li's attn_apply also emits layer li+1's K/V partial slabs from the on-chip output tile.
+            if self.precision == "bf16x3":
+                entry, Wl, nsplit, ws = "ophip_encoder_layer_x3w8", W["coarse_x3"], (), torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(B, N, M), **u8)
+            else:
+                entry, Wl, nsplit, ws = "ophip_encoder_layer_bf16", W["coarse_bf16"], (1,), torch.empty(lib.ophip_encoder_bf16_workspace_bytes(B, N, M), **u8)
+
+            def launch(li, name, x3d, x2d, y3d, y2d):
+                nxt = Wl[li + 1] if li + 1 < len(names) else None
+                lib_call(entry + sfx, P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(Wl[li], None), P(nxt, None), *nsplit,
+                         1 if name == "cross" else 0, 1 if li > 0 else 0, li & 1, P(ws, None), *pm, S)
+        return launch
+
+    def _coarse_encoder_stage(self, fi, x3d, x2d, main, fkey):
+        """Rows a4-a6 on the compute stream: the coarse encoder's layers over the 3D rows ``x3d`` and the 2D rows ``x2d``; returns the
+        final ``(x3d, x2d)``.  It starts once the previous frame's fine stage is done: the two MFMA-heavy stages (attn_apply is the
+        roofline kernel) never share the chip."""
+        names = self.loftr_coarse.layer_names
+        y3d, y2d = torch.empty_like(x3d), torch.empty_like(x2d)
+        z3d = torch.empty_like(x3d) if self.cache_object else x3d
+        prev = self._fine_streams.get(fkey)
+        if (names or self.precision == "f32") and self.overlap_fine and prev is not None and prev[1] is not None:
+            main.wait_event(prev[1])          # (the exact-f32 mode waits with no layer to run as well)
+        launch = self._coarse_layer_launch(fi, ctypes.c_void_p(main.cuda_stream))
+        for li, name in enumerate(names):
+            launch(li, name, x3d, x2d, y3d, y2d)
+            # Ping-pong: the layer's outputs become the next layer's inputs, its inputs the next outputs.  The one invariant of this
+            # function: a cached ``x3d`` (``hip_cache_object``: the object's entry, shared with later frames) is never an output buffer --
+            # after layer 0 the 3D stream alternates between ``y3d`` and ``z3d``, which is a buffer of this frame's own when the encoding
+            # is cached and the frame's own ``x3d`` otherwise.
+            x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
+        return x3d, x2d
+
+    def _coarse_matching_stage(self, data, fi, x3d, x2d, main, lazy):
+        """Rows a7 + a8 on the compute stream; sets ``data["conf_matrix"]``.  Returns the stage's buffers (read-only from here on; ``held``: what
+        must stay referenced until ``finish()``) and ``select``: with the fine stage on its side stream the single-workgroup select kernel goes there with it (it only feeds that stage
+        and the read-back: the next frame's input kernels then run beside it, not behind it) -- ``select(stream)`` launches it; else None."""
+        lib_call, P = hip.call, hip.ptr
+        B, N, M, dev, kpts_d, qmask, qscale = fi.B, fi.N, fi.M, fi.dev, fi.kpts_d, fi.qmask, fi.qscale
+        S = ctypes.c_void_p(main.cuda_stream)
+        f32, i64 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int64)
+        cm = self.config["coarse_matching"]
         cap = B * N
         conf = None if lazy else torch.empty(B, N, M, **f32)
         cws = torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), **f32)
-        i64 = dict(device=dev, dtype=torch.int64)
         # what the host reads back (count, b_ids, 3D points, refined 2D points) lives in one block: one D2H copy per frame
-        blob, count, b_ids, mk3d, mk2d = _result_block(dev, cap)
+        blob, count, b_ids, mk3d, mk2d = _result_views(torch.empty(16 + 28 * cap, dtype=torch.uint8, device=dev), cap)
         i_ids, j_ids, m_bids = torch.empty(cap, **i64), torch.empty(cap, **i64), torch.empty(cap, **i64)
         gt_mask = torch.empty(cap, device=dev, dtype=torch.bool)
-        fine_on = bool(cfg["fine_matching"]["enable"])
+        fine_on = bool(self.config["fine_matching"]["enable"])
         mconf = torch.empty(cap, **f32)
         mkc = torch.empty(cap, 2, **f32) if fine_on else mk2d
-        scale = data["q_hw_i"][0] / hc
-        cm_args = (P(x3d), P(x2d), P(kpts_d), bstride(kpts_d), B, N, M, wc,
-                   float(cm["dual_softmax"]["temperature"]), float(cm["thr"]), int(cm["border_rm"]), float(scale),
+        scale = data["q_hw_i"][0] / fi.hc
+        temperature = float(cm["dual_softmax"]["temperature"])
+        cm_args = (P(x3d), P(x2d), P(kpts_d), bstride(kpts_d), B, N, M, fi.wc,
+                   temperature, float(cm["thr"]), int(cm["border_rm"]), float(scale),
                    P(conf), P(cws), P(b_ids, torch.int64), P(i_ids, torch.int64), P(j_ids, torch.int64),
                    P(mconf), P(mk3d), P(mkc), P(m_bids, torch.int64), P(gt_mask, torch.bool), P(count, torch.int32),
-                   {"f32": 0, "bf16": 1, "bf16x3": 3}[self.precision])
-        # the single-workgroup select kernel goes with the fine stage onto the side stream (it only feeds that stage and the
-        # read-back): the next frame's input kernels then run beside it instead of behind it
+                   _NSPLIT[self.precision])
         split_select = fine_on and self.overlap_fine
         padded = qmask is not None or qscale is not None
+        pad_args = (P(qmask, torch.uint8), P(qscale))
+        select = None
         with self.profiler.record_function("LoFTR/coarse-matching/get_coarse_match"):
             if padded:
-                lib_call("ophip_coarse_match_masked", *cm_args, 1 if split_select else 3, PM() if qmask is not None else None, P(qscale), S)
+                lib_call("ophip_coarse_match_masked", *cm_args, 1 if split_select else 3, *pad_args, S)
+                if split_select:
+                    select = lambda stream: lib_call("ophip_coarse_match_masked", *cm_args, 2, *pad_args, stream)
+            elif split_select:
+                lib_call("ophip_coarse_match_conf", *cm_args, S)
+                select = lambda stream: lib_call("ophip_coarse_match_select", *cm_args, stream)
             else:
-                lib_call("ophip_coarse_match_conf" if split_select else "ophip_coarse_match", *cm_args, S)
-        data["conf_matrix"] = conf if not lazy else LazyConfMatrix(x3d, x2d, float(cm["dual_softmax"]["temperature"]),
-                                                                     {"f32": 0, "bf16": 1, "bf16x3": 3}[self.precision], main, qmask)
+                lib_call("ophip_coarse_match", *cm_args, S)
+        data["conf_matrix"] = conf if not lazy else LazyConfMatrix(x3d, x2d, temperature, _NSPLIT[self.precision], main, qmask)
+        return dict(blob=blob, b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, mconf=mconf, mk3d=mk3d, mk2d=mk2d, mkc=mkc, count=count, m_bids=m_bids,
+                    gt_mask=gt_mask, held=(x3d, x2d, cws, conf)), select
 
-        fine_ctx = contextlib.nullcontext()
+    def _fine_stage(self, data, fi, cb, select, ff, ff_strides, main, fkey, want_fine_debug, host_copy):
+        """Rows a9-a11 on the coarse stage's buffers ``cb`` (behind the kept-back selection ``select``) and the frame's :class:`PendingFrame`.  With ``hip_overlap_fine`` they run on
+        the compute stream's fine stream, behind an event of the coarse stage, and leave the event the next frame's encoder waits for.  The grid
+        is sized by the capacity B * N (one match per 3D point at most; surplus workgroups exit on the device-side count): no sync yet."""
+        lib_call, P = hip.call, hip.ptr
+        B, N, M, hf, dev, desc, qscale, W = fi.B, fi.N, fi.M, fi.hf, fi.dev, fi.desc_fine_d, fi.qscale, fi.W
+        cfg = self.config
+        fine_on = bool(cfg["fine_matching"]["enable"])
+        f32 = dict(device=dev, dtype=torch.float32)
+        cap = B * N
+        fine_ctx, fine_entry = contextlib.nullcontext(), None
         if fine_on and self.overlap_fine:
-            if fkey not in self._fine_streams:
-                if len(self._fine_streams) >= 16:
-                    self._fine_streams.pop(next(iter(self._fine_streams)))
-                self._fine_streams[fkey] = [torch.cuda.Stream(device=dev), None]
-            sfine = self._fine_streams[fkey][0]
+            fine_entry = _side_stream(self._fine_streams, fkey, dev, with_event=True)
             coarse_done = torch.cuda.Event()
             coarse_done.record(main)
-            sfine.wait_event(coarse_done)
-            fine_ctx = torch.cuda.stream(sfine)
-        keep = [desc_fine_d, W, qmask, qscale]      # inputs of the side-stream kernels stay referenced until finish()
-        keep += [x3d, x2d, cws, conf]
+            fine_entry[0].wait_event(coarse_done)
+            fine_ctx = torch.cuda.stream(fine_entry[0])
+        keep = [desc, W, fi.qmask, qscale, ff, *cb["held"]]          # inputs of the side-stream kernels stay referenced until finish()
+        expec = dbg_w = dbg_3 = None
         with fine_ctx:
             S = hip.stream_handle()
-            if split_select and padded:
-                lib_call("ophip_coarse_match_masked", *cm_args, 2, PM() if qmask is not None else None, P(qscale), S)
-            elif split_select:
-                lib_call("ophip_coarse_match_select", *cm_args, S)
+            if select is not None:
+                select(S)
             if fine_on:
-                # ---- a9-a11: fine refinement (grid sized by capacity, device-side count: no sync yet) ----
                 cf = cfg["loftr_fine"]
                 expec = torch.empty(cap, 3, **f32)
-                mkf = mk2d
                 dbg_w = torch.empty(cap, 25, 128, **f32) if want_fine_debug else None
                 dbg_3 = torch.empty(cap, 128, **f32) if want_fine_debug else None
                 names_f = self.loftr_fine.layer_names
                 cross_bits = sum(1 << i for i, n in enumerate(names_f) if n == "cross")
-                keep.append(ff)
-                stride = hf // hc
-                fine_scale = (cf["window_size"] // 2) * (data["q_hw_i"][0] / hf)
-                max_matches = cap                                # one match per 3D point at most: the grid covers every possible K (surplus workgroups exit)
+                stride = hf // fi.hc
                 if self.fine_full:
-                    fw, fd3 = self._fine_full_stage(ff, ff_strides, hf, wf, desc_fine_d, bstride(desc_fine_d), b_ids, i_ids, j_ids, count, cap, wc,
-                                                    stride, W["fine_full"], bool(cf["enable"]), mkc, qscale, float(data["q_hw_i"][0] / hf),
-                                                    expec, mkf, dev)
+                    fw, fd3 = self._fine_full_stage(fi, cb, ff, ff_strides, stride, float(data["q_hw_i"][0] / hf), expec)
                     if want_fine_debug:
                         dbg_w, dbg_3 = fw, fd3
-                elif self.precision == "f32":
-                    lib_call("ophip_fine_refine" + ("_scaled" if qscale is not None else ""), P(ff), *ff_strides, hf, wf,
-                             P(desc_fine_d), bstride(desc_fine_d), desc_fine_d.stride(1),
-                             P(b_ids, torch.int64), P(i_ids, torch.int64), P(j_ids, torch.int64), P(count, torch.int32), max_matches,
-                             P(mkc), P(W["fine"]), len(names_f), ctypes.c_uint(cross_bits), 1 if cf["enable"] else 0,
-                             wc, stride, float(fine_scale), P(expec), P(mkf), P(dbg_w), P(dbg_3), *((P(qscale),) if qscale is not None else ()), S)
                 else:
-                    lib_call("ophip_fine_refine_bf16" + ("_scaled" if qscale is not None else ""), P(ff), *ff_strides, hf, wf,
-                             P(desc_fine_d), bstride(desc_fine_d), desc_fine_d.stride(1),
-                             P(b_ids, torch.int64), P(i_ids, torch.int64), P(j_ids, torch.int64), P(count, torch.int32), max_matches,
-                             P(mkc), P(W["fine_bf16"], None), len(names_f), ctypes.c_uint(cross_bits), 1 if cf["enable"] else 0,
-                             3 if self.precision == "bf16x3" else 1,
-                             wc, stride, float(fine_scale), P(expec), P(mkf), P(dbg_w), P(dbg_3), *((P(qscale),) if qscale is not None else ()), S)
-
-            if fine_on and self.overlap_fine:
+                    bf = self.precision != "f32"          # the bf16 pipe's kernel takes its operand split (3: split-bf16, 1: plain) as well
+                    fine_scale = (cf["window_size"] // 2) * (data["q_hw_i"][0] / hf)
+                    lib_call("ophip_fine_refine" + ("_bf16" if bf else "") + ("_scaled" if qscale is not None else ""), P(ff), *ff_strides, hf, fi.wf,
+                             P(desc), bstride(desc), desc.stride(1),
+                             P(cb["b_ids"], torch.int64), P(cb["i_ids"], torch.int64), P(cb["j_ids"], torch.int64), P(cb["count"], torch.int32), cap,
+                             P(cb["mkc"]), P(W["fine_bf16"], None) if bf else P(W["fine"]), len(names_f), ctypes.c_uint(cross_bits), 1 if cf["enable"] else 0,
+                             *((_NSPLIT[self.precision],) if bf else ()),
+                             fi.wc, stride, float(fine_scale), P(expec), P(cb["mk2d"]), P(dbg_w), P(dbg_3), *((P(qscale),) if qscale is not None else ()), S)
+            if fine_entry is not None:
                 fine_done = torch.cuda.Event()
                 fine_done.record()
-                self._fine_streams[fkey][1] = fine_done
-            pend = PendingFrame(self, data, dev, B, N, M, cap, fine_on, want_fine_debug,
-                                dict(blob=blob, b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, mconf=mconf, mk3d=mk3d, mkc=mkc, count=count,
-                                     m_bids=m_bids, gt_mask=gt_mask,
-                                     expec=expec if fine_on else None, mkf=mkf if fine_on else None,
-                                     dbg_w=dbg_w if fine_on else None, dbg_3=dbg_3 if fine_on else None, keep=keep), host_copy)
-            pend._rerun = rerun
-        return pend
+                fine_entry[1] = fine_done
+            bufs = dict(blob=cb["blob"], b_ids=cb["b_ids"], i_ids=cb["i_ids"], j_ids=cb["j_ids"], mconf=cb["mconf"], mk3d=cb["mk3d"], mkc=cb["mkc"],
+                        count=cb["count"], m_bids=cb["m_bids"], gt_mask=cb["gt_mask"], expec=expec, mkf=cb["mk2d"] if fine_on else None,
+                        dbg_w=dbg_w, dbg_3=dbg_3, keep=keep)
+            return PendingFrame(self, data, dev, B, N, M, cap, fine_on, want_fine_debug, bufs, host_copy)
 
-
-    def _fine_full_stage(self, ff, ff_strides, hf, wf, desc, desc_bs, b_ids, i_ids, j_ids, count, cap, wc, stride, Wf, encoder_on, mkc, qscale,
-                         scale, expec, mkf, dev):
+    def _fine_full_stage(self, fi, cb, ff, ff_strides, stride, scale, expec):
         """Rows a9-a11 with the fine encoder's full attention, on the current stream: gather (window and 3D token rows), the encoder layers
         (transformer.py:133-171 on [K, 1, C] 3D tokens and [K, 25, C] windows; a cross layer's 3D update reads the pre-update windows), then
-        FineMatching on the one 3D token per match.  Every row count is the capacity: the kernels read the device-side count.  Returns the
+        FineMatching on the one 3D token per match into ``expec`` and ``cb["mk2d"]``.  Every row count is the capacity: the kernels read the device-side count.  Returns the
         encoder's output rows (windows [cap, 25, 128], 3D tokens [cap, 128])."""
         lib_call, P, S = hip.call, hip.ptr, hip.stream_handle()
-        f32 = dict(device=dev, dtype=torch.float32)
-        cnt = P(count, torch.int32)
+        f32 = dict(device=fi.dev, dtype=torch.float32)
+        desc, cap = fi.desc_fine_d, fi.B * fi.N
+        b_ids, i_ids, j_ids = (P(cb[k], torch.int64) for k in ("b_ids", "i_ids", "j_ids"))
+        cnt = P(cb["count"], torch.int32)
         WS, WW = 5, 25
         win, f3 = torch.empty(cap, WW, 128, **f32), torch.empty(cap, 128, **f32)
-        lib_call("ophip_fine_full_gather", P(ff), *ff_strides, hf, wf, P(desc), desc_bs, desc.stride(1), P(b_ids, torch.int64), P(i_ids, torch.int64),
-                 P(j_ids, torch.int64), cnt, cap, wc, stride, WS, P(win), P(f3), S)
+        lib_call("ophip_fine_full_gather", P(ff), *ff_strides, fi.hf, fi.wf, P(desc), bstride(desc), desc.stride(1), b_ids, i_ids, j_ids,
+                 cnt, cap, fi.wc, stride, WS, P(win), P(f3), S)
 
-        def lin(x, T, w, nout, xb=None, relu=False):
-            y = torch.empty(T, nout, **f32)
-            lib_call("ophip_rows_linear_x3", P(x), x.shape[-1], P(xb), xb.shape[-1] if xb is not None else 0, T, P(w, None), nout, 1 if relu else 0,
-                     P(y), S)
-            return y
-
-        def layer(x, Lx, src, Ls, w):                     # LoFTREncoderLayer with FullAttention (transformer.py:65-94)
-            T = cap * Lx
-            q, k, v = lin(x, T, w["q"], 128), lin(src, cap * Ls, w["k"], 128), lin(src, cap * Ls, w["v"], 128)
-            msg = torch.empty(T, 128, **f32)
-            lib_call("ophip_fine_full_attention", P(q), P(k), P(v), cap, Lx, Ls, cnt, P(msg), S)
-            m = lin(msg, T, w["m"], 128)
-            lib_call("ophip_rows_layernorm128", P(m), P(w["norm1_weight"]), P(w["norm1_bias"]), None, T, P(m), S)
-            h = lin(x, T, w["w0"], 256, xb=m, relu=True)
-            o = lin(h, T, w["w2"], 128)
-            y = torch.empty(T, 128, **f32)
-            lib_call("ophip_rows_layernorm128", P(o), P(w["norm2_weight"]), P(w["norm2_bias"]), P(x), T, P(y), S)
-            return y
-        if encoder_on:
-            for li, name in enumerate(self.loftr_fine.layer_names):
-                w = Wf[li]
+        def layer(x, Lx, src, Ls, w):                     # LoFTREncoderLayer with FullAttention over each match's Lx x Ls tokens
+            return rows_encoder_layer(x, cap * Lx, src, cap * Ls, w, lambda q, k, v, msg: lib_call(
+                "ophip_fine_full_attention", P(q), P(k), P(v), cap, Lx, Ls, cnt, P(msg), S))
+        if bool(self.config["loftr_fine"]["enable"]):
+            for w, name in zip(fi.W["fine_full"], self.loftr_fine.layer_names):
                 if name == "self":
                     win, f3 = layer(win, WW, win, WW, w), layer(f3, 1, f3, 1, w)
                 else:
                     win, f3 = layer(win, WW, f3, 1, w), layer(f3, 1, win, WW, w)
-        win, f3 = win.view(cap, WW, 128), f3.view(cap, 128)
-        lib_call("ophip_fine_full_match", P(f3), P(win), P(mkc), P(b_ids, torch.int64), P(qscale), cnt, cap, WS, float(scale), P(expec), P(mkf), S)
+        lib_call("ophip_fine_full_match", P(f3), P(win), P(cb["mkc"]), b_ids, P(fi.qscale), cnt, cap, WS, float(scale), P(expec),
+                 P(cb["mk2d"]), S)
         return win, f3
 
-    def _object_cache_entry(self, kpts_d, desc_in_d, W, dev, B, N, stream, masked=False, keep=True):
+    def _object_cache_entry(self, fi, stream, masked=False, keep=True):
         """The object's cache entry ``{"x3d", "y3d0", "kv1", "ev"}`` (``ophip_object_cache``), built on a miss on ``stream`` with the kernels a
         frame would run.  Keyed on the object tensors' storage + version and the packed weights; ``Bo`` = 1 rows when the batch shares one
         object block (stride-0 expand / batch-1 tensors under a larger query batch), else B."""
         lib_call, P = hip.call, hip.ptr
-        shared = B > 1 and kpts_d.shape[0] == 1 and desc_in_d.shape[0] == 1
-        Bo = 1 if shared else B
+        B, N, dev, kpts_d, desc_in_d, W = fi.B, fi.N, fi.dev, fi.kpts_d, fi.desc_in_d, fi.W
+        Bo = 1 if (B > 1 and kpts_d.shape[0] == 1 and desc_in_d.shape[0] == 1) else B
         names = self.loftr_coarse.layer_names
         deep = (self.precision == "bf16x3" and not self.coarse_full and not self.fine_full and len(names) >= 2 and names[0] == "self"
                 and os.environ.get("OPHIP_OBJECT_CACHE_DEPTH", "2") != "1")
@@ -702,20 +680,12 @@ class OnePosePlus_model(nn.Module):
         ent = self._obj_cache
         if keep and ent is not None and ent["key"] == ckey:
             return ent
-        f32 = dict(device=dev, dtype=torch.float32)
         with torch.cuda.stream(stream):
-            x3d = torch.empty(Bo, N, 256, **f32)
-            if self.kpt_3d_pos_encoding is not None:
-                stats = torch.empty(4 * Bo + 4, **f32)
-                lib_call("ophip_kpt_encode", P(kpts_d), 0 if kpts_d.shape[0] == 1 else kpts_d.stride(0), P(desc_in_d),
-                         0 if desc_in_d.shape[0] == 1 else desc_in_d.stride(0), P(W["kpt"]), P(stats), P(x3d), Bo, N, hip.stream_handle())
-            else:
-                src = desc_in_d if desc_in_d.shape[0] == Bo else desc_in_d.expand(Bo, -1, -1).contiguous()
-                lib_call("ophip_transpose_cl", P(src), P(x3d), Bo, 256, N, hip.stream_handle())
+            x3d = self._encode_keypoints(fi, Bo)
             y3d0 = kv1 = None
             if deep:
                 lib = hip.load()
-                y3d0 = torch.empty(Bo, N, 256, **f32)
+                y3d0 = torch.empty(Bo, N, 256, device=dev, dtype=torch.float32)
                 kv1 = torch.empty(Bo, lib.ophip_encoder_x3w8_kv_block_bytes(), device=dev, dtype=torch.uint8)
                 ws = torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(Bo, N, 1), device=dev, dtype=torch.uint8)
                 lib_call("ophip_encoder_object_x3w8", P(x3d), Bo, N, P(W["coarse_x3"][0], None), P(W["coarse_x3"][1], None), P(ws, None),
@@ -737,30 +707,13 @@ class OnePosePlus_model(nn.Module):
         if fkey in self._frame_call_pending:
             hip.call("ophip_frame_order_after_fine", ctypes.c_void_p(main.cuda_stream))
 
-    def _side_stream(self, table, fkey, dev):
-        st = table.get(fkey)
-        if st is None:
-            if len(table) >= 16:
-                table.pop(next(iter(table)))
-            st = table[fkey] = torch.cuda.Stream(device=dev)
-        return st
-
-    def _enqueue_frame_call(self, data, feat_c, feat_f, kpts_d, desc_in_d, desc_fine_d, x3d_ext, W, dev, main, fkey,
-                            B, N, M, hc, wc, hf, wf, host_copy, inputs_ready, lazy=False, rerun=None, qmask=None, qscale=None):
-        """The whole frame through ``ophip_frame_enqueue`` (csrc/frame.hip): one device block, one C call."""
-        cfg = self.config
-        fc = feat_c if (feat_c.dtype == torch.float32 and feat_c.is_contiguous()) else feat_c.float().contiguous()
-        ff = feat_f if feat_f.dtype == torch.float32 else feat_f.float()
-        transpose_fine = ff.stride(1) != 1
-        if transpose_fine:
-            ff = ff.contiguous()
-        cf_ch = ff.shape[1]
-        cm, lf = cfg["coarse_matching"], cfg["loftr_fine"]
-        img_h = data["q_hw_i"][0]
-        ext_mode = 0 if x3d_ext is None else (2 if x3d_ext["y3d0"] is not None else 1)      # ophip_frame_layout's external_x3d
+    def _frame_plan(self, fi, cf_ch, transpose_fine, ext_mode, img_h, lazy):
+        """``(desc, layout, plan id, kept tensors)`` of ``ophip_frame_enqueue`` for this input shape: built and registered once, then looked up"""
+        B, N, M, hc, wc, hf, wf, dev, W = fi.B, fi.N, fi.M, fi.hc, fi.wc, fi.hf, fi.wf, fi.dev, fi.W
         pkey = (str(dev), B, N, M, hc, wc, hf, wf, cf_ch, bool(transpose_fine), ext_mode, int(img_h), id(W), bool(lazy))
         plan = self._frame_plans.get(pkey)
         if plan is None:
+            cm, lf = self.config["coarse_matching"], self.config["loftr_fine"]
             d = hip.FrameDesc()
             d.B, d.N, d.M, d.hc, d.wc, d.hf, d.wf, d.cf = B, N, M, hc, wc, hf, wf, cf_ch
             d.lazy_conf = 1 if lazy else 0
@@ -787,19 +740,39 @@ class OnePosePlus_model(nn.Module):
             pid = ops.register_frame_plan(d, L, keep_alive=(W, pe))
             self._plan_ids.add(pid)
             plan = self._frame_plans[pkey] = (d, L, pid, (W, pe))      # W and the table stay alive with the pointers, here and in the registry
-        d, L, plan_id = plan[:3]
+        return plan
 
-        prev = self._fine_streams.get(fkey)
-        if prev is not None and prev[1] is not None:                      # a stage-by-stage frame before this one: order behind its fine stage
-            main.wait_event(prev[1])
-            prev[1] = None
-        if fkey not in self._fine_streams:
-            if len(self._fine_streams) >= 16:
-                self._fine_streams.pop(next(iter(self._fine_streams)))
-            self._fine_streams[fkey] = [torch.cuda.Stream(device=dev, priority=int(os.environ.get("OPHIP_FINE_PRIO", "0"))), None]
-        sfine = self._fine_streams[fkey][0]
-        sprep = self._side_stream(self._prep_streams, fkey, dev) if inputs_ready else None
-        scopy = self._side_stream(PendingFrame._copy_streams, (dev, main.cuda_stream), dev)
+    def _enqueue_frame_call(self, data, feat_c, feat_f, fi, main, fkey, host_copy, inputs_ready, lazy=False, rerun=None):
+        """The whole frame through ``ophip_frame_enqueue`` (csrc/frame.hip): one device block, one C call."""
+        B, N, M, dev, kpts_d, desc_in_d, desc_fine_d, qmask, qscale = fi.B, fi.N, fi.M, fi.dev, fi.kpts_d, fi.desc_in_d, fi.desc_fine_d, fi.qmask, fi.qscale
+        x3d_ext = None
+        if self.cache_object or (B > 1 and kpts_d.shape[0] == 1 and desc_in_d.shape[0] == 1):
+            # the reference keeps the object block resident across frames (OnePosePlus_inference_dataset.py:157-169): what depends on it
+            # and the weights alone is computed once per (object tensors, weights) and handed to the frame call -- the keypoint encoding
+            # (rows a2 + a3) and, with a first layer of kind "self", that layer's 3D rows and the K^T V | Ksum block of those rows as the
+            # second layer's source (transformer.py:148-159; ophip_encoder_object_x3w8: the frame's own launches on the 3D stream's
+            # workgroups, so a cached frame is bit-identical).  One entry serves the whole batch when it shares one object (config 3).
+            # A batch whose frames share ONE object block (stride-0 expand: BASELINE config 3) takes the same route WITHOUT the cache flag:
+            # the object-only work is then done once per CALL instead of once per frame of the batch -- nothing is kept for the next call
+            # (`keep=False`), so a forward still does all of its own work.
+            x3d_ext = self._object_cache_entry(fi, main, masked=qmask is not None, keep=self.cache_object)
+        fc = _dense(feat_c)
+        ff = feat_f if feat_f.dtype == torch.float32 else feat_f.float()
+        transpose_fine = ff.stride(1) != 1
+        if transpose_fine:
+            ff = ff.contiguous()
+        ext_mode = 0 if x3d_ext is None else (2 if x3d_ext["y3d0"] is not None else 1)      # ophip_frame_layout's external_x3d
+        d, L, plan_id = self._frame_plan(fi, ff.shape[1], transpose_fine, ext_mode, data["q_hw_i"][0], lazy)[:3]
+
+        fine_entry = self._fine_streams.get(fkey)
+        if fine_entry is None:                     # (only this path reads OPHIP_FINE_PRIO: the stage-by-stage path's fine stream has the default priority)
+            fine_entry = _side_stream(self._fine_streams, fkey, dev, int(os.environ.get("OPHIP_FINE_PRIO", "0")), with_event=True)
+        elif fine_entry[1] is not None:            # a stage-by-stage frame before this one: order behind its fine stage
+            main.wait_event(fine_entry[1])
+            fine_entry[1] = None
+        sfine = fine_entry[0]
+        sprep = _side_stream(self._prep_streams, fkey, dev) if inputs_ready else None
+        scopy = _side_stream(PendingFrame._copy_streams, (dev, main.cuda_stream), dev)
         cap = B * N
         if sprep is not None:
             # the input kernels write into the block on s_prep AHEAD of everything queued on the compute stream, so the block must come
@@ -808,18 +781,13 @@ class OnePosePlus_model(nn.Module):
             # that it goes back to the pool only after their work is done
             with torch.cuda.stream(sprep):
                 blob = torch.empty(L.total, dtype=torch.uint8, device=dev)
-            for st in (main, sfine, scopy):
-                blob.record_stream(st)
         else:
             blob = torch.empty(L.total, dtype=torch.uint8, device=dev)
-            for st in (sfine, scopy):
-                blob.record_stream(st)
+        for st in (sfine, scopy) if sprep is None else (main, sfine, scopy):
+            blob.record_stream(st)
         nbytes = int(L.result_bytes) if host_copy else 16
         pin = PendingFrame._take_pin((cap, bool(host_copy)), nbytes)
-        if transpose_fine:
-            fs = (0, 0, 0, 0)                                             # filled in by the callee for its channels-last copy
-        else:
-            fs = (ff.stride(0), 1, ff.stride(2), ff.stride(3))
+        fs = (0, 0, 0, 0) if transpose_fine else (ff.stride(0), 1, ff.stride(2), ff.stride(3))      # zeros: the callee fills in its channels-last copy's
         try:
             # the whole frame through ONE custom op (torch.ops.onepose_hip.frame_enqueue -> ophip_frame_enqueue).  The reference's two
             # profiler scopes (coarse_matching.py:122,167) enclose it -- get_coarse_match and its argmax are inside this call; a profiler no
@@ -841,13 +809,14 @@ class OnePosePlus_model(nn.Module):
         if lazy:
             f3 = blob[L.feat3d_out:L.feat3d_out + 4 * B * N * 256].view(torch.float32).view(B, N, 256)
             f2 = blob[L.feat2d_out:L.feat2d_out + 4 * B * M * 256].view(torch.float32).view(B, M, 256)
-            data["conf_matrix"] = LazyConfMatrix(f3, f2, float(cm["dual_softmax"]["temperature"]), 3, main, qmask)
+            data["conf_matrix"] = LazyConfMatrix(f3, f2, float(self.config["coarse_matching"]["dual_softmax"]["temperature"]), _NSPLIT["bf16x3"], main, qmask)
         else:
             data["conf_matrix"] = blob[L.conf:L.conf + 4 * B * N * M].view(torch.float32).view(B, N, M)
-        keep = [fc, ff, kpts_d, desc_in_d, desc_fine_d, x3d_ext, W, qmask, qscale]
+        keep = [fc, ff, kpts_d, desc_in_d, desc_fine_d, x3d_ext, fi.W, qmask, qscale]
         pend = PendingFrame._from_block(self, data, dev, B, N, M, cap, blob, L, slot, pin, host_copy, keep)
         pend._rerun = rerun
         return pend
+
 
 class LazyConfMatrix:
     """``data["conf_matrix"]`` of the lazy form (``config["hip_conf_matrix"] = "lazy"``): the N x M dual-softmax matrix is not stored
@@ -924,10 +893,6 @@ def _result_views(blob, cap):
             blob[o_3:o_2].view(torch.float32).view(cap, 3), blob[o_2:o_2 + 8 * cap].view(torch.float32).view(cap, 2))
 
 
-def _result_block(dev, cap):
-    return _result_views(torch.empty(16 + 28 * cap, dtype=torch.uint8, device=dev), cap)
-
-
 class PendingFrame:
     """A batch whose kernels are enqueued but whose match count has not been read yet."""
 
@@ -948,11 +913,7 @@ class PendingFrame:
         # the D2H of the result block runs on a side stream behind an event: on the compute stream the PCIe round trip
         # (~40 us per frame) would sit between this frame's last kernel and the next frame's first one
         main = torch.cuda.current_stream(dev)
-        side = PendingFrame._copy_streams.get((dev, main.cuda_stream))
-        if side is None:
-            if len(PendingFrame._copy_streams) >= 16:          # keyed on raw stream handles: drop the oldest instead of growing for ever
-                PendingFrame._copy_streams.pop(next(iter(PendingFrame._copy_streams)))
-            side = PendingFrame._copy_streams[(dev, main.cuda_stream)] = torch.cuda.Stream(device=dev)
+        side = _side_stream(PendingFrame._copy_streams, (dev, main.cuda_stream), dev)
         ready = torch.cuda.Event()
         ready.record(main)
         side.wait_event(ready)
@@ -1084,8 +1045,4 @@ def build_model(model_configs, ckpt_path) -> OnePosePlus_model:
     executed)."""
     model = OnePosePlus_model(model_configs)
     state_dict = torch.load(ckpt_path, map_location="cpu", weights_only=True)["state_dict"]
-    for k in list(state_dict.keys()):
-        state_dict[k.replace("matcher.", "")] = state_dict.pop(k)
-    model.load_state_dict(state_dict, strict=True)
-    model.eval()
-    return model
+    return load_matcher_checkpoint(model, state_dict)

@@ -53,10 +53,6 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
-def _bstride(t: torch.Tensor) -> int:
-    return 0 if t.shape[0] == 1 or t.stride(0) == 0 else t.stride(0)
-
-
 def _pe_add_transpose(feat_nchw, pe_nlc, out_nlc):
     B, C, h, w = feat_nchw.shape
     hip.call("ophip_pe_add_transpose", hip.ptr(_f32(feat_nchw, "feat_nchw")), hip.ptr(pe_nlc), hip.ptr(_f32(out_nlc, "out_nlc")), B, C, h * w,
@@ -108,7 +104,7 @@ def _coarse_match(feat3d, feat2d, keypoints3d, wc, temperature, thr, border_rm, 
     mconf, mk3, mkc = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     hip.call("ophip_coarse_match", hip.ptr(_f32(feat3d, "feat3d")), hip.ptr(_f32(feat2d, "feat2d")), hip.ptr(_f32(keypoints3d, "keypoints3d")),
-             _bstride(keypoints3d), B, N, M, int(wc), float(temperature), float(thr), int(border_rm), float(scale), hip.ptr(conf), hip.ptr(ws),
+             hip.bstride(keypoints3d), B, N, M, int(wc), float(temperature), float(thr), int(border_rm), float(scale), hip.ptr(conf), hip.ptr(ws),
              *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), None, None, hip.ptr(count, torch.int32),
              int(nsplit), hip.stream_handle())
     return conf, ids[0], ids[1], ids[2], mconf, mk3, mkc, count
@@ -125,7 +121,7 @@ def _fine_refine_bf16(feat_f_cl, desc3d_f, b_ids, i_ids, j_ids, count, mkpts_c, 
     dev = feat_f_cl.device
     expec, mkf = torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
     hip.call("ophip_fine_refine_bf16", hip.ptr(feat_f_cl), feat_f_cl.stride(0), feat_f_cl.stride(1), feat_f_cl.stride(2), feat_f_cl.stride(3), hf, wf,
-             hip.ptr(_f32(desc3d_f, "desc3d_f")), _bstride(desc3d_f), desc3d_f.stride(1),
+             hip.ptr(_f32(desc3d_f, "desc3d_f")), hip.bstride(desc3d_f), desc3d_f.stride(1),
              hip.ptr(b_ids, torch.int64), hip.ptr(i_ids, torch.int64), hip.ptr(j_ids, torch.int64), hip.ptr(count, torch.int32), cap,
              hip.ptr(_f32(mkpts_c, "mkpts_c")), hip.ptr(wpack, None), int(nlayers), ctypes.c_uint(int(cross_bits)), int(bool(encoder_enable)), int(nsplit),
              int(wc), int(stride), float(fine_scale), hip.ptr(expec), hip.ptr(mkf), None, None, hip.stream_handle())
@@ -201,8 +197,8 @@ def _frame_enqueue(plan, block, feat_c, feat_f, fine_strides, keypoints3d, desc3
             oc.kv1, oc.kv1_bs = kv1.data_ptr(), (0 if shared else kvb)
         oc.ready = int(object_ready) or None
     hip.call("ophip_frame_enqueue_object", ctypes.byref(d), ctypes.byref(L), vp(block.data_ptr()),
-             hip.ptr(feat_c), hip.ptr(feat_f), fs[0], fs[1], fs[2], fs[3], hip.ptr(keypoints3d), _bstride(keypoints3d),
-             hip.ptr(desc3d_c), _bstride(desc3d_c), hip.ptr(desc3d_f), _bstride(desc3d_f), desc3d_f.stride(1), ctypes.byref(oc) if oc is not None else None,
+             hip.ptr(feat_c), hip.ptr(feat_f), fs[0], fs[1], fs[2], fs[3], hip.ptr(keypoints3d), hip.bstride(keypoints3d),
+             hip.ptr(desc3d_c), hip.bstride(desc3d_c), hip.ptr(desc3d_f), hip.bstride(desc3d_f), desc3d_f.stride(1), ctypes.byref(oc) if oc is not None else None,
              hip.ptr(query_mask, torch.uint8), hip.ptr(query_scale), vp(host_dst.data_ptr()), int(host_bytes), vp(s_main), vp(s_prep) if s_prep else None, vp(s_fine), vp(s_copy), ctypes.byref(slot))
     return slot.value
 

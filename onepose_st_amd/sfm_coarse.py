@@ -150,10 +150,9 @@ def build_model(state_dict: dict, config: dict | None = None):
     """the reference's ``build_model`` (coarse_match_worker.py:18-29): ``LoFTR_for_OnePose_Plus(config, enable_fine_matching=False)``,
     ``matcher.``-prefixed keys stripped, loaded with ``strict=True``, eval mode (move it to the device yourself)"""
     from .loftr import LoFTR_for_OnePose_Plus, default_cfg
+    from .params import load_matcher_checkpoint
 
-    m = LoFTR_for_OnePose_Plus(copy.deepcopy(config or default_cfg), enable_fine_matching=False)
-    m.load_state_dict({k.replace("matcher.", ""): v for k, v in state_dict.items()}, strict=True)
-    return m.eval()
+    return load_matcher_checkpoint(LoFTR_for_OnePose_Plus(copy.deepcopy(config or default_cfg), enable_fine_matching=False), state_dict)
 
 
 @torch.no_grad()

@@ -219,3 +219,35 @@ def test_packed_weights_follow_the_parameters_without_walking_the_module_tree_ev
     assert m._weights(cpu) is w4
     m.double()                                                         # _apply drops the list as well
     assert m.__dict__["_param_cache"] is None
+
+
+def test_state_dict_key_order_and_shapes_of_both_matchers(sd, cfg):
+    """Both matchers build their encoders from the shared parameter holders (params.py): each model's ``state_dict`` keeps its key LIST
+    (order included) and shapes -- those of the synthetic state dicts -- and loads them strictly, through the shared checkpoint loader
+    as well (``matcher.`` prefix stripped, ``eval()``)."""
+    import copy
+
+    from onepose_st_amd import loftr
+    from onepose_st_amd.params import load_matcher_checkpoint
+    from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
+
+    no_kpt = copy.deepcopy(cfg)
+    no_kpt["keypoints_encoding"]["enable"] = False
+    skh = copy.deepcopy(loftr.default_cfg)
+    skh["match_coarse"]["match_type"] = "sinkhorn"
+    lsd = make_synthetic_loftr_state_dict(0)
+    cases = [
+        (OnePosePlus_model(copy.deepcopy(cfg)), sd),
+        (OnePosePlus_model(no_kpt), {k: v for k, v in sd.items() if not k.startswith("kpt_3d_pos_encoding.")}),
+        (loftr.LoFTR_for_OnePose_Plus(), lsd),
+        (loftr.LoFTR_for_OnePose_Plus(skh), {**lsd, "coarse_matching.bin_score": torch.tensor(0.5)}),
+    ]
+    assert len(cases[0][0].state_dict()) == 195 and len(cases[1][0].state_dict()) == 195 - 8
+    for m, want in cases:
+        own = m.state_dict()
+        assert list(own) == list(want)
+        assert [tuple(v.shape) for v in own.values()] == [tuple(v.shape) for v in want.values()]
+        m.train()
+        assert load_matcher_checkpoint(m, {"matcher." + k: v for k, v in want.items()}) is m and not m.training
+        got = m.state_dict()
+        assert all(torch.equal(got[k], want[k]) for k in want)

@@ -1115,6 +1115,39 @@ def test_object_cache_is_bit_identical(sd, cfg, dev, monkeypatch):
         assert torch.equal(a[k], b[k]), k
 
 
+@pytest.mark.parametrize("precision", ["bf16x3", "bf16", "f32"])
+def test_stage_by_stage_encoder_never_writes_the_cached_encoding(sd, cfg, dev, precision):
+    """The stage-by-stage path (``hip_frame_call`` off) rotates the coarse encoder's buffers over a cached, read-only keypoint encoding
+    (``hip_cache_object``): two consecutive frames, the second with its input kernels on the side stream, give every output of the
+    uncached model bit for bit -- both run the same kernels -- and leave the cached rows as the first frame wrote them."""
+    models = []
+    for cache in (True, False):
+        c = copy.deepcopy(cfg)
+        c["hip_precision"], c["hip_frame_call"], c["hip_cache_object"] = precision, False, cache
+        m = OnePosePlus_model(c).eval()
+        m.load_state_dict(sd, strict=True)
+        models.append(m.to(dev))
+    cached, plain = models
+    frames = [make_synthetic_inputs(sd, n_points=900, image_hw=(128, 160), n_plant=350, seed=47, config=cfg, frame=f) for f in range(2)]
+    obj = {k: frames[0][k].to(dev) for k in ("keypoints3d", "descriptors3d_db", "descriptors3d_coarse_db")}
+    x3d_first = None
+    for t, f in enumerate(frames):
+        fc, ff = f["feat_c"].to(dev), f["feat_f"].to(dev)
+        torch.cuda.synchronize()                                # inputs_ready: nothing that writes the inputs is still queued
+        a, b = dict(obj), dict(obj)
+        plain.enqueue_features(a, fc, ff, f["image_hw"], inputs_ready=t == 1).finish()
+        cached.enqueue_features(b, fc, ff, f["image_hw"], inputs_ready=t == 1).finish()
+        torch.cuda.synchronize()
+        assert not cached._frame_plans and len(a["i_ids"]) > 150
+        assert set(a) == set(b) and {"b_ids", "i_ids", "j_ids", "mconf", "mkpts_3d_db", "mkpts_query_c", "mkpts_query_f", "expec_f", "conf_matrix"} <= set(b)
+        for k in b:
+            if k not in obj:
+                assert torch.equal(a[k], b[k]) if torch.is_tensor(b[k]) else a[k] == b[k], (t, k)
+        if t == 0:
+            x3d_first = cached._obj_cache["x3d"].clone()
+    assert plain._obj_cache is None and torch.equal(cached._obj_cache["x3d"], x3d_first)
+
+
 @pytest.mark.parametrize("size", ["ragged_b2", "c1", "c2"])
 def test_lazy_conf_matrix_is_bit_identical_to_the_eager_form(sd, cfg, dev, size):
     """config["hip_conf_matrix"] = "lazy": conf_matrix is never stored (two passes over the similarity tiles, candidates only);
