@@ -7,8 +7,8 @@ residual.py:6-78.  Here the whole loop is HIP (``csrc/postopt.hip``): one prep k
 on the device.  Also here: the caller's depth-to-world and reprojection updates (dataset/coarse_colmap_dataset.py:353-423), and
 float64 restatements of pytorch3d's ``so3_exp_map`` / ``so3_log_map`` (pytorch3d is not a dependency).
 
-Device tensors only: CPU inputs raise :class:`hip.HipLibraryError`.  COLMAP I/O, triangulation and feature aggregation stay with the
-caller.
+Device tensors only: CPU inputs raise :class:`hip.HipLibraryError`.  COLMAP I/O and feature aggregation stay with the
+caller; the triangulation is ``sfm_triangulate``'s.
 """
 from __future__ import annotations
 

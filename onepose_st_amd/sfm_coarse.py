@@ -27,7 +27,8 @@ The merge's contract (``merge_pair_matches``), bit-exact against the reference's
   an image index outside ``[0, I)`` raises ``IndexError``; CPU tensors raise :class:`hip.HipLibraryError`.
 
 The pair order the caller passes IS the reference's dict order: it decides the float64 summation order.  The reference's
-``random.shuffle`` of the pair list and its h5 files stay with the caller (h5py is not a dependency).
+``random.shuffle`` of the pair list and its h5 files stay with the caller (h5py is not a dependency).  The merge's result, with
+``pair_images`` added, is what ``sfm_triangulate.triangulate`` takes.
 """
 from __future__ import annotations
 

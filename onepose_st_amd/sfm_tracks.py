@@ -7,7 +7,8 @@ per-track rows the optimiser and the feature aggregation read (``ConstructOptimi
 aggregation loop at the top of ``optimizer.py:start_optimize``), all in Python loops over every track element.  Here the sequential
 part is HIP (``csrc/sfm_tracks.hip`` in ``libonepose_sfm_tracks.so``, include/onepose_sfm_tracks.h); the integer
 tables between the launches are sorted, scanned and compacted with torch on the device.  File I/O (``read_write_model``, images,
-pickles), triangulation, the matcher itself and the rotation-matrix / quaternion round trip stay with the caller.
+pickles), the matcher itself and the rotation-matrix / quaternion round trip stay with the caller; the model comes from
+``sfm_triangulate.triangulate``.
 
 The model, a dict of flat device tensors:
 
