@@ -355,8 +355,12 @@ int ophip_frame_enqueue_object(const ophip_frame_desc* desc, const ophip_frame_l
  *   + bilinear x2 upsampling with align_corners=True of `up` [B][Hup][Wup][cout_pad] f32 (FPN top-down, resnet.py:155-160),
  *   + `table` [Hout][Wout][cout_pad] f32 shared by all batch elements (the positional encoding of the coarse map, a1),
  *   activation (0 none, 1 ReLU, 2 LeakyReLU 0.01), then planes (out_hi/out_lo) and / or f32 channels-last
- *   out_f32 [B][Hout][Wout][out_c] (out_c <= cout_pad, multiple of 4). */
+ *   out_f32 [B][Hout][Wout][out_c] (out_c <= cout_pad, multiple of 4).
+ * ophip_conv_tile_shape: host query, launches nothing and touches no device: the wave tile ophip_conv2d_bf16 runs these sizes with,
+ *   th x nt MFMA tiles (32 th pixels x 32 nt channels) per wave and wave_rows wave rows per workgroup.  Same checks of B, Hin, Win,
+ *   cout_pad, ks and stride as ophip_conv2d_bf16; on -1 the three outputs are left as they were.  (Added without a version step.) */
 size_t ophip_conv_wpack_bytes(int cin_pad, int cout_pad, int ks);
+int ophip_conv_tile_shape(int B, int Hin, int Win, int cout_pad, int ks, int stride, int* th, int* nt, int* wave_rows);
 int ophip_stem_conv7(const float* image, int B, int H, int W, const float* wpack, void* out_hi, void* out_lo, int nsplit, void* stream);
 int ophip_conv2d_bf16(const void* in_hi, const void* in_lo, int B, int Hin, int Win, int cin_pad,
                       const void* wpack, int cout_pad, int ks, int stride, int act,

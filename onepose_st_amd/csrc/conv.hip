@@ -45,6 +45,33 @@ struct ConvArgs {
 
 __device__ __forceinline__ int patch_off(int p, int c) { return p * PIXB + ((c ^ ((p >> 2) & 3)) << 4); }
 
+// Seeded errors of tests/test_gpu_backbone.py (tools/build_variant.sh with EXTRA=-DOPHIP_CONV_ERR_...; all off in the normal
+// build).  Each one picks another REGISTER or value, never another address, bound or guard:
+//   _TH: the second accumulator row (TH = 2) takes the activation fragment of the first
+//   _NT: the second channel tile (NT = 2) takes the first tile's weight fragments
+//   _WR: with two wave rows the stage write takes acc[t][0] for every row
+//   _UP: the bilinear add reads row uy0 for both of its rows
+#ifdef OPHIP_CONV_ERR_TH
+constexpr bool ERR_TH = true;
+#else
+constexpr bool ERR_TH = false;
+#endif
+#ifdef OPHIP_CONV_ERR_NT
+constexpr bool ERR_NT = true;
+#else
+constexpr bool ERR_NT = false;
+#endif
+#ifdef OPHIP_CONV_ERR_WR
+constexpr bool ERR_WR = true;
+#else
+constexpr bool ERR_WR = false;
+#endif
+#ifdef OPHIP_CONV_ERR_UP
+constexpr bool ERR_UP = true;
+#else
+constexpr bool ERR_UP = false;
+#endif
+
 template <int KS, int STRIDE, int NS, int TH, int NT, int WR>
 __global__ __launch_bounds__(128 * WR) OPHIP_WAVES_PER_SIMD((TH * NT <= 4 && !(TH == 1 && NT == 2)) ? 3 : 2, (TH * NT >= 8) ? 2 : 3) void conv_mfma_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -135,7 +162,10 @@ __global__ __launch_bounds__(128 * WR) OPHIP_WAVES_PER_SIMD((TH * NT <= 4 && !(T
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int tt = 0; tt < TH; ++tt) acc[t][tt] = mma_bf16<NS>(rh[kbl][t], rl[kbl][t], xh[cur][tt], xl[cur][tt], acc[t][tt]);
+                for (int tt = 0; tt < TH; ++tt) {
+                    const int tw = ERR_NT ? 0 : t, tx = ERR_TH ? 0 : tt;          // (seeded errors: off in the normal build)
+                    acc[t][tt] = mma_bf16<NS>(rh[kbl][tw], rl[kbl][tw], xh[cur][tx], xl[cur][tx], acc[t][tt]);
+                }
             {
                 const size_t nx = (size_t)min(s + 2, S - 1) * 64;        // the last two refills re-read the final k-block (unused)
 #pragma unroll
@@ -171,7 +201,8 @@ __global__ __launch_bounds__(128 * WR) OPHIP_WAVES_PER_SIMD((TH * NT <= 4 && !(T
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int ch = (32 * (NT * wc + t) + 8 * g + 4 * h) >> 2;
-                        const f32x4 v = {acc[t][tt][4 * g], acc[t][tt][4 * g + 1], acc[t][tt][4 * g + 2], acc[t][tt][4 * g + 3]};
+                        const f32x16& av = acc[t][(ERR_WR && WR == 2) ? 0 : tt];
+                        const f32x4 v = {av[4 * g], av[4 * g + 1], av[4 * g + 2], av[4 * g + 3]};
                         *reinterpret_cast<f32x4*>(stage + r * SROW + ((ch ^ (r & 15)) << 4)) = v;
                     }
             }
@@ -183,7 +214,7 @@ __global__ __launch_bounds__(128 * WR) OPHIP_WAVES_PER_SIMD((TH * NT <= 4 && !(T
             const float sy = a.Hout > 1 ? (float)(a.Hup - 1) / (float)(a.Hout - 1) : 0.f;
             const float fy = sy * (float)y;
             uy0 = min((int)fy, a.Hup - 1);
-            uy1 = uy0 + (uy0 < a.Hup - 1 ? 1 : 0);
+            uy1 = ERR_UP ? uy0 : uy0 + (uy0 < a.Hup - 1 ? 1 : 0);
             upy_l = fminf(fmaxf(fy - (float)uy0, 0.f), 1.f);
         }
         for (int i = tid; i < 32 * CH16; i += NTHR) {
@@ -328,14 +359,14 @@ int launch_conv_tile(const ConvArgs& a, int B, hipStream_t stream) {
 // Measured per layer at 480 x 640 (tools/bench_backbone_hip.py, B = 1 and 4): (2, 2) wins whenever it yields >= 2 waves
 // per SIMD; below that the 1/4-resolution maps take (2, 1), the 1/8-resolution maps (1, 1); stride-2 convolutions (large
 // input patch per tile) prefer to stay at 2 channel tiles per wave; (4, x) never won and is not built.
-template <int KS, int STRIDE, int NS>
-int launch_conv(const ConvArgs& a, int B, hipStream_t stream) {
-    const long w22 = (long)((a.Wout + TW - 1) / TW) * ((a.Hout + 1) / 2) * B * ((a.ctiles + 3) / 4) * 2;      // waves of the (2, 2) shape
-    int th = 2, nt = 2;
-    if (KS == 3 && STRIDE == 1) {
+// The one copy of the rule: launch_conv and the host query ophip_conv_tile_shape both call it.
+void conv_tile_shape(int ks, int stride, int B, int Hout, int Wout, int ctiles, int& th, int& nt, int& wrows) {
+    const long w22 = (long)((Wout + TW - 1) / TW) * ((Hout + 1) / 2) * B * ((ctiles + 3) / 4) * 2;      // waves of the (2, 2) shape
+    th = 2; nt = 2;
+    if (ks == 3 && stride == 1) {
         if (w22 < 2000) nt = 1;
         if (2 * w22 < 2000) th = 1;
-    } else if (KS == 3) {
+    } else if (ks == 3) {
         if (w22 < 2000) th = 1;
         if (w22 < 1000) nt = 1;
     } else if (w22 < 2000) {
@@ -343,7 +374,13 @@ int launch_conv(const ConvArgs& a, int B, hipStream_t stream) {
     }
     // wave rows per workgroup: 2 (a 4-wave workgroup on a shared patch: halo 1.6x instead of 2.1x at TH = 2) when the map is
     // tall enough to keep the grid full
-    const int wrows = (KS == 3 && STRIDE == 1 && w22 >= 2000) ? 2 : 1;
+    wrows = (ks == 3 && stride == 1 && w22 >= 2000) ? 2 : 1;
+}
+
+template <int KS, int STRIDE, int NS>
+int launch_conv(const ConvArgs& a, int B, hipStream_t stream) {
+    int th, nt, wrows;
+    conv_tile_shape(KS, STRIDE, B, a.Hout, a.Wout, a.ctiles, th, nt, wrows);
 #define OPHIP_CONV_CASE(TH_, NT_, WR_) if (th == TH_ && nt == NT_ && wrows == WR_) return launch_conv_tile<KS, STRIDE, NS, TH_, NT_, WR_>(a, B, stream);
     OPHIP_CONV_CASE(2, 2, 1) OPHIP_CONV_CASE(2, 1, 1) OPHIP_CONV_CASE(1, 2, 1) OPHIP_CONV_CASE(1, 1, 1)
     OPHIP_CONV_CASE(2, 2, 2) OPHIP_CONV_CASE(2, 1, 2) OPHIP_CONV_CASE(1, 2, 2) OPHIP_CONV_CASE(1, 1, 2)
@@ -355,6 +392,15 @@ int launch_conv(const ConvArgs& a, int B, hipStream_t stream) {
 
 extern "C" size_t ophip_conv_wpack_bytes(int cin_pad, int cout_pad, int ks) {
     return (size_t)2 * cout_pad * cin_pad * ks * ks * 2 + (size_t)cout_pad * 4;       // hi plane | lo plane | bias f32
+}
+
+extern "C" int ophip_conv_tile_shape(int B, int Hin, int Win, int cout_pad, int ks, int stride, int* th, int* nt, int* wave_rows) {
+    if (!th || !nt || !wave_rows) return ophip_bad_arg(__func__, "null pointer");
+    if (B < 1 || Hin < 1 || Win < 1 || cout_pad < 32 || cout_pad % 32) return ophip_bad_arg(__func__, "bad sizes (channels padded to 32)");
+    if (!((ks == 3 || ks == 1) && (stride == 1 || stride == 2))) return ophip_bad_arg(__func__, "kernel 1 or 3, stride 1 or 2");
+    const int pad = ks / 2;
+    conv_tile_shape(ks, stride, B, (Hin + 2 * pad - ks) / stride + 1, (Win + 2 * pad - ks) / stride + 1, cout_pad / 32, *th, *nt, *wave_rows);
+    return 0;
 }
 
 extern "C" int ophip_conv2d_bf16(const void* in_hi, const void* in_lo, int B, int Hin, int Win, int cin_pad,

@@ -76,6 +76,29 @@ def test_pe_add_transpose_exact(dev):
     assert torch.equal(out.cpu(), ref)           # one f32 add per element on identical table bits
 
 
+def _transpose_cl_exact(dev, B, C, L):
+    x = torch.randn(B, C, L, generator=torch.Generator().manual_seed(B * 100003 + C * 1009 + L)).to(dev)
+    out = torch.full((B * L + 1, C), -3.0, device=dev)          # one row longer than the result
+    hip.call("ophip_transpose_cl", hip.ptr(x), hip.ptr(out), B, C, L, hip.stream_handle())
+    torch.cuda.synchronize()
+    assert torch.equal(out[:B * L].view(B, L, C), x.transpose(1, 2).contiguous())          # a copy: bit for bit
+    assert bool((out[B * L] == -3.0).all())                                                 # and nothing behind the last row
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("L", [1, 31, 32, 33, 1000])
+def test_transpose_cl_128_channels_exact(dev, B, L):
+    """``transpose_c128_kernel``: 32 positions per workgroup, so L below, at and above one tile, and many tiles."""
+    _transpose_cl_exact(dev, B, 128, L)
+
+
+@pytest.mark.parametrize("C", [1, 100, 256])
+@pytest.mark.parametrize("L", [1, 33, 1000])
+def test_transpose_cl_generic_exact(dev, C, L):
+    """The generic 32 x 32 tile kernel (every C but 128): ragged tiles along both axes."""
+    _transpose_cl_exact(dev, 2, C, L)
+
+
 @pytest.mark.parametrize("B,N,shared", [(1, 77, False), (2, 1000, False), (3, 33, True)])
 def test_kpt_encode(sd, dev, B, N, shared):
     g = torch.Generator().manual_seed(1)
