@@ -379,8 +379,13 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             mk1c = mk1c * (s1[b_ids] if s1.shape[0] > 1 else s1)
         return x0, x1, conf, b_ids, ids[1][:K], ids[2][:K], ids[3][:K], gt_mask[:K], mconf[:K], mk0c, mk1c
 
-    def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug):
-        """fine stage (windows on both images, two-stream fine transformer, correlation + soft-argmax) on the matches' cells"""
+    def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug,
+              b_ids1=None, scale_ids=None):
+        """fine stage (windows on both images, two-stream fine transformer, correlation + soft-argmax) on the matches' cells.
+        ``b_ids1`` / ``scale_ids`` (``sfm_fine``: every row names its own two images): the batch index into ``ff1`` and the row of ``s1``
+        when they are not ``b_ids``"""
+        b_ids1 = b_ids if b_ids1 is None else b_ids1
+        scale_ids = b_ids if scale_ids is None else scale_ids
         call, P, S = hip.call, hip.ptr, hip.stream_handle()
         dev = ff0.device
         Wf = int(self.config["fine_window_size"])
@@ -393,7 +398,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         ff0c, ff1c = ff0.contiguous(), ff1.contiguous()          # [V or 1][hf * wf][128] channels-last
         call("ophip_fine2_gather_b", P(ff0c), ff0c.stride(0) if ff0c.shape[0] > 1 else 0, P(b_ids, torch.int64), hw0_f[0], hw0_f[1],
              P(i_ids, torch.int64), K, hw0_c[1], stride, Wf, P(f0), S)
-        call("ophip_fine2_gather_b", P(ff1c), ff1c.stride(0) if ff1c.shape[0] > 1 else 0, P(b_ids, torch.int64), hw1_f[0], hw1_f[1],
+        call("ophip_fine2_gather_b", P(ff1c), ff1c.stride(0) if ff1c.shape[0] > 1 else 0, P(b_ids1, torch.int64), hw1_f[0], hw1_f[1],
              P(j_ids, torch.int64), K, hw1_c[1], hw1_f[0] // hw1_c[0], Wf, P(f1), S)
         T = K * WW
         attn = "ophip_fine2_full_attention" if self.fine_full else "ophip_fine2_attention"
@@ -413,7 +418,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             s1 = s1 if s1 is not None else torch.ones(1, 2, device=dev)
             mk1c_ = mk1c.contiguous()
             mk1f = torch.empty(K, 2, dtype=mk1c.dtype, device=dev)
-            call("ophip_fine2_match_scaled", P(f0), P(f1), P(mk1c_, None), int(mk1c.dtype == torch.float64), P(b_ids, torch.int64), P(s1),
+            call("ophip_fine2_match_scaled", P(f0), P(f1), P(mk1c_, None), int(mk1c.dtype == torch.float64), P(scale_ids, torch.int64), P(s1),
                  2 if s1.shape[0] > 1 else 0, K, Wf, float(h0i / hw0_f[0]), P(expec), P(mk1f, None), S)
         else:
             mk1f = torch.empty(K, 2, device=dev)
