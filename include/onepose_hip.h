@@ -187,7 +187,8 @@ int ophip_coarse_match_select(const float* feat3d, const float* feat2d, const fl
  * (loftr_module/fine_preprocess.py:32-55, loftr_module/transformer.py:133-171, utils/fine_matching.py:28-110).
  * feat_f: fine feature map addressed by strides in floats (NCHW or channels-last), hf x wf.
  * desc3d_f [B][128][N] (strides ds_b, ds_c).  Matches come from ophip_coarse_match (device count, no host sync);
- * the grid covers max_matches, surplus workgroups exit.  expec_f [.][3] = (x, y, std), mkpts_f [.][2].
+ * the grid covers max_matches, surplus workgroups exit.  *count is clamped to max_matches in every variant (f32, bf16, _scaled): a count
+ * above the capacity refines rows 0 .. max_matches - 1 and writes no output row >= max_matches.  expec_f [.][3] = (x, y, std), mkpts_f [.][2].
  * dbg_win [.][25][128] / dbg_f3 [.][128] (both or neither; NULL in production) receive the fine-encoder outputs. */
 int ophip_fine_refine(const float* feat_f, long long fs_b, long long fs_c, long long fs_y, long long fs_x, int hf, int wf,
                       const float* desc3d_f, long long ds_b, long long ds_c,

@@ -24,7 +24,7 @@ struct FineArgs {
     const float* feat_f; long long fs_b, fs_c, fs_y, fs_x; int hf, wf;
     const float* desc_f; long long ds_b, ds_c;          // [B][128][N], n-stride 1
     const long long *b_ids, *i_ids, *j_ids;
-    const int* count;
+    const int* count; int cap;   // device-side match count; capacity of the id lists (the grid covers it)
     const float* mkq_c;
     const float* wpack;          // nlayers x LAYER_FLOATS
     int nlayers; unsigned cross_bits;                    // bit l set: layer l is "cross"
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) OPHIP_WAVES_PER_SIMD(1, 2) void fine_refine_ke
     float* P = X + 32 * LDF;             // [32][LDF]
     float* Hh = P + 32 * LDF;            // [32][LDF2]
     const int k = blockIdx.x;
-    if (k >= *p.count) return;
+    if (k >= min(*p.count, p.cap)) return;        // the count is clamped to the capacity, as in fine_bf16.hip (here the grid already ends there)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int b = (int)p.b_ids[k], i3 = (int)p.i_ids[k], j = (int)p.j_ids[k];
@@ -233,7 +233,7 @@ int fine_f32(const float* feat_f, long long fs_b, long long fs_c, long long fs_y
     FineArgs a;
     a.feat_f = feat_f; a.fs_b = fs_b; a.fs_c = fs_c; a.fs_y = fs_y; a.fs_x = fs_x; a.hf = hf; a.wf = wf;
     a.desc_f = desc3d_f; a.ds_b = ds_b; a.ds_c = ds_c;
-    a.b_ids = b_ids; a.i_ids = i_ids; a.j_ids = j_ids; a.count = count; a.mkq_c = mkpts_c;
+    a.b_ids = b_ids; a.i_ids = i_ids; a.j_ids = j_ids; a.count = count; a.cap = max_matches; a.mkq_c = mkpts_c;
     a.wpack = wpack; a.nlayers = nlayers; a.cross_bits = cross_bits; a.enc_enable = encoder_enable;
     a.wc = wc; a.stride = stride; a.fine_scale = fine_scale; a.qscale = query_scale;
     a.expec_f = expec_f; a.mkq_f = mkpts_f; a.dbg_win = dbg_win; a.dbg_f3 = dbg_f3;

@@ -301,7 +301,7 @@ __global__ __launch_bounds__(NM * 256) OPHIP_WAVES_PER_SIMD(2, 2) void fine_refi
     char* stage = HH;
     float* scratch = reinterpret_cast<float*>(HH);
     const int k0 = NM * blockIdx.x;
-    const int total = *p.count;
+    const int total = min(*p.count, p.cap);           // a count above the lists' capacity refines the capacity's worth of matches
     if (k0 >= total) return;
     // waves: wave = 4 * tt + ft owns feature tile ft (features 32 ft .. 32 ft + 31) of match / token tile tt
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -581,7 +581,9 @@ __global__ __launch_bounds__(256) OPHIP_WAVES_PER_SIMD(2, 2) void fine_pair_kern
     const bool in1 = k0 + 1 < p.cap;
     const int b0 = (int)p.b_ids[k0], i30 = (int)p.i_ids[k0], j0 = (int)p.j_ids[k0];
     const int b1_ = in1 ? (int)p.b_ids[k0 + 1] : 0, i31_ = in1 ? (int)p.i_ids[k0 + 1] : 0, j1_ = in1 ? (int)p.j_ids[k0 + 1] : 0;
-    const int total = *p.count;
+    // clamped to the capacity: with an odd capacity and a count above it, row `cap` would otherwise be the live second match of the last
+    // workgroup and expec_f / mkpts_f / the debug rows would be written one row past the buffers
+    const int total = min(*p.count, p.cap);
     if (k0 >= total) return;
     const int tid = threadIdx.x, lane = tid & 63, ft = tid >> 6;
     const int r = lane & 31, h = lane >> 5;

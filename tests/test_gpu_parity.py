@@ -359,6 +359,32 @@ def test_coarse_match_vs_oracle(dev, B, N, hc, wc, nsplit, rtol):
     assert torch.equal(mk3.cpu(), ref["mkpts_3d_db"]) and torch.equal(mkc.cpu(), ref["mkpts_query_c"])
 
 
+@pytest.mark.parametrize("B,N,hc,wc", [(1, 300, 10, 13), (2, 129, 9, 9), (1, 1000, 30, 40)])
+def test_coarse_match_plain_bf16_like_for_like(dev, B, N, hc, wc):
+    """Plain bf16 (nsplit 1) against a float64 reference that rounds where the kernel rounds: operands bf16(f / 16) (frag_planes_kernel's hi
+    plane), products and sums in float64, times the kernel's own f32 factor 1 / float32(temperature + 1e-4), then the oracle's dual softmax
+    and selection.  A single GEMM has no rounded intermediates, so only f32 accumulation order is left and the bound is the split mode's own
+    (rtol 1e-3 / atol 1e-7 instead of test_coarse_match_vs_oracle's 0.5).  Measured on the MI355X: conf within 9.3e-6 / 2.1e-6 / 7.8e-6 relative (elements above 1e-6) at the three sizes,
+    mconf within 2.5e-6."""
+    from tests.bf16_faithful import bf16_round
+    f3, f2 = _planted_features(B, N, hc, wc, 3, min(N, hc * wc) // 2)
+    kp = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(4))
+    inv_temp = float(np.float32(1.0) / np.float32(0.08 + 1e-4))
+    sim = torch.einsum("nlc,nsc->nls", bf16_round(f3 * 0.0625).double(), bf16_round(f2 * 0.0625).double()) * inv_temp
+    ref_conf = torch.softmax(sim, 1) * torch.softmax(sim, 2)
+    ref = orc.coarse_match_select(ref_conf, (hc, wc), (hc * 8, wc * 8), kp, 0.1, 2)
+    conf, (b_ids, i_ids, j_ids), mconf, mk3, mkc = _coarse_match(dev, f3, f2, kp, wc, nsplit=1)
+    big = ref_conf > 1e-6
+    print(f"plain bf16 like for like: conf max rel err {((conf.cpu().double() - ref_conf).abs() / ref_conf)[big].max().item():.2e} (elements > 1e-6), "
+          f"mconf {((mconf.cpu().double() - ref['mconf']).abs() / ref['mconf']).max().item():.2e}")
+    assert len(ref["i_ids"]) > 10
+    for got, want in ((b_ids, ref["b_ids"]), (i_ids, ref["i_ids"]), (j_ids, ref["j_ids"])):
+        assert got.dtype == torch.int64 and torch.equal(got.cpu(), want)
+    close(conf.double(), ref_conf, rtol=1e-3, atol=1e-7, msg="conf_matrix")
+    close(mconf.double(), ref["mconf"], rtol=1e-3, atol=1e-7)
+    assert torch.equal(mk3.cpu(), ref["mkpts_3d_db"])
+
+
 @pytest.mark.parametrize("nsplit", [3, 1])
 @pytest.mark.parametrize("B,N,hc,wc", [(1, 300, 10, 13), (2, 129, 9, 9), (1, 1000, 30, 40), (1, 1408, 24, 32)])
 def test_coarse_match_tile_kernels_and_two_pass_form_agree(dev, monkeypatch, B, N, hc, wc, nsplit):
