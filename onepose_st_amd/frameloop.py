@@ -110,10 +110,18 @@ class SequenceRunner:
 
     Within a sequence frame t + 1's crop depends on frame t's pose, so frames are processed strictly in order; the next
     frame's upload is queued on a side stream while the current one is matched.
+
+    ``pnp="host"`` (the default): the matches are copied to the host and solved by ``pnp.ransac_PnP``.  ``pnp="device"``: the pose is
+    solved on the device from ``data["mkpts_3d_db"]`` / ``data["mkpts_query_f"]`` (``pnp_device.ransac_pnp``) and only pose, status and
+    inlier mask are read back; a frame whose status asks for more trials than ran falls back to the host call.  Box projection and
+    crop geometry stay on the host either way.
     """
 
     def __init__(self, model, object_block: dict, K, bbox3d, detector, crop_size: int = 512, pnp_reprojection_error: float = 7,
-                 pnp_scale: float = 1000, min_inliers: int = MIN_INLIERS, crop_fn=crop_query):
+                 pnp_scale: float = 1000, min_inliers: int = MIN_INLIERS, crop_fn=crop_query, pnp: str = "host"):
+        if pnp not in ("host", "device"):
+            raise ValueError(f"pnp={pnp!r}: 'host' or 'device'")
+        self.pnp = pnp
         self.model, self.block, self.crop_fn = model, object_block, crop_fn
         self.K, self.bbox3d, self.detector = np.asarray(K, np.float64), np.asarray(bbox3d, np.float64), detector
         self.crop_size, self.reproj, self.scale, self.min_inliers = crop_size, pnp_reprojection_error, pnp_scale, min_inliers
@@ -150,6 +158,12 @@ class SequenceRunner:
                     "descriptors3d_db": self.block["descriptors3d_db"], "descriptors3d_coarse_db": self.block["descriptors3d_coarse_db"]}
             with torch.no_grad():
                 self.model(data)
+            if self.pnp == "device":
+                pose, inliers, num_matches = self._device_pose(K_crop, data)
+                prev = (pose, inliers)
+                records.append({"pose": pose, "inliers": inliers, "bbox": bbox, "K_crop": K_crop, "trans": trans,
+                                "num_matches": num_matches, "redetected": bool(redetect)})
+                continue
             mk3d, mk2d = data["mkpts_3d_db"].cpu().numpy(), data["mkpts_query_f"].cpu().numpy()
             pose, _, inliers = ransac_PnP(K_crop, mk2d, mk3d, scale=self.scale, pnp_reprojection_error=self.reproj,
                                           img_hw=[self.crop_size, self.crop_size], use_pycolmap_ransac=True)
@@ -157,3 +171,14 @@ class SequenceRunner:
             records.append({"pose": pose, "inliers": inliers, "bbox": bbox, "K_crop": K_crop, "trans": trans,
                             "num_matches": int(mk2d.shape[0]), "redetected": bool(redetect)})
         return records
+
+    def _device_pose(self, K_crop, data):
+        """``pnp="device"``: the matches stay on the device; the read-back is pose, status and inlier mask"""
+        from . import pnp_device
+        mk3d, mk2d = data["mkpts_3d_db"].float().contiguous(), data["mkpts_query_f"].float().contiguous()
+        out = pnp_device.ransac_pnp(K_crop, mk2d, mk3d, scale=self.scale, pnp_reprojection_error=self.reproj)
+        (pose, _, inliers), = out.to_host()
+        if int(out.status_host[0]) & pnp_device.STATUS_NEEDS_MORE:          # the confidence asks for more trials than ran: the host's open-ended policy
+            pose, _, inliers = ransac_PnP(K_crop, mk2d.cpu().numpy(), mk3d.cpu().numpy(), scale=self.scale, pnp_reprojection_error=self.reproj,
+                                          img_hw=[self.crop_size, self.crop_size], use_pycolmap_ransac=True)
+        return pose, inliers, int(mk2d.shape[0])

@@ -1,0 +1,326 @@
+"""Device PnP: the pose of a frame from the matcher's device-side matches, without a host round trip (opt-in; ``pnp.ransac_PnP`` on the
+host stays the default).
+
+The float64 work is HIP (``csrc/pnp_device.hip`` in ``libonepose_pnp_device.so``, include/onepose_pnp_device.h).  Like the host solver
+this is the project's own estimator, not a restatement of pycolmap; only the ``use_pycolmap_ransac=True`` policy exists here: P3P
+samples, every root scored on every match, a fixed number of trials.  ``solver="dlt6"`` and the adaptive policy raise
+``NotImplementedError``; CPU tensors raise :class:`hip.HipLibraryError` (no CPU fallback).
+
+The specification (``tests/pnp_device_oracle.py`` restates it in numpy float64, one function per stage):
+
+1. ``ranges`` + ``prep``: a frame's rows ``[begin, end)`` by binary search in the ascending ``b_ids``; per row ``X = scale * pts3d``, the
+   pixel and ``ray = K^-1 (u, v, 1)`` in float64.  ``count`` is clamped to the capacity, rows at or beyond it are never read, a row whose
+   ``b_ids`` lies outside ``[0, frames)`` belongs to no frame.
+2. ``sample``: trial ``t`` of frame ``f`` draws ``k = 0, 1, 2`` with ``h = mix(seed + G * (((f << 32 | t) * 4 + k) + 1))`` (``G =
+   0x9E3779B97F4A7C15``, ``mix`` the splitmix64 finaliser, arithmetic mod 2^64); index ``k`` is ``h % (n - k)`` stepped past the earlier
+   picks in ascending order.  A frame of fewer than 4 rows runs no trials.
+3. ``p3p``: the host solver's ``p3p_poses`` (Grunert's quartic, Ferrari, three Newton steps, triangle alignment): up to four poses per
+   trial, the valid roots first in the solver's order, ``4 * trials`` slots per frame, unused slots NaN.
+4. ``score``: ``count_inliers``' expression on every row of the frame in row order: ``zc > 1e-12``, ``e2 < thr2``,
+   ``cost += e2 if inlier else thr2``.  A hypothesis with a non-finite entry: count 0, cost inf.
+5. ``select``: the winner under the total order (count descending, cost ascending, trial ascending, root ascending) among the
+   hypotheses with a count above 0; its inlier mask; status bit ``STATUS_NEEDS_MORE`` when the frame has at least 4 rows and the host's
+   ``needed_for(count) = ceil(log(1 - confidence) / log(1 - w^3))`` (1 when ``w^3 > 1 - 1e-12``, ``MAX_NEEDED`` when ``w^3 <= 1e-12`` or
+   above it) exceeds ``trials``.
+6. ``refine``: the host's ``finish``: ``refine_lm`` (lambda 1e-3, x 0.3 on an accepted step while above 1e-9, x 10 on a rejected one, at
+   most 8 tries per iteration, 20 iterations, stop at a relative cost decrease below 1e-12) on the masked rows, the inlier set
+   re-evaluated, a second round unless it is unchanged.  Fewer than 4 inliers: status ``STATUS_NO_POSE``, the identity pose, an empty
+   mask.  ``t`` is divided by ``scale``.
+
+Nothing is synchronised and the match count is never read on the host: every launch is sized by the capacity.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import cabi, hip
+
+_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+_LIB_PATH = os.environ.get("OPPNPD_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_pnp_device.so")      # OPPNPD_LIB: A/B builds
+_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_pnp_device.h")
+_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
+_SIGNATURES = {name: cabi.signature(proto) for name, proto in _HEADER.prototypes.items()}                  # the header is the one place
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+ABI_VERSION = _HEADER.defines.get("OPPNPD_ABI_VERSION")
+MAX_TRIALS = _HEADER.defines.get("OPPNPD_MAX_TRIALS")
+DEFAULT_TRIALS = _HEADER.defines.get("OPPNPD_DEFAULT_TRIALS")
+MAX_ROWS = _HEADER.defines.get("OPPNPD_MAX_ROWS")
+MAX_FRAMES = _HEADER.defines.get("OPPNPD_MAX_FRAMES")
+ROW_DOUBLES = _HEADER.defines.get("OPPNPD_ROW_DOUBLES")
+SELECT_BLOCK = _HEADER.defines.get("OPPNPD_SELECT_BLOCK")
+SCORE_CHUNK = _HEADER.defines.get("OPPNPD_SCORE_CHUNK")
+STATUS_NO_POSE = _HEADER.defines.get("OPPNPD_STATUS_NO_POSE")
+STATUS_NEEDS_MORE = _HEADER.defines.get("OPPNPD_STATUS_NEEDS_MORE")
+MIN_INLIERS = _HEADER.defines.get("OPPNPD_MIN_INLIERS")
+MAX_NEEDED = _HEADER.defines.get("OPPNPD_MAX_NEEDED")
+_lib = None
+
+
+def library_path() -> str:
+    return _LIB_PATH
+
+
+def load():
+    """Load (once) and return the ctypes handle of ``libonepose_pnp_device.so``"""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_LIB_PATH):
+            raise hip.HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
+        if not _HEADER.prototypes:
+            raise hip.HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
+        lib = ctypes.CDLL(_LIB_PATH)
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        if lib.oppnpd_abi_version() != ABI_VERSION:
+            raise hip.HipLibraryError(f"libonepose_pnp_device.so ABI version {lib.oppnpd_abi_version()}, this binding is written for {ABI_VERSION}")
+        _lib = lib
+    return _lib
+
+
+def check_arity(name: str, args) -> None:
+    """ctypes accepts surplus arguments silently, so the count is checked against the header's prototype"""
+    params = _HEADER.prototypes[name].params
+    if len(args) != len(params):
+        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
+
+
+def call(name: str, *args) -> None:
+    check_arity(name, args)
+    lib = load()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.oppnpd_last_error().decode(errors="replace")
+        if rc == -1:
+            raise ValueError(f"{name}: {msg}")
+        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
+
+
+def _stream(stream):
+    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else hip.stream_handle()
+
+
+def _check_policy(solver, use_pycolmap_ransac) -> None:
+    if solver not in (None, "p3p"):
+        raise NotImplementedError(f"solver={solver!r}: the device path implements P3P only (the host's pnp.ransac_PnP has the 6-point DLT)")
+    if not use_pycolmap_ransac:
+        raise NotImplementedError("the adaptive policy (use_pycolmap_ransac=False) exists on the host only: pnp.ransac_PnP")
+
+
+class _Inputs:
+    """The checked device tensors of one call"""
+
+    def __init__(self, K, pts_2d, pts_3d, count, b_ids, frames):
+        named = [("pts_2d", pts_2d), ("pts_3d", pts_3d)] + [(k, v) for k, v in (("K", K), ("count", count), ("b_ids", b_ids)) if isinstance(v, torch.Tensor)]
+        for name, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}: expected a tensor")
+        if not all(t.is_cuda for _, t in named):
+            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        dev = pts_2d.device
+        if pts_2d.dim() != 2 or pts_2d.shape[1] != 2 or pts_3d.dim() != 2 or pts_3d.shape[1] != 3 or pts_2d.shape[0] != pts_3d.shape[0]:
+            raise ValueError("pts_2d [cap, 2] and pts_3d [cap, 3] must have the same length")
+        if pts_2d.dtype != torch.float32 or pts_3d.dtype != torch.float32:
+            raise ValueError("pts_2d and pts_3d: float32")
+        self.frames = int(frames)
+        if not 1 <= self.frames <= MAX_FRAMES:
+            raise ValueError(f"frames: an integer in [1, {MAX_FRAMES}]")
+        n = pts_2d.shape[0]
+        if n > MAX_ROWS:
+            raise ValueError(f"at most {MAX_ROWS} rows")
+        if n == 0:                                          # the library wants a table of at least one row; the count says it is unused
+            pts_2d, pts_3d = torch.zeros(1, 2, dtype=torch.float32, device=dev), torch.zeros(1, 3, dtype=torch.float32, device=dev)
+            b_ids = None if b_ids is None else torch.zeros(1, dtype=torch.int64, device=dev)
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.cap = pts_2d.shape[0]
+        self.pts_2d, self.pts_3d = pts_2d.contiguous(), pts_3d.contiguous()
+        if count is None:
+            count = torch.full((1,), n, dtype=torch.int32, device=dev)
+        elif not isinstance(count, torch.Tensor):
+            count = torch.full((1,), int(count), dtype=torch.int32, device=dev)
+        if count.dtype != torch.int32 or count.numel() != 1:
+            raise ValueError("count: one int32 on the device")
+        self.count = count
+        if b_ids is None:
+            if self.frames != 1:
+                raise ValueError("frames > 1 needs b_ids")
+        elif b_ids.dtype != torch.int64 or tuple(b_ids.shape) != (self.cap,):
+            raise ValueError(f"b_ids: int64 [{self.cap}]")
+        self.b_ids = None if b_ids is None else b_ids.contiguous()
+        if not isinstance(K, torch.Tensor):
+            K = torch.as_tensor(np.asarray(K, dtype=np.float64), device=dev)
+        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        if K.shape[0] not in (1, self.frames):
+            raise ValueError(f"K: [3, 3] shared, or [{self.frames}, 3, 3]")
+        self.K, self.k_shared = K, int(K.shape[0] == 1)
+        self.dev = dev
+
+
+def _check_options(scale, reproj, confidence, trials):
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError("scale: a finite number > 0")
+    if not (math.isfinite(reproj) and reproj > 0):
+        raise ValueError("pnp_reprojection_error: a finite number > 0")
+    if not 0 < confidence < 1:
+        raise ValueError("confidence: in (0, 1)")
+    if int(trials) != trials or not 1 <= trials <= MAX_TRIALS:
+        raise ValueError(f"trials: an integer in [1, {MAX_TRIALS}]")
+
+
+class DevicePoses:
+    """What :func:`ransac_pnp` returns, on the device: ``pose [F, 3, 4]`` float64, ``n_inliers [F]`` and ``status [F]`` int32,
+    ``inlier_mask [cap]`` uint8 over the rows (``ranges [F, 2]``: the rows of every frame)."""
+
+    def __init__(self, pose, n_inliers, status, inlier_mask, ranges, keep=()):
+        self.pose, self.n_inliers, self.status, self.inlier_mask, self.ranges = pose, n_inliers, status, inlier_mask, ranges
+        self.status_host = None
+        self._keep = keep                                   # the inputs and the workspace stay referenced while the work may be queued
+
+    @property
+    def needs_more(self) -> torch.Tensor:
+        return (self.status & STATUS_NEEDS_MORE) != 0
+
+    def to_host(self):
+        """Per frame ``(pose [3, 4], pose_homo [4, 4], inliers int64)`` in ``pnp.ransac_PnP``'s shape (the inliers are row numbers
+        within the frame); a frame without a pose: the identity and an empty array.  The one read-back."""
+        F, cap = self.pose.shape[0], self.inlier_mask.shape[0]
+        packed = torch.cat([self.pose.reshape(-1).view(torch.uint8), self.status.view(torch.uint8), self.ranges.reshape(-1).view(torch.uint8),
+                            self.inlier_mask]).cpu().numpy()
+        o = 0
+        pose = packed[o:o + 96 * F].view(np.float64).reshape(F, 3, 4); o += 96 * F
+        status = packed[o:o + 4 * F].view(np.int32); o += 4 * F
+        ranges = packed[o:o + 8 * F].view(np.int32).reshape(F, 2); o += 8 * F
+        mask = packed[o:o + cap]
+        self.status_host = status.copy()                    # the status of every frame, read with the rest
+        out = []
+        for f in range(F):
+            b, e = int(ranges[f, 0]), int(ranges[f, 1])
+            ok = not (int(status[f]) & STATUS_NO_POSE)
+            p = pose[f].copy()
+            homo = np.concatenate([p, np.array([[0.0, 0.0, 0.0, 1.0]])], axis=0)
+            inl = np.nonzero(mask[b:e])[0].astype(np.int64) if ok else np.array([], dtype=np.int64)
+            out.append((p, homo, inl))
+        return out
+
+
+def ransac_pnp(K, pts_2d, pts_3d, *, count=None, b_ids=None, frames=1, scale=1, pnp_reprojection_error=5, confidence=0.99,
+               trials=DEFAULT_TRIALS, seed=1, stream=None, solver=None, use_pycolmap_ransac=True) -> DevicePoses:
+    """The module docstring's estimator on device tensors ``pts_2d [cap, 2]``, ``pts_3d [cap, 3]`` float32; ``count`` int32[1] on the
+    device (default: all rows), ``b_ids [cap]`` int64 ascending with ``frames`` frames (default: one frame); ``K [3, 3]`` shared or
+    ``[frames, 3, 3]``.  Everything is enqueued on ``stream`` (default: the current one); nothing is read back."""
+    _check_policy(solver, use_pycolmap_ransac)
+    _check_options(float(scale), float(pnp_reprojection_error), float(confidence), trials)
+    a = _Inputs(K, pts_2d, pts_3d, count, b_ids, frames)
+    F, cap, dev = a.frames, a.cap, a.dev
+    nbytes = load().oppnpd_workspace_bytes(cap, F, int(trials))
+    if nbytes == 0:
+        raise ValueError("frames x trials: too many hypotheses for one call")
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with ctx:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        pose = torch.empty(F, 3, 4, dtype=torch.float64, device=dev)
+        n_in = torch.zeros(F, dtype=torch.int32, device=dev)
+        status = torch.zeros(F, dtype=torch.int32, device=dev)
+        mask = torch.zeros(cap, dtype=torch.uint8, device=dev)
+        P = hip.ptr
+        call("oppnpd_solve", P(a.pts_2d), P(a.pts_3d), P(a.count, torch.int32), cap, P(a.b_ids, torch.int64), F, P(a.K, torch.float64), a.k_shared,
+             float(scale), float(pnp_reprojection_error), float(confidence), int(trials), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), P(ws, None),
+             nbytes, P(pose, torch.float64), P(n_in, torch.int32), P(status, torch.int32), P(mask, torch.uint8), _stream(stream))
+    ranges = ws[:8 * F].view(torch.int32).view(F, 2)       # the first table of the workspace
+    return DevicePoses(pose, n_in, status, mask, ranges, keep=(ws, a))
+
+
+def enqueue_after(pending_frame, K, **kw) -> DevicePoses:
+    """:func:`ransac_pnp` on a ``PendingFrame``'s own capacity-sized result buffers (``count``, ``b_ids``, ``mk3d``, ``mk2d``), before its
+    ``finish()``: the current stream is ordered behind the frame's last kernel and the solve is enqueued there.  The match count is not
+    read on the host.  ``frames`` defaults to the frame's batch size."""
+    pf = pending_frame
+    _check_policy(kw.get("solver"), kw.get("use_pycolmap_ransac", True))
+    if getattr(pf, "_slot", None) is not None:              # the one-call frame: its fine stage may be kept back or on its side stream
+        hip.call("ophip_frame_order_after_fine", hip.stream_handle())
+        bufs = pf.bufs if pf.bufs is not None else pf._block_views()
+    else:
+        torch.cuda.current_stream(pf.dev).wait_event(pf.event)
+        bufs = pf.bufs
+    mk2d = bufs["mkf"] if pf.fine_on and bufs.get("mkf") is not None else bufs["mkc"]
+    kw.setdefault("frames", pf.B)
+    out = ransac_pnp(K, mk2d, bufs["mk3d"], count=bufs["count"], b_ids=bufs["b_ids"], **kw)
+    out._keep = (*out._keep, bufs)
+    return out
+
+
+class stages:
+    """Thin wrappers over the per-stage entries (device tensors in, device tensors out); what ``oppnpd_solve`` enqueues in this order"""
+
+    @staticmethod
+    def ranges(b_ids, count, cap, frames, stream=None):
+        out = torch.empty(frames, 2, dtype=torch.int32, device=count.device)
+        call("oppnpd_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(frames), hip.ptr(out, torch.int32), _stream(stream))
+        return out
+
+    @staticmethod
+    def prep(K, pts_2d, pts_3d, count, b_ids, frames, scale=1.0, stream=None):
+        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        cap = pts_2d.shape[0]
+        rows = torch.zeros(cap, ROW_DOUBLES, dtype=torch.float64, device=pts_2d.device)
+        call("oppnpd_prep", hip.ptr(pts_2d), hip.ptr(pts_3d), hip.ptr(count, torch.int32), cap, hip.ptr(b_ids, torch.int64), int(frames),
+             hip.ptr(K, torch.float64), int(K.shape[0] == 1), float(scale), hip.ptr(rows, torch.float64), _stream(stream))
+        return rows
+
+    @staticmethod
+    def sample(ranges, trials, seed, stream=None):
+        F = ranges.shape[0]
+        out = torch.empty(F, trials, 3, dtype=torch.int32, device=ranges.device)
+        call("oppnpd_sample", hip.ptr(ranges, torch.int32), F, int(trials), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), hip.ptr(out, torch.int32),
+             _stream(stream))
+        return out
+
+    @staticmethod
+    def p3p(rows, ranges, samples, stream=None):
+        F, trials = samples.shape[0], samples.shape[1]
+        hyps = torch.empty(F, 4 * trials, 3, 4, dtype=torch.float64, device=rows.device)
+        nsol = torch.empty(F, trials, dtype=torch.int32, device=rows.device)
+        call("oppnpd_p3p", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(samples, torch.int32), rows.shape[0], F, trials,
+             hip.ptr(hyps, torch.float64), hip.ptr(nsol, torch.int32), _stream(stream))
+        return hyps, nsol
+
+    @staticmethod
+    def score(rows, ranges, K, hyps, reproj, stream=None):
+        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        F, H = hyps.shape[0], hyps.shape[1]
+        cnt = torch.empty(F, H, dtype=torch.int32, device=rows.device)
+        cost = torch.empty(F, H, dtype=torch.float64, device=rows.device)
+        call("oppnpd_score", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1),
+             hip.ptr(hyps, torch.float64), rows.shape[0], F, H, float(reproj), hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), _stream(stream))
+        return cnt, cost
+
+    @staticmethod
+    def select(cnt, cost, rows, ranges, count, K, hyps, reproj, confidence, trials, stream=None):
+        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        F, H, dev = hyps.shape[0], hyps.shape[1], rows.device
+        nblk = (H + SELECT_BLOCK - 1) // SELECT_BLOCK
+        partial = torch.empty(16 * F * nblk, dtype=torch.uint8, device=dev)
+        best, n_in, status = (torch.empty(F, dtype=torch.int32, device=dev) for _ in range(3))
+        mask = torch.zeros(rows.shape[0], dtype=torch.uint8, device=dev)
+        call("oppnpd_select", hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32),
+             hip.ptr(count, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1), hip.ptr(hyps, torch.float64), rows.shape[0], F, H,
+             float(reproj), float(confidence), int(trials), hip.ptr(partial, None), hip.ptr(best, torch.int32), hip.ptr(n_in, torch.int32),
+             hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), _stream(stream))
+        return best, n_in, status, mask
+
+    @staticmethod
+    def refine(rows, ranges, K, hyps, best, n_inliers, status, mask, reproj, scale=1.0, stream=None):
+        """Updates ``n_inliers``, ``status`` and ``mask`` in place; returns ``pose [F, 3, 4]``"""
+        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        F, H = hyps.shape[0], hyps.shape[1]
+        pose = torch.empty(F, 3, 4, dtype=torch.float64, device=rows.device)
+        call("oppnpd_refine", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1),
+             hip.ptr(hyps, torch.float64), hip.ptr(best, torch.int32), rows.shape[0], F, H, float(reproj), float(scale), hip.ptr(pose, torch.float64),
+             hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), _stream(stream))
+        return pose
