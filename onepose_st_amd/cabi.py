@@ -1,6 +1,6 @@
 """Reader of the project's C headers (``include/onepose_hip.h``, ``include/onepose_pnp.h``, ``include/onepose_sfm.h``,
 ``include/onepose_sfm_tracks.h``, ``include/onepose_sfm_triangulate.h``, ``include/onepose_sfm_fine.h``,
-``include/onepose_pnp_device.h``) and the one rule that turns a C type
+``include/onepose_pnp_device.h``, ``include/onepose_track.h``) and the one rule that turns a C type
 into a ctypes class.  The headers are the only place a C signature is written; ``hip.py`` and ``pnp.py`` bind from what this reads.
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
@@ -16,7 +16,7 @@ SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 RETURN_TYPES = (*SCALARS, "const char*", "void", "void*")
 _POINTEES = (*SCALARS, "char", "unsigned char", "void")
-_NAME = r"\b(?:ophip|oppnp|oppnpd|opsfm|opsft|opstr|opsff)_\w+"
+_NAME = r"\b(?:ophip|oppnp|oppnpd|opsfm|opsft|opstr|opsff|optrk)_\w+"
 
 
 class HeaderError(ValueError):

@@ -113,15 +113,33 @@ class SequenceRunner:
 
     ``pnp="host"`` (the default): the matches are copied to the host and solved by ``pnp.ransac_PnP``.  ``pnp="device"``: the pose is
     solved on the device from ``data["mkpts_3d_db"]`` / ``data["mkpts_query_f"]`` (``pnp_device.ransac_pnp``) and only pose, status and
-    inlier mask are read back; a frame whose status asks for more trials than ran falls back to the host call.  Box projection and
-    crop geometry stay on the host either way.
+    inlier mask are read back; a frame whose status asks for more trials than ran falls back to the host call.
+
+    ``track="host"`` (the default): the box of frame t + 1 is projected on the host from frame t's pose, so frame t + 1 is enqueued after
+    frame t's pose has been read.  ``track="device"`` (needs ``pnp="device"``): box, crop intrinsics and crop are computed on the device
+    from the device pose (``track_device``), and up to ``lookahead`` frames are enqueued before the oldest one's record is read (one
+    packed read-back per frame, queued with the frame).  The device marks the frames the host loop would not have projected a box for
+    (``track_device``'s flags); the frames enqueued past the first marked one are abandoned and the loop goes on from there as the host
+    loop would (the detector, or the host solver's pose), so the records and the detector calls do not depend on ``lookahead``.
+    ``crop_fn`` is not used then.  ``data`` also carries ``frame_index`` (host int) and ``crop_trans`` / ``K_crop`` (device float64
+    ``[3, 3]``); a ``model`` without ``enqueue`` is called as ``model(data)`` and may fill ``mkpts_query_f`` / ``mkpts_3d_db`` from those
+    without leaving the device.
     """
 
+    MAX_LOOKAHEAD = 8         # the one-call frame keeps 16 frames in flight at most
+
     def __init__(self, model, object_block: dict, K, bbox3d, detector, crop_size: int = 512, pnp_reprojection_error: float = 7,
-                 pnp_scale: float = 1000, min_inliers: int = MIN_INLIERS, crop_fn=crop_query, pnp: str = "host"):
+                 pnp_scale: float = 1000, min_inliers: int = MIN_INLIERS, crop_fn=crop_query, pnp: str = "host", track: str = "host",
+                 lookahead: int = 2):
         if pnp not in ("host", "device"):
             raise ValueError(f"pnp={pnp!r}: 'host' or 'device'")
-        self.pnp = pnp
+        if track not in ("host", "device"):
+            raise ValueError(f"track={track!r}: 'host' or 'device'")
+        if track == "device" and pnp != "device":
+            raise ValueError("track='device' needs pnp='device': the box is computed from the device pose")
+        if int(lookahead) != lookahead or not 1 <= lookahead <= self.MAX_LOOKAHEAD:
+            raise ValueError(f"lookahead: an integer in [1, {self.MAX_LOOKAHEAD}]")
+        self.pnp, self.track, self.lookahead = pnp, track, int(lookahead)
         self.model, self.block, self.crop_fn = model, object_block, crop_fn
         self.K, self.bbox3d, self.detector = np.asarray(K, np.float64), np.asarray(bbox3d, np.float64), detector
         self.crop_size, self.reproj, self.scale, self.min_inliers = crop_size, pnp_reprojection_error, pnp_scale, min_inliers
@@ -140,6 +158,8 @@ class SequenceRunner:
 
     def run(self, frames):
         frames = list(frames)
+        if self.track == "device":
+            return self._run_device_tracked(frames)
         records = []
         nxt = self._upload(frames[0]) if frames else None
         prev = None                                   # (pose, inliers) of the previous frame
@@ -182,3 +202,102 @@ class SequenceRunner:
             pose, _, inliers = ransac_PnP(K_crop, mk2d.cpu().numpy(), mk3d.cpu().numpy(), scale=self.scale, pnp_reprojection_error=self.reproj,
                                           img_hw=[self.crop_size, self.crop_size], use_pycolmap_ransac=True)
         return pose, inliers, int(mk2d.shape[0])
+
+    # ---- track="device" ------------------------------------------------------------------------------------------------------------------
+    def _enqueue_tracked(self, t, frame_dev, state):
+        """Crop, matcher, pose and the next frame's state of frame ``t``, and the packed read-back into pinned memory: all enqueued on the
+        current stream, nothing read.  -> the in-flight entry"""
+        from . import pnp_device, track_device
+        data = {"query_image": track_device.crop(frame_dev, state, self.crop_size), "keypoints3d": self.block["keypoints3d"],
+                "descriptors3d_db": self.block["descriptors3d_db"], "descriptors3d_coarse_db": self.block["descriptors3d_coarse_db"],
+                "frame_index": t, "crop_trans": state.trans, "K_crop": state.K_crop}
+        kw = dict(scale=self.scale, pnp_reprojection_error=self.reproj)
+        pend = None
+        with torch.no_grad():
+            if hasattr(self.model, "enqueue"):
+                pend = self.model.enqueue(data)
+                poses = pnp_device.enqueue_after(pend, state.K_crop, **kw)
+            else:
+                self.model(data)
+                poses = pnp_device.ransac_pnp(state.K_crop, data["mkpts_query_f"].float().contiguous(), data["mkpts_3d_db"].float().contiguous(), **kw)
+        nxt = track_device.next_box(poses, state, self._K_dev, self._bbox3d_dev, min_inliers=self.min_inliers, crop_size=self.crop_size)
+        packed = poses.pack(extra=(state.blob, nxt.flag.view(torch.uint8)))
+        pool = self._pins.setdefault(packed.numel(), [])
+        pin = pool.pop() if pool else torch.empty(packed.numel(), dtype=torch.uint8).pin_memory()
+        pin.copy_(packed, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return {"t": t, "state": state, "next": nxt, "data": data, "pend": pend, "poses": poses, "pin": pin, "event": ev}
+
+    def _release(self, entry, abandon=False):
+        if abandon and entry["pend"] is not None:
+            entry["pend"].close()
+        pool = self._pins.setdefault(entry["pin"].numel(), [])
+        if len(pool) < 2 * self.MAX_LOOKAHEAD:      # copies into a reused buffer are ordered by the stream; the host reads behind its own event
+            pool.append(entry["pin"])
+
+    def _host_pose(self, K_crop, data):
+        mk3d, mk2d = data["mkpts_3d_db"].float().cpu().numpy(), data["mkpts_query_f"].float().cpu().numpy()
+        pose, _, inliers = ransac_PnP(K_crop, mk2d, mk3d, scale=self.scale, pnp_reprojection_error=self.reproj,
+                                      img_hw=[self.crop_size, self.crop_size], use_pycolmap_ransac=True)
+        return pose, inliers
+
+    def _run_device_tracked(self, frames):
+        from collections import deque
+
+        from . import pnp_device, track_device
+        if self.device.type != "cuda":
+            raise hip.HipLibraryError("track='device' needs the object block on the HIP device (no CPU fallback)")
+        self._K_dev = torch.as_tensor(np.ascontiguousarray(self.K[:3, :3])).to(self.device)
+        self._bbox3d_dev = torch.as_tensor(np.ascontiguousarray(self.bbox3d.reshape(8, 3))).to(self.device)
+        self._pins = {}
+        n, records, uploads, queue = len(frames), [], {}, deque()
+        t_next, state, redetected = 0, None, {}             # state None: the host loop would call the detector for frame t_next
+        while len(records) < n:
+            while len(queue) < self.lookahead and t_next < n:
+                t = t_next
+                for k in (t, t + 1):
+                    if k < n and k not in uploads:
+                        uploads[k] = self._upload(frames[k])
+                if state is None:                           # frame 0 and the frame after a lost one: the queue is empty here
+                    bbox = np.asarray(self.detector(frames[t], t)).astype(np.int32)
+                    state, redetected[t] = track_device.set_box(bbox, self._K_dev, self.crop_size), True
+                frame_dev, ev = uploads[t]
+                if ev is not None:
+                    torch.cuda.current_stream().wait_event(ev)
+                entry = self._enqueue_tracked(t, frame_dev, state)
+                queue.append(entry)
+                state, t_next = entry["next"], t + 1
+            e = queue.popleft()
+            t, data, rerun = e["t"], e["data"], False
+            if e["pend"] is not None:
+                before = getattr(self.model, "lazy_reruns", 0)
+                e["pend"].finish()
+                rerun = getattr(self.model, "lazy_reruns", 0) != before
+            e["event"].synchronize()                        # the frame's one read-back, queued with the frame
+            ((pose, _, inliers),), (raw_state, raw_flag) = e["poses"].unpack(e["pin"].numpy(), (track_device.STATE_BYTES, 4))
+            status, next_flag = int(e["poses"].status_host[0]), int(raw_flag.view(np.int32)[0])
+            bbox, _, K_crop, trans = track_device.TrackState.unpack(raw_state)
+            self._release(e)
+            host_step = rerun or bool(status & pnp_device.STATUS_NEEDS_MORE)
+            if rerun:                                       # finish() ran the frame again: the early solve saw the abandoned run's buffers
+                out = pnp_device.ransac_pnp(e["state"].K_crop, data["mkpts_query_f"].float().contiguous(), data["mkpts_3d_db"].float().contiguous(),
+                                            scale=self.scale, pnp_reprojection_error=self.reproj)
+                (pose, _, inliers), = out.to_host()
+                status = int(out.status_host[0])
+            if status & pnp_device.STATUS_NEEDS_MORE:       # the host's open-ended policy replaces the pose, as in the host-tracked loop
+                pose, inliers = self._host_pose(K_crop, data)
+            records.append({"pose": pose, "inliers": inliers, "bbox": bbox, "K_crop": K_crop, "trans": trans,
+                            "num_matches": int(data["mkpts_3d_db"].shape[0]), "redetected": bool(redetected.pop(t, False))})
+            uploads.pop(t, None)
+            if not host_step and next_flag == 0:
+                continue
+            # rewind: what was enqueued past this frame used a box the host loop would not have used
+            while queue:
+                self._release(queue.popleft(), abandon=True)
+            t_next, state = t + 1, None
+            if host_step and len(inliers) >= self.min_inliers:      # the pose changed on the host: its box, as the host loop computes it
+                nb = project_bbox(self.K, pose, self.bbox3d)
+                if nb[2] > nb[0] and nb[3] > nb[1]:
+                    state = track_device.set_box(nb, self._K_dev, self.crop_size)
+        return records

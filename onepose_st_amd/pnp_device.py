@@ -186,17 +186,21 @@ class DevicePoses:
     def needs_more(self) -> torch.Tensor:
         return (self.status & STATUS_NEEDS_MORE) != 0
 
-    def to_host(self):
-        """Per frame ``(pose [3, 4], pose_homo [4, 4], inliers int64)`` in ``pnp.ransac_PnP``'s shape (the inliers are row numbers
-        within the frame); a frame without a pose: the identity and an empty array.  The one read-back."""
+    def pack(self, extra=()) -> torch.Tensor:
+        """One uint8 device tensor for one read-back: pose, status, ranges, the inlier mask, then every 1-D uint8 device tensor of
+        ``extra`` (what a caller wants read with the pose); :meth:`unpack` reads it on the host"""
+        return torch.cat([self.pose.reshape(-1).view(torch.uint8), self.status.view(torch.uint8), self.ranges.reshape(-1).view(torch.uint8),
+                          self.inlier_mask, *extra])
+
+    def unpack(self, packed, extra_sizes=()):
+        """:meth:`to_host`'s result from the host bytes of :meth:`pack` (a uint8 numpy array); with ``extra_sizes`` a pair of that and the
+        byte arrays of the extras"""
         F, cap = self.pose.shape[0], self.inlier_mask.shape[0]
-        packed = torch.cat([self.pose.reshape(-1).view(torch.uint8), self.status.view(torch.uint8), self.ranges.reshape(-1).view(torch.uint8),
-                            self.inlier_mask]).cpu().numpy()
         o = 0
         pose = packed[o:o + 96 * F].view(np.float64).reshape(F, 3, 4); o += 96 * F
         status = packed[o:o + 4 * F].view(np.int32); o += 4 * F
         ranges = packed[o:o + 8 * F].view(np.int32).reshape(F, 2); o += 8 * F
-        mask = packed[o:o + cap]
+        mask = packed[o:o + cap]; o += cap
         self.status_host = status.copy()                    # the status of every frame, read with the rest
         out = []
         for f in range(F):
@@ -206,7 +210,17 @@ class DevicePoses:
             homo = np.concatenate([p, np.array([[0.0, 0.0, 0.0, 1.0]])], axis=0)
             inl = np.nonzero(mask[b:e])[0].astype(np.int64) if ok else np.array([], dtype=np.int64)
             out.append((p, homo, inl))
-        return out
+        if not extra_sizes:
+            return out
+        extras = []
+        for n in extra_sizes:
+            extras.append(packed[o:o + n].copy()); o += n
+        return out, extras
+
+    def to_host(self):
+        """Per frame ``(pose [3, 4], pose_homo [4, 4], inliers int64)`` in ``pnp.ransac_PnP``'s shape (the inliers are row numbers
+        within the frame); a frame without a pose: the identity and an empty array.  The one read-back."""
+        return self.unpack(self.pack().cpu().numpy())
 
 
 def ransac_pnp(K, pts_2d, pts_3d, *, count=None, b_ids=None, frames=1, scale=1, pnp_reprojection_error=5, confidence=0.99,
