@@ -1,7 +1,7 @@
-"""Reader of the project's C headers (``include/onepose_hip.h``, ``include/onepose_pnp.h``, ``include/onepose_sfm.h``,
-``include/onepose_sfm_tracks.h``, ``include/onepose_sfm_triangulate.h``, ``include/onepose_sfm_fine.h``,
-``include/onepose_pnp_device.h``, ``include/onepose_track.h``) and the one rule that turns a C type
-into a ctypes class.  The headers are the only place a C signature is written; ``hip.py`` and ``pnp.py`` bind from what this reads.
+"""Reader of the project's C headers (``include/onepose_*.h``: one per entry of ``LIBRARIES`` below, plus ``onepose_pnp.h`` of the host
+library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures and the loaded handle of one
+HIP library.  The headers are the only place a C signature is written; the modules ``LIBRARIES`` names and ``pnp.py`` bind from what
+this reads.
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -9,17 +9,34 @@ from __future__ import annotations
 
 import ctypes
 import itertools
+import os
 import re
 from collections import namedtuple
+
+# The HIP libraries, one line each: C prefix, header under include/, file under onepose_st_amd/lib/, the environment variable that names
+# another build of it (A/B runs), the module that binds it.  __graft_entry__.build() checks and loads every entry, the reader below knows
+# an entry point by these prefixes, and DESIGN.md section 1b says what else a new one needs.
+Library = namedtuple("Library", "prefix header so env module")
+LIBRARIES = (Library("ophip", "onepose_hip.h", "libonepose_hip.so", "OPHIP_LIB", "hip"),
+             Library("opsfm", "onepose_sfm.h", "libonepose_sfm.so", "OPSFM_LIB", "sfm_objectblock"),
+             Library("opsft", "onepose_sfm_tracks.h", "libonepose_sfm_tracks.so", "OPSFT_LIB", "sfm_tracks"),
+             Library("opstr", "onepose_sfm_triangulate.h", "libonepose_sfm_triangulate.so", "OPSTR_LIB", "sfm_triangulate"),
+             Library("opsff", "onepose_sfm_fine.h", "libonepose_sfm_fine.so", "OPSFF_LIB", "sfm_fine"),
+             Library("oppnpd", "onepose_pnp_device.h", "libonepose_pnp_device.so", "OPPNPD_LIB", "pnp_device"),
+             Library("optrk", "onepose_track.h", "libonepose_track.so", "OPTRK_LIB", "track_device"))
 
 SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 RETURN_TYPES = (*SCALARS, "const char*", "void", "void*")
 _POINTEES = (*SCALARS, "char", "unsigned char", "void")
-_NAME = r"\b(?:ophip|oppnp|oppnpd|opsfm|opsft|opstr|opsff|optrk)_\w+"
+_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp'])})_\w+"          # oppnp: the host library (pnp.py)
 
 
 class HeaderError(ValueError):
+    pass
+
+
+class HipLibraryError(RuntimeError):
     pass
 
 
@@ -114,3 +131,73 @@ def check_mirror(mirror, struct_name: str, fields: tuple):
     for k, (w, g) in enumerate(itertools.zip_longest(want, got)):
         if w != g:
             raise HeaderError(f"{struct_name}.{(w or g)[0]}: field {k} is {w and w[1:]} in the header, {g and g[1:]} in {mirror.__name__}")
+
+
+class Binding:
+    """One HIP library bound from its header: ``header`` (an empty parse when the file is missing, and ``load()`` says so),
+    ``signatures`` (name -> (restype, argtypes)), ``exported_symbols``, ``abi_version`` (the header's ``<PREFIX>_ABI_VERSION``), ``path``
+    (the environment variable ``env``, read once here, or ``lib/<so>``) and ``handle`` (``None`` until ``load()``)."""
+
+    def __init__(self, header: str, so: str, prefix: str, env: str, mirrors: dict | None = None):
+        pkg = os.path.dirname(os.path.abspath(__file__))
+        self.so, self.prefix = so, prefix
+        self.path = os.environ.get(env) or os.path.join(pkg, "lib", so)
+        self.header_path = os.path.join(os.path.dirname(pkg), "include", header)         # where csrc/Makefile finds it too
+        self.header = parse(open(self.header_path).read() if os.path.exists(self.header_path) else "")
+        self.signatures = {name: signature(proto, mirrors) for name, proto in self.header.prototypes.items()}
+        self.exported_symbols = tuple(self.signatures)
+        self.abi_version = self.header.defines.get(f"{prefix.upper()}_ABI_VERSION")
+        self.handle = None
+        self._params = {name: proto.params for name, proto in self.header.prototypes.items()}
+        self._last_error = f"{prefix}_last_error"
+
+    @classmethod
+    def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
+        """The binding of the ``LIBRARIES`` entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES if e.module == module.rpartition(".")[2]]
+        return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors)
+
+    def library_path(self) -> str:
+        return self.path
+
+    def load(self):
+        """Load (once) and return the ctypes handle; raises ``HipLibraryError`` when the library or its header is missing or their ABI
+        versions differ -- build it with ``python -c 'import __graft_entry__ as g; g.build()'``."""
+        if self.handle is not None:
+            return self.handle
+        if not os.path.exists(self.path):
+            raise HipLibraryError(f"{self.path} not found: the HIP extension is not built (run __graft_entry__.build())")
+        if not self.header.prototypes:
+            raise HipLibraryError(f"{self.header_path} not found: the binding takes every C signature from that header")
+        lib = ctypes.CDLL(self.path)
+        for name, (res, args) in self.signatures.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        built = getattr(lib, f"{self.prefix}_abi_version")()
+        if built != self.abi_version:
+            raise HipLibraryError(f"{self.so} ABI version {built}, this binding is written for {self.abi_version} "
+                                  f"({self.header_path} {self.prefix.upper()}_ABI_VERSION): rebuild with __graft_entry__.build()")
+        self.handle = lib
+        return lib
+
+    def check_arity(self, name: str, args) -> None:
+        """ctypes accepts surplus arguments silently (a stream handle one slot late would reach C), so the count is checked against
+        the header's prototype"""
+        params = self._params[name]
+        if len(args) != len(params):
+            raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
+
+    def call(self, name: str, *args) -> None:
+        """Call an entry point that returns a status and raise on failure: -1 (a rejected argument) -> ``ValueError``, any other
+        non-zero status -> ``RuntimeError``, both with the library's ``<prefix>_last_error()``.  The arity check comes first."""
+        if len(args) != len(self._params[name]):
+            self.check_arity(name, args)
+        lib = self.handle
+        if lib is None:
+            lib = self.load()
+        rc = getattr(lib, name)(*args)
+        if rc != 0:
+            msg = getattr(lib, self._last_error)().decode(errors="replace")
+            if rc == -1:
+                raise ValueError(f"{name}: {msg}")
+            raise RuntimeError(f"{name} failed (rc={rc}): {msg}")

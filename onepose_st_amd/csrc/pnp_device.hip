@@ -16,8 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "onepose_pnp_device.h"
+#include "capi_error.h"
+
+using capi::bad_arg;
+using capi::blocks_of;
+using capi::fail;
+using capi::g_error;
 
 #pragma clang fp contract(off)
 
@@ -29,26 +34,6 @@ constexpr int kChunk = OPPNPD_SCORE_CHUNK;
 constexpr int kSelBlock = OPPNPD_SELECT_BLOCK;
 constexpr int kSums = 27;                         // 21 entries of the upper triangle of J^T J and 6 of the gradient
 constexpr int kMinIn = OPPNPD_MIN_INLIERS;
-
-thread_local char g_error[256] = "";
-
-int fail(hipError_t e, const char* where) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, hipGetErrorString(e));
-    return (int)e > 0 ? (int)e : 1;
-}
-
-int bad_arg(const char* where, const char* what) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, what);
-    return -1;
-}
-
-#define OPPNPD_CHECK_LAUNCH()                                  \
-    do {                                                       \
-        hipError_t e__ = hipGetLastError();                    \
-        if (e__ != hipSuccess) return fail(e__, __func__);     \
-    } while (0)
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 struct Intr { double fx, sk, cx, fy, cy; };
 
@@ -708,7 +693,7 @@ int oppnpd_ranges(const long long* b_ids, const int* count, int cap, int F, int*
     if (!count || !ranges) return bad_arg(__func__, "null pointer");
     if (!b_ids && F != 1) return bad_arg(__func__, "b_ids = NULL means one frame");
     ranges_kernel<<<blocks_of(F, kThreads), kThreads, 0, (hipStream_t)stream>>>(b_ids, count, cap, F, ranges);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -719,7 +704,7 @@ int oppnpd_prep(const float* pts2d, const float* pts3d, const int* count, int ca
     if (!b_ids && F != 1) return bad_arg(__func__, "b_ids = NULL means one frame");
     if (!(isfinite(scale) && scale > 0.0)) return bad_arg(__func__, "scale: a finite number > 0");
     prep_kernel<<<blocks_of(cap, kThreads), kThreads, 0, (hipStream_t)stream>>>(pts2d, pts3d, count, cap, b_ids, F, K, k_shared, scale, rows);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -727,7 +712,7 @@ int oppnpd_sample(const int* ranges, int F, int trials, unsigned long long seed,
     if (F < 1 || F > OPPNPD_MAX_FRAMES || trials < 1 || trials > OPPNPD_MAX_TRIALS || !hyps_ok(F, 4ll * trials)) return bad_arg(__func__, "table sizes");
     if (!ranges || !samples) return bad_arg(__func__, "null pointer");
     sample_kernel<<<dim3(blocks_of(trials, kThreads), F), kThreads, 0, (hipStream_t)stream>>>(ranges, OPPNPD_MAX_ROWS, F, trials, (uint64_t)seed, samples);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -735,7 +720,7 @@ int oppnpd_p3p(const double* rows, const int* ranges, const int* samples, int ca
     if (!sizes_ok(cap, F) || trials < 1 || trials > OPPNPD_MAX_TRIALS || !hyps_ok(F, 4ll * trials)) return bad_arg(__func__, "table sizes");
     if (!rows || !ranges || !samples || !hyps || !nsol) return bad_arg(__func__, "null pointer");
     p3p_kernel<<<dim3(blocks_of(trials, kThreads), F), kThreads, 0, (hipStream_t)stream>>>(rows, ranges, samples, cap, F, trials, hyps, nsol);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -746,7 +731,7 @@ int oppnpd_score(const double* rows, const int* ranges, const double* K, int k_s
     if (!thr_ok(reproj_err_px)) return bad_arg(__func__, "reproj_err_px: a finite number > 0");
     score_kernel<<<dim3(blocks_of(H, kThreads), F), kThreads, 0, (hipStream_t)stream>>>(rows, ranges, K, k_shared, hyps, cap, F, H,
                                                                                       reproj_err_px * reproj_err_px, cnt, cost);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -761,12 +746,12 @@ int oppnpd_select(const int* cnt, const double* cost, const double* rows, const 
     const int nblk = (int)blocks_of(H, kSelBlock);
     hipStream_t S = (hipStream_t)stream;
     select_partial_kernel<<<dim3(nblk, F), kThreads, 0, S>>>(cnt, cost, F, H, nblk, (Best*)partial);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     mask_clear_kernel<<<blocks_of(cap, kThreads), kThreads, 0, S>>>(count, cap, inlier_mask);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     select_final_kernel<<<F, kThreads, 0, S>>>((const Best*)partial, nblk, rows, ranges, K, k_shared, hyps, cap, F, H, reproj_err_px * reproj_err_px,
                                                confidence, trials, best, n_inliers, status, inlier_mask);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -778,7 +763,7 @@ int oppnpd_refine(const double* rows, const int* ranges, const double* K, int k_
     if (!(isfinite(scale) && scale > 0.0)) return bad_arg(__func__, "scale: a finite number > 0");
     refine_kernel<<<F, kThreads, 0, (hipStream_t)stream>>>(rows, ranges, K, k_shared, hyps, best, cap, F, H, reproj_err_px * reproj_err_px, scale, pose,
                                                            n_inliers, status, inlier_mask);
-    OPPNPD_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 

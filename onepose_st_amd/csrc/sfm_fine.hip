@@ -14,30 +14,16 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "onepose_sfm_fine.h"
+#include "capi_error.h"
+
+using capi::bad_arg;
+using capi::fail;
+using capi::g_error;
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-thread_local char g_error[256] = "";
-
-int fail(hipError_t e, const char* where) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, hipGetErrorString(e));
-    return (int)e > 0 ? (int)e : 1;
-}
-
-int bad_arg(const char* where, const char* what) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, what);
-    return -1;
-}
-
-#define OPSFF_CHECK_LAUNCH()                                   \
-    do {                                                       \
-        hipError_t e__ = hipGetLastError();                    \
-        if (e__ != hipSuccess) return fail(e__, __func__);     \
-    } while (0)
 
 __device__ __forceinline__ float rint_t(float v) { return rintf(v); }          // torch.round / nearbyint: half to even
 __device__ __forceinline__ double rint_t(double v) { return rint(v); }
@@ -212,7 +198,7 @@ extern "C" int opsff_row_ids(const void* mkpts0, int mk0_double, const void* mkp
         return bad_arg(__func__, "null pointer");
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(init_ctrl_kernel, dim3(1), dim3(64), 0, stream, ctrl);
-    OPSFF_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     if (M == 0) return 0;
     IdsArgs a{{mkpts0, mkpts1}, {mkpts0_out, mkpts1_out}, {row_left, row_right}, image_hw, image_scale, {i_ids, j_ids}, ctrl, M, I, coarse_scale};
     const dim3 grid((unsigned)((2 * M + 255) / 256));
@@ -220,7 +206,7 @@ extern "C" int opsff_row_ids(const void* mkpts0, int mk0_double, const void* mkp
     else if (mk0_double) hipLaunchKernelGGL((row_ids_kernel<double, float>), grid, dim3(256), 0, stream, a);
     else if (mk1_double) hipLaunchKernelGGL((row_ids_kernel<float, double>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((row_ids_kernel<float, float>), grid, dim3(256), 0, stream, a);
-    OPSFF_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -256,6 +242,6 @@ extern "C" int opsff_sample_rows(const float* coarse0, long long coarse0_bstride
     a.I = I;
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)n), dim3(256), 0, stream, a);      // 4 n waves, 4 per workgroup
-    OPSFF_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }

@@ -20,9 +20,14 @@
 // Sorting, scans and compaction of the integer tables between these launches are the caller's (sfm_objectblock.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <math.h>
 #include "onepose_sfm.h"
+#include "capi_error.h"
+
+using capi::bad_arg;
+using capi::blocks_of;
+using capi::fail;
+using capi::g_error;
 
 namespace {
 
@@ -31,26 +36,6 @@ constexpr int kPerThread = 4;                     // points a thread of the pair
 constexpr int kTile = OPSFM_PAIR_TILE;            // partners staged in LDS at a time
 static_assert(kThreads * kPerThread == OPSFM_PAIR_BLOCK, "a workgroup's points");
 static_assert(kTile == kThreads, "thread t stages partner t of the tile");
-
-thread_local char g_error[256] = "";
-
-int fail(hipError_t e, const char* where) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, hipGetErrorString(e));
-    return (int)e > 0 ? (int)e : 1;
-}
-
-int bad_arg(const char* where, const char* what) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, what);
-    return -1;
-}
-
-#define OPSFM_CHECK_LAUNCH()                                   \
-    do {                                                       \
-        hipError_t e__ = hipGetLastError();                    \
-        if (e__ != hipSuccess) return fail(e__, __func__);     \
-    } while (0)
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ---- stage A -----------------------------------------------------------------------------------------------------------------------------
 struct TrackTables {
@@ -322,7 +307,7 @@ extern "C" int opsfm_aggregate(const long long* assigned_image, const long long*
     hipLaunchKernelGGL(agg_winner_kernel, dim3(blocks_of(W, kThreads)), dim3(kThreads), 0, stream, t, winner, scores_cleared);
     hipLaunchKernelGGL(agg_write_kernel, dim3(blocks_of(W, kThreads / 64)), dim3(kThreads), 0, stream, t, winner, feature_c0, feature_c1,
                        feature0, feature1, dim_c, dim_f, desc_coarse, desc_fine, written);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -330,7 +315,7 @@ extern "C" int opsfm_box_test(const double* xyz, long long Q, const double* corn
     if (!xyz || !corners || !keep) return bad_arg(__func__, "null pointer");
     if (Q < 1 || Q > OPSFM_MAX_ITEMS) return bad_arg(__func__, "bad sizes");
     hipLaunchKernelGGL(box_test_kernel, dim3(blocks_of(Q, kThreads)), dim3(kThreads), 0, (hipStream_t)stream_, xyz, Q, corners, keep);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -340,7 +325,7 @@ extern "C" int opsfm_pair_count(const double* xyz, int N, double dist_threshold,
     if (!pair_sizes_ok(N, chunk_len, n_chunks) || !(dist_threshold > 0.0)) return bad_arg(__func__, "bad sizes");
     hipLaunchKernelGGL(pair_kernel<false>, dim3(blocks_of(N, OPSFM_PAIR_BLOCK), n_chunks), dim3(kThreads), 0, (hipStream_t)stream_, xyz, N,
                        dist_threshold, chunk_len, n_chunks, counts, (const long long*)nullptr, (int*)nullptr, 0LL);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -350,7 +335,7 @@ extern "C" int opsfm_pair_emit(const double* xyz, int N, double dist_threshold, 
     if (!pair_sizes_ok(N, chunk_len, n_chunks) || !(dist_threshold > 0.0) || E < N) return bad_arg(__func__, "bad sizes");
     hipLaunchKernelGGL(pair_kernel<true>, dim3(blocks_of(N, OPSFM_PAIR_BLOCK), n_chunks), dim3(kThreads), 0, (hipStream_t)stream_, xyz, N,
                        dist_threshold, chunk_len, n_chunks, (long long*)nullptr, positions, neighbours, E);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -365,7 +350,7 @@ extern "C" int opsfm_merge_resolve(const long long* positions, int n_chunks, con
     hipError_t e = hipMemsetAsync(recorded, 0, (size_t)N, stream);
     if (e != hipSuccess) return fail(e, __func__);
     hipLaunchKernelGGL(merge_resolve_kernel, dim3(1), dim3(64), 0, stream, positions, n_chunks, neighbours, multi, M, N, recorded, accepted);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -377,7 +362,7 @@ extern "C" int opsfm_group_emit(const double* xyz, const long long* ids, const l
     if (G < 1 || N < G || n_chunks < 1 || members_total < G) return bad_arg(__func__, "bad sizes");
     hipLaunchKernelGGL(group_emit_kernel, dim3(blocks_of(G, kThreads)), dim3(kThreads), 0, (hipStream_t)stream_, xyz, ids, accepted_idx,
                        positions, n_chunks, neighbours, group_offsets, G, N, keypoints3d, group_members, members_total);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -387,6 +372,6 @@ extern "C" int opsfm_point_mean(const float* table, long long U, int dim, const 
     if (U < 1 || dim < 1 || G < 1) return bad_arg(__func__, "bad sizes");
     hipLaunchKernelGGL(point_mean_kernel, dim3(blocks_of(G, kThreads / 64)), dim3(kThreads), 0, (hipStream_t)stream_, table, U, dim, obs,
                        run_offsets, G, out);
-    OPSFM_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }

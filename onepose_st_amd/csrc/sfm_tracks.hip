@@ -21,8 +21,13 @@
 // Seeded faults for the tests (tools/build_variant.sh sfm_tracks, EXTRA=-DOPSFT_FAULT_...): never defined in the product build.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "onepose_sfm_tracks.h"
+#include "capi_error.h"
+
+using capi::bad_arg;
+using capi::blocks_of;
+using capi::fail;
+using capi::g_error;
 
 namespace {
 
@@ -31,26 +36,6 @@ constexpr int kSelectThreads = OPSFT_MAX_IMAGES;  // one remaining image per thr
 constexpr int kLanesPerSlot = 16;                 // lanes that walk one slot's track (the mean track is ~20 elements)
 constexpr int kMaxTakeBlocks = 2048;
 static_assert(kSelectThreads <= 1024, "one workgroup");
-
-thread_local char g_error[256] = "";
-
-int fail(hipError_t e, const char* where) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, hipGetErrorString(e));
-    return (int)e > 0 ? (int)e : 1;
-}
-
-int bad_arg(const char* where, const char* what) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, what);
-    return -1;
-}
-
-#define OPSFT_CHECK_LAUNCH()                                   \
-    do {                                                       \
-        hipError_t e__ = hipGetLastError();                    \
-        if (e__ != hipSuccess) return fail(e__, __func__);     \
-    } while (0)
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ---- the greedy rounds -----------------------------------------------------------------------------------------------------------------
 // Python's sorted(items, key=count, reverse=True) is stable and the sorted dict is carried into the next round: the rank of the image at
@@ -325,7 +310,7 @@ int opsft_assign(const long long* kpt_offsets, const long long* slot_point, cons
         take_kernel<<<take_blocks, kThreads, 0, s>>>(t, state, count, assigned_image, assigned_kpt, ctrl);
     }
     select_kernel<<<1, kSelectThreads, 0, s>>>(count, order, keyframes, ctrl, I);      // sets the done flag after the I-th keyframe
-    OPSFT_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -335,7 +320,7 @@ int opsft_finish(const int* state, const long long* slot_image, const long long*
     if (!state || !slot_image || !point_ids || !xyz || !K || !R || !t || !state_ids || !initial_depth) return bad_arg(__func__, "null pointer");
     finish_kernel<<<blocks_of(U, kThreads), kThreads, 0, (hipStream_t)stream>>>(state, slot_image, point_ids, xyz, K, R, t, I, U, Q,
                                                                                    state_ids, initial_depth);
-    OPSFT_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -347,7 +332,7 @@ int opsft_track_rows(const long long* track_offsets, const long long* elem_point
         return bad_arg(__func__, "null pointer");
     track_rows_kernel<<<blocks_of(E, kThreads), kThreads, 0, (hipStream_t)stream>>>(track_offsets, elem_point, elem_image, track_kpt,
                                                                                        assigned_image, Q, E, other, match_kpt, ref_kpt);
-    OPSFT_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -359,7 +344,7 @@ int opsft_pair_keys(const long long* owner_slot, const long long* row_elem, cons
     if (!owner_slot || !row_elem || !slot_image || !kpt_offsets || !elem_image || !id_rank || !keys) return bad_arg(__func__, "null pointer");
     const PairTables t{owner_slot, row_elem, slot_image, kpt_offsets, elem_image, I, U, E, M};
     pair_keys_kernel<<<blocks_of(M, kThreads), kThreads, 0, (hipStream_t)stream>>>(t, id_rank, key_stride, keys);
-    OPSFT_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -374,7 +359,7 @@ int opsft_pair_emit(const long long* perm, const long long* owner_slot, const lo
     const PairTables t{owner_slot, row_elem, slot_image, kpt_offsets, elem_image, I, U, E, M};
     pair_emit_kernel<<<blocks_of(M, kThreads), kThreads, 0, (hipStream_t)stream>>>(t, perm, match_kpt, xys, mkpts0_c, mkpts1_c, mkpts0_idx,
                                                                                       row_left, row_right);
-    OPSFT_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -389,7 +374,7 @@ int opsft_fine_rows(const long long* row_point, const long long* ref_image, cons
     fine_rows_kernel<<<blocks_of(R, kThreads), kThreads, 0, (hipStream_t)stream>>>(row_point, ref_image, assigned_image, assigned_kpt,
                                                                                       image_ids, pair_left, pair_right, pair_offsets,
                                                                                       mkpts0_idx, I, Q, R, Np, M, fine_row, error_flag);
-    OPSFT_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 

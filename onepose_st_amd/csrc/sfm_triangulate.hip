@@ -16,8 +16,13 @@
 // This file is compiled with -ffp-contract=off: every expression is evaluated in the written order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "onepose_sfm_triangulate.h"
+#include "capi_error.h"
+
+using capi::bad_arg;
+using capi::blocks_of;
+using capi::fail;
+using capi::g_error;
 
 namespace {
 
@@ -26,26 +31,6 @@ constexpr int kShort = OPSTR_SHORT_TRACK;         // one wavefront
 constexpr int kCam = OPSTR_CAMERA_DOUBLES;
 constexpr int kSums = 10;                         // the widest reduction: 6 + 3 normal-equation entries and the cost
 constexpr int kElemDoubles = 21;                  // P 12, xy 2, dir 3, centre 3, one pad (an odd stride over the LDS banks)
-
-thread_local char g_error[256] = "";
-
-int fail(hipError_t e, const char* where) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, hipGetErrorString(e));
-    return (int)e > 0 ? (int)e : 1;
-}
-
-int bad_arg(const char* where, const char* what) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, what);
-    return -1;
-}
-
-#define OPSTR_CHECK_LAUNCH()                                   \
-    do {                                                       \
-        hipError_t e__ = hipGetLastError();                    \
-        if (e__ != hipSuccess) return fail(e__, __func__);     \
-    } while (0)
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ---- components --------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int load_parent(const int* parent, int x) { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -540,7 +525,7 @@ int opstr_components(const long long* slot0, const long long* slot1, long long T
     hipStream_t s = (hipStream_t)stream;
     if (T > 0) hook_kernel<<<blocks_of(T, kThreads), kThreads, 0, s>>>(slot0, slot1, T, U, parent);
     flatten_kernel<<<blocks_of(U, kThreads), kThreads, 0, s>>>(parent, U, labels);
-    OPSTR_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -551,7 +536,7 @@ int opstr_prepare(const double* K, const double* R, const double* t, const doubl
     hipStream_t s = (hipStream_t)stream;
     camera_kernel<<<blocks_of(I, kThreads), kThreads, 0, s>>>(K, R, t, I, cameras);
     dir_kernel<<<blocks_of(U, kThreads), kThreads, 0, s>>>(K, R, xys, slot_image, I, U, dirs);
-    OPSTR_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
@@ -576,7 +561,7 @@ int opstr_round(const long long* comp_offsets, const long long* comp_label, cons
                         point_error, min_slot, assigned};
     round_short_kernel<<<(unsigned)C, kShort, 0, s>>>(t);
     if (n_long > 0) round_long_kernel<<<(unsigned)n_long, kThreads, 0, s>>>(t, long_comps, n_long);
-    OPSTR_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 

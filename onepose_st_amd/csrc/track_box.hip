@@ -9,28 +9,11 @@
 // Every value is a fixed expression of the inputs, so the lane layout cannot change a bit.  Nothing is indexed by a device-side value:
 // the status, the counts and the boxes only select between values.  Compiled with contraction off.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "onepose_pnp_device.h"
 #include "onepose_track.h"
-#include "track_internal.h"
+#include "capi_error.h"
 
 #pragma clang fp contract(off)
-
-namespace optrk {
-
-thread_local char g_error[256] = "";
-
-int fail(hipError_t e, const char* where) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, hipGetErrorString(e));
-    return (int)e > 0 ? (int)e : 1;
-}
-
-int bad_arg(const char* where, const char* what) {
-    snprintf(g_error, sizeof g_error, "%s: %s", where, what);
-    return -1;
-}
-
-}  // namespace optrk
 
 namespace {
 
@@ -130,26 +113,26 @@ __global__ __launch_bounds__(kThreads) void box_from_pose_kernel(const double* _
 extern "C" {
 
 int optrk_abi_version(void) { return OPTRK_ABI_VERSION; }
-const char* optrk_last_error(void) { return optrk::g_error; }
+const char* optrk_last_error(void) { return capi::g_error; }
 
 int optrk_box_set(int x0, int y0, int x1, int y1, const double* K, int S, int* box, int* flag, double* K_crop, double* trans, void* stream) {
-    if (!K || !box || !flag || !K_crop || !trans) return optrk::bad_arg(__func__, "null pointer");
-    if (S < 1 || S > OPTRK_MAX_CROP) return optrk::bad_arg(__func__, "crop size S outside [1, OPTRK_MAX_CROP]");
-    if (x1 <= x0 || y1 <= y0) return optrk::bad_arg(__func__, "empty box (need x1 > x0, y1 > y0)");
+    if (!K || !box || !flag || !K_crop || !trans) return capi::bad_arg(__func__, "null pointer");
+    if (S < 1 || S > OPTRK_MAX_CROP) return capi::bad_arg(__func__, "crop size S outside [1, OPTRK_MAX_CROP]");
+    if (x1 <= x0 || y1 <= y0) return capi::bad_arg(__func__, "empty box (need x1 > x0, y1 > y0)");
     box_set_kernel<<<1, kThreads, 0, (hipStream_t)stream>>>(x0, y0, x1, y1, K, S, box, flag, K_crop, trans);
-    OPTRK_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 
 int optrk_box_from_pose(const double* K, const double* pose, const int* n_inliers, const int* status, const double* bbox3d, const int* prev_box,
                         const int* prev_flag, int min_inliers, int S, int* box, int* flag, double* K_crop, double* trans, void* stream) {
     if (!K || !pose || !n_inliers || !status || !bbox3d || !prev_box || !prev_flag || !box || !flag || !K_crop || !trans)
-        return optrk::bad_arg(__func__, "null pointer");
-    if (S < 1 || S > OPTRK_MAX_CROP) return optrk::bad_arg(__func__, "crop size S outside [1, OPTRK_MAX_CROP]");
-    if (min_inliers < 0) return optrk::bad_arg(__func__, "min_inliers < 0");
+        return capi::bad_arg(__func__, "null pointer");
+    if (S < 1 || S > OPTRK_MAX_CROP) return capi::bad_arg(__func__, "crop size S outside [1, OPTRK_MAX_CROP]");
+    if (min_inliers < 0) return capi::bad_arg(__func__, "min_inliers < 0");
     box_from_pose_kernel<<<1, kThreads, 0, (hipStream_t)stream>>>(K, pose, n_inliers, status, bbox3d, prev_box, prev_flag, min_inliers, S, box, flag,
                                                                   K_crop, trans);
-    OPTRK_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }
 

@@ -11,7 +11,7 @@
 // (0.5 S is exact, so X - 0.5 S is the same fused or not).  tests/test_gpu_track_device.py compares the two kernels.
 #include <hip/hip_runtime.h>
 #include "onepose_track.h"
-#include "track_internal.h"
+#include "capi_error.h"
 
 #pragma clang fp contract(off)
 
@@ -47,9 +47,9 @@ __global__ __launch_bounds__(256) void crop_box_kernel(const unsigned char* __re
 }  // namespace
 
 extern "C" int optrk_crop(const unsigned char* image, int H, int W, const int* box, int S, float* out, void* stream) {
-    if (!image || !box || !out) return optrk::bad_arg(__func__, "null pointer");
-    if (H < 1 || W < 1 || S < 1 || S > OPTRK_MAX_CROP) return optrk::bad_arg(__func__, "bad sizes");
+    if (!image || !box || !out) return capi::bad_arg(__func__, "null pointer");
+    if (H < 1 || W < 1 || S < 1 || S > OPTRK_MAX_CROP) return capi::bad_arg(__func__, "bad sizes");
     crop_box_kernel<<<dim3((S + 31) / 32, (S + 7) / 8), dim3(256), 0, (hipStream_t)stream>>>(image, H, W, box, S, out);
-    OPTRK_CHECK_LAUNCH();
+    CAPI_CHECK_LAUNCH();
     return 0;
 }

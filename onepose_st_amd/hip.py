@@ -8,22 +8,11 @@ the C ABI with raw device pointers.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
 from . import cabi
-
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.environ.get("OPHIP_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_hip.so")   # OPHIP_LIB: A/B builds
-_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_hip.h")             # where csrc/Makefile finds it too
-_lib = None
-# The header is the one place a signature, a structure or a constant of the C ABI is written: an entry point is added there and in its
-# .hip file, nothing here.  (A missing header leaves the tables empty and load() says so.)
-_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
-ABI_VERSION = _HEADER.defines.get("OPHIP_ABI_VERSION")                  # what the FrameDesc / FrameLayout mirrors below are written for
-SAMPLE_MAX_JOBS = _HEADER.defines.get("OPHIP_SAMPLE_MAX_JOBS")
-COARSE_PLANES_READY = _HEADER.defines.get("OPHIP_COARSE_PLANES_READY")    # or-ed into ophip_coarse_match's nsplit
+from .cabi import HipLibraryError  # noqa: F401  (its old name: hip.HipLibraryError)
 
 c_i = ctypes.c_int
 c_ll = ctypes.c_longlong
@@ -60,48 +49,16 @@ class ObjectCache(ctypes.Structure):
 
 
 _MIRRORS = {"ophip_sample_job": SampleJob, "ophip_frame_desc": FrameDesc, "ophip_frame_layout_t": FrameLayout, "ophip_object_cache": ObjectCache}
-for _name, _fields in _HEADER.structs.items():
+# The header is the one place a signature, a structure or a constant of the C ABI is written: an entry point is added there and in its
+# .hip file, nothing here.  (A missing header leaves the tables empty and load() says so.)
+_BINDING = cabi.Binding.of(__name__, _MIRRORS)
+for _name, _fields in _BINDING.header.structs.items():
     cabi.check_mirror(_MIRRORS[_name], _name, _fields)
-_SIGNATURES = {name: cabi.signature(proto, _MIRRORS) for name, proto in _HEADER.prototypes.items()}      # name -> (restype, argtypes)
-
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-
-
-class HipLibraryError(RuntimeError):
-    pass
-
-
-def library_path() -> str:
-    return _LIB_PATH
-
-
-def load():
-    """Load (once) and return the ctypes handle; raises ``HipLibraryError`` when the
-    library is missing -- build it with ``python -c 'import __graft_entry__ as g; g.build()'``."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_LIB_PATH):
-        raise HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
-    if not _HEADER.prototypes:
-        raise HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
-    lib = ctypes.CDLL(_LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    if lib.ophip_abi_version() != ABI_VERSION:
-        raise HipLibraryError(f"libonepose_hip.so ABI version {lib.ophip_abi_version()}, this binding is written for {ABI_VERSION} "
-                              "(include/onepose_hip.h OPHIP_ABI_VERSION): rebuild with __graft_entry__.build()")
-    _lib = lib
-    return lib
-
-
-def _check(rc: int, name: str):
-    if rc != 0:
-        msg = load().ophip_last_error().decode(errors="replace")
-        if rc == -1:
-            raise ValueError(f"{name}: {msg}")
-        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
+library_path, load, call = _BINDING.library_path, _BINDING.load, _BINDING.call
+EXPORTED_SYMBOLS = _BINDING.exported_symbols
+ABI_VERSION = _BINDING.abi_version                                      # what the FrameDesc / FrameLayout mirrors above are written for
+SAMPLE_MAX_JOBS = _BINDING.header.defines.get("OPHIP_SAMPLE_MAX_JOBS")
+COARSE_PLANES_READY = _BINDING.header.defines.get("OPHIP_COARSE_PLANES_READY")    # or-ed into ophip_coarse_match's nsplit
 
 
 def ptr(t: torch.Tensor | None, dtype=torch.float32):
@@ -124,15 +81,19 @@ def stream_handle():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def call(name: str, *args):
-    """Call an entry point that returns a status and raise on failure.  ctypes accepts surplus arguments silently (a stream handle one
-    slot late would reach C), so the count is checked against the header's prototype first."""
-    fn = getattr(load(), name)
-    params = _HEADER.prototypes[name].params
-    if len(args) != len(params):
-        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
-    rc = fn(*args)
-    _check(rc, name)
+def need_device(named) -> None:
+    """``named``: (name, value) pairs.  Every value is a tensor, and then every one of them lies on the device."""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+    for name, t in named:
+        if not t.is_cuda:
+            raise HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+
+
+def exclusive(counts: torch.Tensor) -> torch.Tensor:
+    """``[n]`` counts -> ``[n + 1]`` int64 offsets from 0"""
+    return torch.cat([torch.zeros(1, dtype=torch.int64, device=counts.device), torch.cumsum(counts, 0)])
 
 
 def build_stamp() -> str:

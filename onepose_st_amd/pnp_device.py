@@ -34,72 +34,27 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import cabi, hip
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.environ.get("OPPNPD_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_pnp_device.so")      # OPPNPD_LIB: A/B builds
-_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_pnp_device.h")
-_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
-_SIGNATURES = {name: cabi.signature(proto) for name, proto in _HEADER.prototypes.items()}                  # the header is the one place
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-ABI_VERSION = _HEADER.defines.get("OPPNPD_ABI_VERSION")
-MAX_TRIALS = _HEADER.defines.get("OPPNPD_MAX_TRIALS")
-DEFAULT_TRIALS = _HEADER.defines.get("OPPNPD_DEFAULT_TRIALS")
-MAX_ROWS = _HEADER.defines.get("OPPNPD_MAX_ROWS")
-MAX_FRAMES = _HEADER.defines.get("OPPNPD_MAX_FRAMES")
-ROW_DOUBLES = _HEADER.defines.get("OPPNPD_ROW_DOUBLES")
-SELECT_BLOCK = _HEADER.defines.get("OPPNPD_SELECT_BLOCK")
-SCORE_CHUNK = _HEADER.defines.get("OPPNPD_SCORE_CHUNK")
-STATUS_NO_POSE = _HEADER.defines.get("OPPNPD_STATUS_NO_POSE")
-STATUS_NEEDS_MORE = _HEADER.defines.get("OPPNPD_STATUS_NEEDS_MORE")
-MIN_INLIERS = _HEADER.defines.get("OPPNPD_MIN_INLIERS")
-MAX_NEEDED = _HEADER.defines.get("OPPNPD_MAX_NEEDED")
-_lib = None
-
-
-def library_path() -> str:
-    return _LIB_PATH
-
-
-def load():
-    """Load (once) and return the ctypes handle of ``libonepose_pnp_device.so``"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            raise hip.HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
-        if not _HEADER.prototypes:
-            raise hip.HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
-        lib = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        if lib.oppnpd_abi_version() != ABI_VERSION:
-            raise hip.HipLibraryError(f"libonepose_pnp_device.so ABI version {lib.oppnpd_abi_version()}, this binding is written for {ABI_VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check_arity(name: str, args) -> None:
-    """ctypes accepts surplus arguments silently, so the count is checked against the header's prototype"""
-    params = _HEADER.prototypes[name].params
-    if len(args) != len(params):
-        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
-
-
-def call(name: str, *args) -> None:
-    check_arity(name, args)
-    lib = load()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.oppnpd_last_error().decode(errors="replace")
-        if rc == -1:
-            raise ValueError(f"{name}: {msg}")
-        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
+library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+EXPORTED_SYMBOLS = _BINDING.exported_symbols
+ABI_VERSION = _BINDING.abi_version
+MAX_TRIALS = _BINDING.header.defines.get("OPPNPD_MAX_TRIALS")
+DEFAULT_TRIALS = _BINDING.header.defines.get("OPPNPD_DEFAULT_TRIALS")
+MAX_ROWS = _BINDING.header.defines.get("OPPNPD_MAX_ROWS")
+MAX_FRAMES = _BINDING.header.defines.get("OPPNPD_MAX_FRAMES")
+ROW_DOUBLES = _BINDING.header.defines.get("OPPNPD_ROW_DOUBLES")
+SELECT_BLOCK = _BINDING.header.defines.get("OPPNPD_SELECT_BLOCK")
+SCORE_CHUNK = _BINDING.header.defines.get("OPPNPD_SCORE_CHUNK")
+STATUS_NO_POSE = _BINDING.header.defines.get("OPPNPD_STATUS_NO_POSE")
+STATUS_NEEDS_MORE = _BINDING.header.defines.get("OPPNPD_STATUS_NEEDS_MORE")
+MIN_INLIERS = _BINDING.header.defines.get("OPPNPD_MIN_INLIERS")
+MAX_NEEDED = _BINDING.header.defines.get("OPPNPD_MAX_NEEDED")
 
 
 def _stream(stream):

@@ -45,14 +45,6 @@ MAX_ROWS = (1 << 30) - 1                # OPHIP_SFM_POINTS2D_MAX_ROWS
 MAX_IMAGES = 1 << 22                    # OPHIP_SFM_POINTS2D_MAX_IMAGES
 
 
-def _dev(t, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a tensor")
-    if not t.is_cuda:
-        raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
-    return t
-
-
 def check_inputs(mkpts0: torch.Tensor, mkpts1: torch.Tensor, mconf: torch.Tensor, pair_offsets: torch.Tensor, pair_images: torch.Tensor,
                  n_images: int):
     """``merge_pair_matches``' input checks, on tensors of any device (the errors of the module docstring) -> (T, P, I)"""
@@ -102,7 +94,7 @@ def merge_pair_matches(mkpts0: torch.Tensor, mkpts1: torch.Tensor, mconf: torch.
     "pair_offsets" [P + 1] int64}`` (the last one as given).  Host reads: the small pair tables, one flag tensor of the input checks and
     the unique-key total."""
     for name, t in (("mkpts0", mkpts0), ("mkpts1", mkpts1), ("mconf", mconf), ("pair_offsets", pair_offsets), ("pair_images", pair_images)):
-        _dev(t, name)
+        hip.need_device([(name, t)])                # one at a time: the first input that is wrong in either way is the one reported
     T, P, I = check_inputs(mkpts0, mkpts1, mconf, pair_offsets, pair_images, n_images)
 
     lib = hip.load()

@@ -36,71 +36,24 @@ fallback).  ``M == 0`` returns empty tensors of the right shapes and dtypes.
 """
 from __future__ import annotations
 
-import ctypes
-import os
-
 import numpy as np
 import torch
 
 from . import cabi, hip
 from .backbone_hip import HipBackbone
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.environ.get("OPSFF_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_sfm_fine.so")      # OPSFF_LIB: A/B builds
-_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_sfm_fine.h")
-_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
-_SIGNATURES = {name: cabi.signature(proto) for name, proto in _HEADER.prototypes.items()}                # the header is the one place
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-ABI_VERSION = _HEADER.defines.get("OPSFF_ABI_VERSION")
-MAX_ROWS = _HEADER.defines.get("OPSFF_MAX_ROWS")
-CTRL_INTS = _HEADER.defines.get("OPSFF_CTRL_INTS")
-NO_ROW = _HEADER.defines.get("OPSFF_NO_ROW")
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
+library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+EXPORTED_SYMBOLS = _BINDING.exported_symbols
+ABI_VERSION = _BINDING.abi_version
+MAX_ROWS = _BINDING.header.defines.get("OPSFF_MAX_ROWS")
+CTRL_INTS = _BINDING.header.defines.get("OPSFF_CTRL_INTS")
+NO_ROW = _BINDING.header.defines.get("OPSFF_NO_ROW")
 COARSE_SCALE = 8.0                                  # image rows per coarse row (ResNetFPN 8 -> 2)
 PAIR_KEYS = ("mkpts0_c", "mkpts1_c", "row_left", "row_right")
 RESULT_KEYS = ("mkpts0_c", "mkpts1_c", "mkpts0_f", "mkpts1_f", "expec_f", "i_ids", "j_ids", "feature_c0", "feature_c1", "feature0", "feature1")
 REFERENCE_KEYS = ("mkpts0_c", "mkpts1_c", "mkpts0_f", "mkpts1_f", "mkpts0_idx", "scale0", "scale1", "feature_c0", "feature_c1", "feature0",
                   "feature1")
-_lib = None
-
-
-def library_path() -> str:
-    return _LIB_PATH
-
-
-def load():
-    """Load (once) and return the ctypes handle of ``libonepose_sfm_fine.so``"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            raise hip.HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
-        if not _HEADER.prototypes:
-            raise hip.HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
-        lib = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        if lib.opsff_abi_version() != ABI_VERSION:
-            raise hip.HipLibraryError(f"libonepose_sfm_fine.so ABI version {lib.opsff_abi_version()}, this binding is written for {ABI_VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check_arity(name: str, args) -> None:
-    """ctypes accepts surplus arguments silently, so the count is checked against the header's prototype"""
-    params = _HEADER.prototypes[name].params
-    if len(args) != len(params):
-        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
-
-
-def call(name: str, *args):
-    check_arity(name, args)
-    lib = load()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.opsff_last_error().decode(errors="replace")
-        if rc == -1:
-            raise ValueError(f"{name}: {msg}")
-        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
 
 
 def _check_matcher(matcher):

@@ -61,83 +61,23 @@ rounds (nothing is read inside the loop), the row counts that size outputs, one 
 """
 from __future__ import annotations
 
-import ctypes
-import os
-
 import torch
 
 from . import cabi, hip, postopt
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.environ.get("OPSFT_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_sfm_tracks.so")      # OPSFT_LIB: A/B builds
-_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_sfm_tracks.h")
-_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
-_SIGNATURES = {name: cabi.signature(proto) for name, proto in _HEADER.prototypes.items()}                  # the header is the one place
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-ABI_VERSION = _HEADER.defines.get("OPSFT_ABI_VERSION")
-MAX_IMAGES = _HEADER.defines.get("OPSFT_MAX_IMAGES")
-MAX_ITEMS = _HEADER.defines.get("OPSFT_MAX_ITEMS")
-CTRL_INTS = _HEADER.defines.get("OPSFT_CTRL_INTS")
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
+library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+EXPORTED_SYMBOLS = _BINDING.exported_symbols
+ABI_VERSION = _BINDING.abi_version
+MAX_IMAGES = _BINDING.header.defines.get("OPSFT_MAX_IMAGES")
+MAX_ITEMS = _BINDING.header.defines.get("OPSFT_MAX_ITEMS")
+CTRL_INTS = _BINDING.header.defines.get("OPSFT_CTRL_INTS")
 MAX_ID = 2 ** 53
 MODEL_KEYS = ("image_ids", "kpt_offsets", "xys", "point3D_ids", "K", "R", "t", "point_ids", "xyz", "track_offsets", "track_image", "track_kpt")
 PLAN_KEYS = ("keyframes", "state", "is_keyframe", "assigned_image", "assigned_kpt", "initial_depth")
 PAIR_KEYS = ("pair_left", "pair_right", "pair_offsets", "mkpts0_c", "mkpts1_c", "mkpts0_idx", "row_left", "row_right")
 ROW_KEYS = ("fine_row", "ref_image", "ref_kpt", "row_point", "n_query", "row_offsets")
 TRACK_KEYS = ("assigned_image", "assigned_kpt", "row_offsets", "ref_image", "ref_kpt", "feature_c0", "feature_c1", "feature0", "feature1")
-_lib = None
-
-
-def library_path() -> str:
-    return _LIB_PATH
-
-
-def load():
-    """Load (once) and return the ctypes handle of ``libonepose_sfm_tracks.so``"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            raise hip.HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
-        if not _HEADER.prototypes:
-            raise hip.HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
-        lib = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        if lib.opsft_abi_version() != ABI_VERSION:
-            raise hip.HipLibraryError(f"libonepose_sfm_tracks.so ABI version {lib.opsft_abi_version()}, this binding is written for {ABI_VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check_arity(name: str, args) -> None:
-    """ctypes accepts surplus arguments silently, so the count is checked against the header's prototype"""
-    params = _HEADER.prototypes[name].params
-    if len(args) != len(params):
-        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
-
-
-def call(name: str, *args):
-    check_arity(name, args)
-    lib = load()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.opsft_last_error().decode(errors="replace")
-        if rc == -1:
-            raise ValueError(f"{name}: {msg}")
-        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
-
-
-def _need_device(named):
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor")
-    for name, t in named:
-        if not t.is_cuda:
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
-
-
-def _exclusive(counts: torch.Tensor) -> torch.Tensor:
-    return torch.cat([torch.zeros(1, dtype=torch.int64, device=counts.device), torch.cumsum(counts, 0)])
 
 
 # ---- the model's checks ---------------------------------------------------------------------------------------------------------------
@@ -228,7 +168,7 @@ def check_model(model: dict, feature_track_assignment_strategy: str = "greedy") 
 def assign_tracks(model: dict, feature_track_assignment_strategy: str = "greedy") -> dict:
     """Section 1 of the module docstring -> the plan"""
     if feature_track_assignment_strategy == "greedy" and all(k in model for k in MODEL_KEYS):
-        _need_device([(k, model[k]) for k in MODEL_KEYS])
+        hip.need_device([(k, model[k]) for k in MODEL_KEYS])
     d = check_model(model, feature_track_assignment_strategy)
     I, U, Q, E = d["I"], d["U"], d["Q"], d["E"]
     dev = model["xys"].device
@@ -266,7 +206,7 @@ def _track_rows(plan: dict, model: dict) -> dict:
     ``row_offsets [Q + 1]``, ``match_kpt`` / ``ref_kpt [E]``"""
     if "_rows" in plan:
         return plan["_rows"]
-    _need_device([(k, model[k]) for k in MODEL_KEYS] + [("plan state", plan["_state"])])
+    hip.need_device([(k, model[k]) for k in MODEL_KEYS] + [("plan state", plan["_state"])])
     d = plan["_tables"]
     Q, E = d["Q"], d["E"]
     dev = model["xys"].device
@@ -279,7 +219,7 @@ def _track_rows(plan: dict, model: dict) -> dict:
          Pt(ref_kpt, i64), hip.stream_handle())
     rows_e = torch.nonzero(other).squeeze(1)
     n_query = torch.bincount(d["elem_point"][rows_e], minlength=Q)
-    plan["_rows"] = {"rows_e": rows_e, "n_query": n_query, "row_offsets": _exclusive(n_query), "match_kpt": match_kpt, "ref_kpt": ref_kpt}
+    plan["_rows"] = {"rows_e": rows_e, "n_query": n_query, "row_offsets": hip.exclusive(n_query), "match_kpt": match_kpt, "ref_kpt": ref_kpt}
     return plan["_rows"]
 
 
@@ -294,7 +234,7 @@ def matching_pairs(plan: dict, model: dict) -> dict:
     owned = torch.nonzero(plan["_state"] >= 0).squeeze(1)                  # ascending slot = image, then keypoint index
     point_of = plan["_state"][owned].to(i64)
     per_slot = tr["n_query"][point_of]
-    first = _exclusive(per_slot)
+    first = hip.exclusive(per_slot)
     M = int(first[-1])                                                     # read-back: sizes the rows
     if M == 0:
         raise ValueError("no point is seen in a second image: there is no pair to match")
@@ -317,7 +257,7 @@ def matching_pairs(plan: dict, model: dict) -> dict:
          Pt(tr["match_kpt"], i64), Pt(model["xys"].contiguous(), f64), I, U, E, M, Pt(out["mkpts0_c"], f64), Pt(out["mkpts1_c"], f64),
          Pt(out["mkpts0_idx"], i64), Pt(out["row_left"], i64), Pt(out["row_right"], i64), S)
     _, per_pair = torch.unique_consecutive(torch.div(sorted_keys, d["max_slots"], rounding_mode="floor"), return_counts=True)
-    offsets = _exclusive(per_pair)
+    offsets = hip.exclusive(per_pair)
     out.update(pair_offsets=offsets, pair_left=out["row_left"][offsets[:-1]], pair_right=out["row_right"][offsets[:-1]])
     return out
 
@@ -340,7 +280,7 @@ def to_reference_outputs(pairs: dict, model: dict) -> dict:
 # ---- 3. the optimiser's rows -------------------------------------------------------------------------------------------------------------
 def optimisation_rows(plan: dict, model: dict, pairs: dict) -> dict:
     """Section 3 of the module docstring -> the rows"""
-    _need_device([(k, pairs[k]) for k in ("pair_left", "pair_right", "pair_offsets", "mkpts0_idx")])
+    hip.need_device([(k, pairs[k]) for k in ("pair_left", "pair_right", "pair_offsets", "mkpts0_idx")])
     tr = _track_rows(plan, model)
     d = plan["_tables"]
     I, Q = d["I"], d["Q"]
@@ -381,7 +321,7 @@ def assigned_slots(plan: dict, model: dict) -> torch.Tensor:
 def to_optimizer_inputs(plan: dict, model: dict, pairs: dict, rows: dict, mkpts1_f: torch.Tensor) -> tuple:
     """``mkpts1_f [M, 2]``: the fine matcher's refined right keypoints, one per pair row -> ``(aggregated, frame_poses)`` as
     ``postopt.Optimizer.start_optimize`` documents them (``ConstructOptimizationData`` reduced as ``start_optimize`` reduces it)"""
-    _need_device([("mkpts1_f", mkpts1_f)])
+    hip.need_device([("mkpts1_f", mkpts1_f)])
     M = pairs["mkpts0_idx"].numel()
     if mkpts1_f.dim() != 2 or tuple(mkpts1_f.shape) != (M, 2):
         raise ValueError(f"mkpts1_f: expected [{M}, 2], got {list(mkpts1_f.shape)}")
@@ -398,7 +338,7 @@ def to_optimizer_inputs(plan: dict, model: dict, pairs: dict, rows: dict, mkpts1
 def to_aggregation_inputs(plan: dict, rows: dict, feature_c0, feature_c1, feature0, feature1) -> dict:
     """The fine matcher's four feature tables, one row per pair row -> stage A's track dict of ``sfm_objectblock.build_object_block``"""
     feats = (("feature_c0", feature_c0), ("feature_c1", feature_c1), ("feature0", feature0), ("feature1", feature1))
-    _need_device(feats)
+    hip.need_device(feats)
     fr = rows["fine_row"]
     out = {"assigned_image": plan["assigned_image"], "assigned_kpt": plan["assigned_kpt"], "row_offsets": rows["row_offsets"],
            "ref_image": rows["ref_image"], "ref_kpt": rows["ref_kpt"]}
@@ -413,7 +353,7 @@ def to_aggregation_inputs(plan: dict, rows: dict, feature_c0, feature_c1, featur
 def update_model(plan: dict, model: dict, depth: torch.Tensor, R: torch.Tensor, t: torch.Tensor) -> dict:
     """``depth [Q]`` (or ``[Q, 1]``) and the refined poses ``R [I, 3, 3]``, ``t [I, 3]`` -> ``{"xyz" [Q, 3], "xys" [U, 2]}``: every point
     unprojected from its assigned keypoint, then every registered slot reprojected (update_optimize_results_to_colmap)"""
-    _need_device([("depth", depth), ("R", R), ("t", t)] + [(k, model[k]) for k in MODEL_KEYS])
+    hip.need_device([("depth", depth), ("R", R), ("t", t)] + [(k, model[k]) for k in MODEL_KEYS])
     d = plan["_tables"]
     xyz = postopt.points_from_depth(model["xys"][assigned_slots(plan, model)], depth, plan["assigned_image"], model["K"], R, t)
     reg = torch.nonzero(d["slot_point"] >= 0).squeeze(1)

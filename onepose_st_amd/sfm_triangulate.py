@@ -47,75 +47,25 @@ their outputs, and the number of points the round added; at the end the number o
 """
 from __future__ import annotations
 
-import ctypes
 import math
-import os
 
 import torch
 
 from . import cabi, hip
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.environ.get("OPSTR_LIB") or os.path.join(_PKG_DIR, "lib", "libonepose_sfm_triangulate.so")   # OPSTR_LIB: A/B builds
-_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "onepose_sfm_triangulate.h")
-_HEADER = cabi.parse(open(_HEADER_PATH).read()) if os.path.exists(_HEADER_PATH) else cabi.parse("")
-_SIGNATURES = {name: cabi.signature(proto) for name, proto in _HEADER.prototypes.items()}                  # the header is the one place
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-ABI_VERSION = _HEADER.defines.get("OPSTR_ABI_VERSION")
-MAX_ITEMS = _HEADER.defines.get("OPSTR_MAX_ITEMS")
-SHORT_TRACK = _HEADER.defines.get("OPSTR_SHORT_TRACK")
-MAX_HYPOTHESES = _HEADER.defines.get("OPSTR_MAX_HYPOTHESES")
-MAX_REFINE_STEPS = _HEADER.defines.get("OPSTR_MAX_REFINE_STEPS")
-MAX_ROUNDS = _HEADER.defines.get("OPSTR_MAX_ROUNDS")
-CAMERA_DOUBLES = _HEADER.defines.get("OPSTR_CAMERA_DOUBLES")
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
+library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+EXPORTED_SYMBOLS = _BINDING.exported_symbols
+ABI_VERSION = _BINDING.abi_version
+MAX_ITEMS = _BINDING.header.defines.get("OPSTR_MAX_ITEMS")
+SHORT_TRACK = _BINDING.header.defines.get("OPSTR_SHORT_TRACK")
+MAX_HYPOTHESES = _BINDING.header.defines.get("OPSTR_MAX_HYPOTHESES")
+MAX_REFINE_STEPS = _BINDING.header.defines.get("OPSTR_MAX_REFINE_STEPS")
+MAX_ROUNDS = _BINDING.header.defines.get("OPSTR_MAX_ROUNDS")
+CAMERA_DOUBLES = _BINDING.header.defines.get("OPSTR_CAMERA_DOUBLES")
 MERGED_KEYS = ("keypoints", "kpt_offsets", "match_ids", "pair_offsets", "pair_images")
 CAMERA_KEYS = ("image_ids", "K", "R", "t")
 DEFAULTS = {"max_reproj_error": 4.0, "min_tri_angle": 1.5, "max_hypotheses": 256, "refine_steps": 5, "max_rounds": 3}
-_lib = None
-
-
-def library_path() -> str:
-    return _LIB_PATH
-
-
-def load():
-    """Load (once) and return the ctypes handle of ``libonepose_sfm_triangulate.so``"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            raise hip.HipLibraryError(f"{_LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build())")
-        if not _HEADER.prototypes:
-            raise hip.HipLibraryError(f"{_HEADER_PATH} not found: the binding takes every C signature from that header")
-        lib = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        if lib.opstr_abi_version() != ABI_VERSION:
-            raise hip.HipLibraryError(f"libonepose_sfm_triangulate.so ABI version {lib.opstr_abi_version()}, this binding is written for {ABI_VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check_arity(name: str, args) -> None:
-    """ctypes accepts surplus arguments silently, so the count is checked against the header's prototype"""
-    params = _HEADER.prototypes[name].params
-    if len(args) != len(params):
-        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
-
-
-def call(name: str, *args):
-    check_arity(name, args)
-    lib = load()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.opstr_last_error().decode(errors="replace")
-        if rc == -1:
-            raise ValueError(f"{name}: {msg}")
-        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
-
-
-def _exclusive(counts: torch.Tensor) -> torch.Tensor:
-    return torch.cat([torch.zeros(1, dtype=torch.int64, device=counts.device), torch.cumsum(counts, 0)])
 
 
 def check_options(options: dict) -> dict:
@@ -252,7 +202,7 @@ def triangulate(merged: dict, cameras: dict, **options) -> dict:
         several = counts >= 2                                            # a component of one candidate has no hypothesis: no workgroup for it
         elem_slot = elem_slot[several[comp_of]].contiguous()
         comp_label, counts = comp_label[several], counts[several]
-        offsets = _exclusive(counts)
+        offsets = hip.exclusive(counts)
         long_comps = torch.nonzero(counts > SHORT_TRACK).squeeze(1).contiguous()
         C, n_elems, n_long = comp_label.numel(), elem_slot.numel(), long_comps.numel()     # read-back: sizes the launch and its outputs
         if C == 0:
@@ -289,7 +239,7 @@ def triangulate(merged: dict, cameras: dict, **options) -> dict:
         track_image = slot_image[elems]
         model.update(point_ids=torch.arange(1, Q + 1, dtype=i64, device=dev), xyz=torch.cat(kept_xyz)[order].contiguous(),
                      point_error=torch.cat(kept_err)[order].contiguous(), point3D_ids=slot_point + (slot_point >= 0).to(i64),
-                     track_offsets=_exclusive(torch.bincount(point_of, minlength=Q)), track_image=track_image,
+                     track_offsets=hip.exclusive(torch.bincount(point_of, minlength=Q)), track_image=track_image,
                      track_kpt=elems - ko[track_image])
     else:
         model.update(point_ids=torch.zeros(0, dtype=i64, device=dev), xyz=torch.zeros(0, 3, dtype=f64, device=dev),

@@ -1,7 +1,10 @@
 """The Python bindings take every C signature, constant and structure layout from ``include/*.h`` (``onepose_st_amd/cabi.py``).
-CPU only: the reader on the real headers and on made-up ones, the structure mirrors, the arity check of ``hip.call``, and three faults
-seeded into copies of the header that the prototypes written out below must catch."""
+CPU only: the reader on the real headers and on made-up ones, the structure mirrors, ``cabi.Binding`` (arity check, error mapping, load
+errors) on stand-in handles and on the built libraries for every entry of ``cabi.LIBRARIES``, and three faults seeded into copies of the
+header that the prototypes written out below must catch."""
 import ctypes
+import glob
+import importlib
 import os
 import re
 
@@ -12,6 +15,8 @@ from onepose_st_amd import cabi, hip
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP_H = open(os.path.join(REPO, "include", "onepose_hip.h")).read()
 PNP_H = open(os.path.join(REPO, "include", "onepose_pnp.h")).read()
+
+BINDINGS = {entry.module: importlib.import_module(f"onepose_st_amd.{entry.module}")._BINDING for entry in cabi.LIBRARIES}
 
 LL4 = "long long, long long, long long, long long"
 # (name, return type, parameter types): written from the headers by hand, one of every type the headers use
@@ -73,7 +78,7 @@ def test_reader_finds_every_prototype_of_both_headers():
 
 def test_the_rule_from_c_types_to_ctypes_classes():
     vp, i = ctypes.c_void_p, ctypes.c_int
-    sig = hip._SIGNATURES
+    sig = BINDINGS["hip"].signatures
     assert sig["ophip_device_info"] == (i, [vp, vp, ctypes.c_char_p, i])
     assert sig["ophip_build_stamp"] == (ctypes.c_char_p, [])
     assert sig["ophip_coarse_frag_planes"] == (i, [vp, i, i, i, ctypes.POINTER(vp), ctypes.POINTER(vp)])
@@ -175,18 +180,23 @@ def test_structure_mirrors_match_the_header():
 
 
 class _StandIn:
-    """in place of the library handle: records what would have reached C"""
+    """in place of the library handle: records what would have reached C; ``rc`` is what every entry point returns, ``<prefix>_last_error``
+    and ``<prefix>_abi_version`` answer ``error`` and ``abi``"""
 
-    def __init__(self):
-        self.entered = []
+    def __init__(self, rc=0, error=b"", abi=None):
+        self.entered, self.rc, self.error, self.abi = [], rc, error, abi
 
     def __getattr__(self, name):
-        return lambda *args: self.entered.append((name, args)) or 0
+        if name.endswith("_last_error"):
+            return lambda: self.entered.append((name, ())) or self.error
+        if name.endswith("_abi_version"):
+            return lambda: self.abi
+        return lambda *args: self.entered.append((name, args)) or self.rc
 
 
 def test_call_checks_the_number_of_arguments(monkeypatch):
     lib = _StandIn()
-    monkeypatch.setattr(hip, "_lib", lib)
+    monkeypatch.setattr(BINDINGS["hip"], "handle", lib)
     args = (None, None, None, 1, 2, 3, None)                       # ophip_pe_add_transpose(feat_nchw, pe_nlc, out_nlc, B, C, M, stream)
     hip.call("ophip_pe_add_transpose", *args)
     assert lib.entered == [("ophip_pe_add_transpose", args)]
@@ -200,6 +210,74 @@ def test_call_checks_the_number_of_arguments(monkeypatch):
     with pytest.raises(TypeError):                                  # the spliced kind: an optional pointer too many pushes the stream one slot late
         hip.call("ophip_encoder_layer_x3w8_streams", *([None] * 12), None)
     assert len(lib.entered) == 1                                    # nothing else reached the handle
+
+
+def _status_entry(binding):
+    """the first entry point of a binding that returns a status and takes arguments"""
+    return next(p for p in binding.header.prototypes.values() if p.ret == "int" and p.params)
+
+
+@pytest.mark.parametrize("module", BINDINGS)
+def test_every_binding_checks_the_number_of_arguments(module, monkeypatch):
+    """the same statement for each library, through the names its module exports"""
+    binding, mod, lib = BINDINGS[module], importlib.import_module(f"onepose_st_amd.{module}"), _StandIn()
+    monkeypatch.setattr(binding, "handle", lib)
+    proto = _status_entry(binding)
+    args = (None,) * len(proto.params)
+    mod.call(proto.name, *args)
+    assert lib.entered == [(proto.name, args)]
+    for wrong in (args + (None,), args[:-1]):
+        for check in ((lambda: mod.call(proto.name, *wrong)), (lambda: binding.check_arity(proto.name, wrong))):
+            with pytest.raises(TypeError) as e:
+                check()
+            msg = str(e.value)
+            assert proto.name in msg and f"takes {len(args)} arguments" in msg and f"{len(wrong)} given" in msg
+            assert ", ".join(n for _, n in proto.params) in msg
+    binding.check_arity(proto.name, args)
+    if module != "hip":
+        assert mod.check_arity == binding.check_arity
+    assert len(lib.entered) == 1                                    # nothing else reached the handle
+
+
+@pytest.mark.parametrize("module", BINDINGS)
+def test_call_maps_the_status_to_an_exception(module, monkeypatch):
+    binding, mod = BINDINGS[module], importlib.import_module(f"onepose_st_amd.{module}")
+    proto = _status_entry(binding)
+    args = (None,) * len(proto.params)
+    last_error = (f"{binding.prefix}_last_error", ())
+    ok = _StandIn(rc=0, error=b"never read")
+    monkeypatch.setattr(binding, "handle", ok)
+    assert mod.call(proto.name, *args) is None
+    assert ok.entered == [(proto.name, args)]                       # the error text is read on failure only
+    rejected = _StandIn(rc=-1, error=b"somewhere: null pointer")
+    monkeypatch.setattr(binding, "handle", rejected)
+    with pytest.raises(ValueError) as e:
+        mod.call(proto.name, *args)
+    assert str(e.value) == f"{proto.name}: somewhere: null pointer"
+    assert rejected.entered == [(proto.name, args), last_error]
+    failed = _StandIn(rc=7, error=b"somewhere: out of memory")
+    monkeypatch.setattr(binding, "handle", failed)
+    with pytest.raises(RuntimeError) as e:
+        mod.call(proto.name, *args)
+    assert "rc=7" in str(e.value) and "somewhere: out of memory" in str(e.value) and proto.name in str(e.value)
+    assert not isinstance(e.value, cabi.HipLibraryError) and failed.entered == [(proto.name, args), last_error]
+
+
+@pytest.mark.parametrize("module", BINDINGS)
+def test_abi_mismatch_is_reported_by_load(module, monkeypatch):
+    binding = BINDINGS[module]
+    opened = []
+    monkeypatch.setattr(binding, "handle", None)
+    monkeypatch.setattr(cabi.ctypes, "CDLL", lambda path: opened.append(path) or _StandIn(abi=binding.abi_version + 1))
+    for attempt in (1, 2):                                          # the handle is not kept: the second load() opens the file again
+        with pytest.raises(cabi.HipLibraryError) as e:
+            binding.load()
+        msg = str(e.value)
+        assert binding.so in msg and f"ABI version {binding.abi_version + 1}" in msg and f"written for {binding.abi_version}" in msg
+        assert binding.header_path in msg and "__graft_entry__.build()" in msg
+        assert binding.handle is None and opened == [binding.path] * attempt
+    monkeypatch.setattr(cabi.ctypes, "CDLL", lambda path: _StandIn(abi=binding.abi_version))
+    assert binding.load() is binding.handle is not None
 
 
 def test_call_arity_with_the_real_library():
@@ -241,12 +319,79 @@ def test_seeded_fault_layout_field_moved():
         cabi.check_mirror(hip.FrameLayout, "ophip_frame_layout_t", bad.structs["ophip_frame_layout_t"])
 
 
-def test_missing_header_is_reported_by_load(monkeypatch):
-    monkeypatch.setattr(hip, "_lib", None)
-    monkeypatch.setattr(hip, "_HEADER", cabi.parse(""))
-    monkeypatch.setattr(hip, "_HEADER_PATH", os.path.join(REPO, "include", "no_such_header.h"))
+@pytest.mark.parametrize("entry", cabi.LIBRARIES, ids=lambda e: e.module)
+def test_missing_header_is_reported_by_load(entry):
+    binding = cabi.Binding("no_such_header.h", entry.so, entry.prefix, entry.env)
+    assert binding.exported_symbols == () and binding.abi_version is None and binding.library_path() == BINDINGS[entry.module].path
     with pytest.raises(hip.HipLibraryError, match="no_such_header.h"):
-        hip.load()
+        binding.load()
+    assert binding.handle is None
+
+
+def test_missing_library_is_reported_by_load(monkeypatch, tmp_path):
+    monkeypatch.setenv("OPSFT_LIB", str(tmp_path / "libonepose_absent.so"))        # read once, when the binding is made
+    binding = cabi.Binding.of("onepose_st_amd.sfm_tracks")
+    with pytest.raises(cabi.HipLibraryError, match=r"libonepose_absent\.so not found.*__graft_entry__\.build\(\)"):
+        binding.load()
+    monkeypatch.delenv("OPSFT_LIB")
+    assert binding.library_path().endswith("libonepose_absent.so") and BINDINGS["sfm_tracks"].path.endswith("libonepose_sfm_tracks.so")
+
+
+def test_the_table_of_libraries_is_complete():
+    assert hip.HipLibraryError is cabi.HipLibraryError
+    headers = sorted(os.path.basename(p) for p in glob.glob(os.path.join(REPO, "include", "onepose_*.h")))
+    assert sorted(e.header for e in cabi.LIBRARIES) == [h for h in headers if h != "onepose_pnp.h"] and "onepose_pnp.h" in headers
+    for column in zip(*cabi.LIBRARIES):
+        assert len(set(column)) == len(cabi.LIBRARIES)              # no header, prefix, file, variable or module twice
+    for entry in cabi.LIBRARIES:
+        mod, binding = importlib.import_module(f"onepose_st_amd.{entry.module}"), BINDINGS[entry.module]
+        assert (binding.so, binding.prefix, os.path.basename(binding.header_path)) == (entry.so, entry.prefix, entry.header)
+        assert (mod.load, mod.call, mod.library_path) == (binding.load, binding.call, binding.library_path)
+        assert mod.EXPORTED_SYMBOLS is binding.exported_symbols and mod.ABI_VERSION == binding.abi_version and isinstance(mod.ABI_VERSION, int)
+        assert hasattr(mod, "check_arity") or entry.module == "hip"
+        assert mod.EXPORTED_SYMBOLS and all(s.startswith(entry.prefix + "_") for s in mod.EXPORTED_SYMBOLS)
+        assert {f"{entry.prefix}_abi_version", f"{entry.prefix}_last_error"} <= set(mod.EXPORTED_SYMBOLS)
+        text = open(binding.header_path).read()
+        assert set(mod.EXPORTED_SYMBOLS) == set(re.findall(rf"\b({entry.prefix}_\w+)\s*\(", text))     # no other library's prefix in it
+
+
+_PTR = ctypes.c_void_p(8)        # not null and never followed: the entries below return before they launch anything
+# One entry point per satellite library whose argument checks are its first statements, before any HIP call (read in its .hip file),
+# the arguments that are not 0 / NULL, and the text the library itself writes.
+REJECTED = {
+    "sfm_objectblock": ("opsfm_box_test", {}, "opsfm_box_test: null pointer"),
+    "sfm_tracks": ("opsft_finish", {}, "opsft_finish: table sizes"),
+    "sfm_triangulate": ("opstr_components", {"T": -1, "U": 1}, "opstr_components: table sizes"),
+    "sfm_fine": ("opsff_row_ids", {}, "opsff_row_ids: null pointer"),
+    "pnp_device": ("oppnpd_ranges", {"cap": 1}, "oppnpd_ranges: table sizes"),
+    "track_device": ("optrk_box_set", {"x1": 1, "y1": 1, "K": _PTR, "S": 0, "box": _PTR, "flag": _PTR, "K_crop": _PTR, "trans": _PTR},
+                     "optrk_box_set: crop size S outside [1, OPTRK_MAX_CROP]"),
+}
+
+
+def test_the_built_libraries_answer_for_themselves():
+    """No device: the ABI number of each built library, then one rejected call per satellite library.  Every library keeps its own error
+    text, whatever is called in another one afterwards."""
+    assert set(REJECTED) == set(BINDINGS) - {"hip"}
+    for module, binding in BINDINGS.items():
+        mod = importlib.import_module(f"onepose_st_amd.{module}")
+        assert getattr(mod.load(), f"{binding.prefix}_abi_version")() == mod.ABI_VERSION == binding.abi_version
+        assert mod.load() is binding.handle
+
+    def last_error(module):
+        return getattr(BINDINGS[module].load(), f"{BINDINGS[module].prefix}_last_error")().decode()
+
+    for module, (name, given, text) in REJECTED.items():
+        mod, params = importlib.import_module(f"onepose_st_amd.{module}"), BINDINGS[module].header.prototypes[name].params
+        assert set(given) <= {n for _, n in params}
+        args = [given.get(n, None if c.endswith("*") else 0) for c, n in params]
+        with pytest.raises(ValueError) as e:
+            mod.call(name, *args)
+        assert str(e.value) == f"{name}: {text}" and last_error(module) == text
+        hip.call("ophip_timing_every", 1)                           # a correct call into another library (host side only)
+        assert last_error(module) == text
+    for module, (_, _, text) in REJECTED.items():                   # and the five rejections that followed in other libraries
+        assert last_error(module) == text
 
 
 def test_pnp_binds_from_its_header():

@@ -3,6 +3,7 @@ interface of ``onepose_st_amd/pnp_device.py`` (header, binding, policy errors). 
 """
 import os
 import re
+import subprocess
 import sys
 
 import numpy as np
@@ -137,7 +138,15 @@ def test_header_and_binding():
     mk = open(os.path.join(REPO, "onepose_st_amd", "csrc", "Makefile")).read()
     srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
     assert "pnp_device.hip" not in srcs and re.search(r"^PND_SRCS := pnp_device.hip$", mk, re.M)
-    assert re.search(r"^build/pnd/%\.o:.*\n(\t.*\n)*\t\$\(HIPCC\).*-ffp-contract=off", mk, re.M)
+
+    def compile_line(obj):                       # what make would run for one object, however the Makefile writes its rules
+        out = subprocess.run(["make", "-n", "-B", obj], cwd=os.path.join(REPO, "onepose_st_amd", "csrc"), check=True, capture_output=True, text=True)
+        line, = [ln for ln in out.stdout.splitlines() if ln.endswith(f" -o {obj}")]
+        return line.split()
+
+    for obj in ("build/pnd/pnp_device.o", "build/sfm/sfm_objectblock.o", "build/sft/sfm_tracks.o", "build/str/sfm_triangulate.o", "build/trk/track_box.o"):
+        assert "-ffp-contract=off" in compile_line(obj), obj
+    assert "-ffp-contract=off" not in compile_line("build/trk/track_crop.o")      # that file writes its fused operations out itself
     # the package does not import the oracle
     for root, _, files in os.walk(os.path.join(REPO, "onepose_st_amd")):
         for fn in files:

@@ -3,19 +3,16 @@
 # = the working tree's csrc with the listed files taken from <git rev>; result: onepose_st_amd/lib/variants/libonepose_hip_<name>.so
 # EXTRA="-D..." in the environment adds compiler flags; <git rev> may be "-" with no files (working tree + EXTRA only).
 # (load it with OPHIP_LIB=<path>; `tools/box.sh <name> ab:R:S:variants` runs variants interleaved on one box).  Variants are scratch: git-ignored like every .so.
-# A first <csrc file> of `sfm`, `sfm_tracks`, `pnp_device` or `track` is a goal, not a file: the variant is then one of libonepose_sfm.so (OPSFM_LIB),
-# libonepose_sfm_tracks.so (OPSFT_LIB), libonepose_pnp_device.so (OPPNPD_LIB) or libonepose_track.so (OPTRK_LIB), e.g. the seeded faults of tests/test_gpu_sfm_tracks.py:
+# A first <csrc file> of `sfm`, `sfm_tracks`, `sfm_triangulate`, `sfm_fine`, `pnp_device` or `track` is a goal, not a file: the variant is then that satellite
+# library, libonepose_<goal>.so (load it with its OP*_LIB variable, onepose_st_amd/cabi.py LIBRARIES), e.g. the seeded faults of tests/test_gpu_sfm_tracks.py:
 #   EXTRA=-DOPSFT_FAULT_TIE_INITIAL_ORDER tools/build_variant.sh tie - sfm_tracks   -> lib/variants/libonepose_sfm_tracks_tie.so
 set -e
 name=$1; rev=$2; shift 2
 root=$(cd $(dirname $0)/.. && pwd)
 lib=libonepose_hip; var=OUT
-case "$1" in
-  sfm) lib=libonepose_sfm; var=SFM_OUT; shift;;
-  sfm_tracks) lib=libonepose_sfm_tracks; var=SFT_OUT; shift;;
-  pnp_device) lib=libonepose_pnp_device; var=PND_OUT; shift;;
-  track) lib=libonepose_track; var=TRK_OUT; shift;;
-esac
+# a goal is the <name> of a `satellite` line of csrc/Makefile; its tag names the variable that takes the output path
+tag=$(sed -n "s/^\$(eval \$(call satellite,\([A-Z]*\),[a-z]*,$1))\$/\1/p" $root/onepose_st_amd/csrc/Makefile)
+if [ -n "$tag" ]; then lib=libonepose_$1; var=${tag}_OUT; shift; fi
 tmp=$(mktemp -d)
 mkdir -p $tmp/onepose_st_amd $root/onepose_st_amd/lib/variants
 cp -r $root/onepose_st_amd/csrc $tmp/onepose_st_amd/csrc
