@@ -1,0 +1,230 @@
+"""Device detection: the object detector's vote -- one affine RANSAC per reference view, the box every view votes, the winning view and
+the track state of its box -- from the LoFTR matcher's device-side matches, without a host round trip (opt-in; the host vote of
+``detector.LocalFeatureObjectDetector.match_worker`` with ``pnp.estimate_affine2d`` stays the default).
+
+The work is HIP (``csrc/detect_affine.hip`` in ``libonepose_detect.so``, include/detect/onepose_detect.h).  CPU tensors raise
+:class:`hip.HipLibraryError` (no CPU fallback).  The specification (written out in the header;
+``tests/detect_device_oracle.py`` restates it in numpy float64, one function per stage) is the host estimator's model, inlier rule and
+fit with a fixed number of counter-based trials in place of the sequential generator and the adaptive stop:
+
+1. ``ranges``: a view's rows ``[begin, end)`` by binary search in the ascending ``b_ids``; ``count`` is clamped to the capacity, a row
+   whose id lies outside ``[0, V)`` belongs to no view.
+2. ``score``: trial ``t`` of view ``v`` draws three distinct rows (``pnp_device``'s sampler with ``v`` in place of the frame), forms
+   ``affine_from3`` of them and counts the view's rows with ``ex^2 + ey^2 < thr^2``; a degenerate sample counts 0; a view of fewer than
+   ``max(min_matches, 3)`` rows runs no trials.
+3. ``select``: per view the trial with the highest count, the lowest trial among equals; its count and inlier mask;
+   ``STATUS_NEEDS_MORE`` when the host's stop formula asks for more trials than ran (informational).
+4. ``fit_box``: the host's normal equations on the winner's inliers, every sum in the header's fixed order; the view's corners through
+   the affinity, truncated toward zero, their minimum and maximum.  The centre box ``[W // 2 - 500, H // 2 - 500, W // 2 + 500,
+   H // 2 + 500]`` with 0 inliers and ``STATUS_NO_MODEL`` for a view of fewer than ``min_matches`` rows, a best count below 3, a singular
+   system, or a corner that is not finite or outside int32.
+5. ``vote``: the view with the most inliers, the first among equals; the ``track_device.TrackState`` of its box (bit-equal to
+   ``track_device.set_box`` of it); a winning box with ``x1 <= x0`` or ``y1 <= y0`` gives the centre box and ``STATUS_DEGENERATE``.
+
+Nothing is synchronised or read back: every launch is sized by the capacity.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import cabi, hip
+from .track_device import MAX_CROP, TrackState
+
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
+library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+EXPORTED_SYMBOLS = _BINDING.exported_symbols
+ABI_VERSION = _BINDING.abi_version
+MAX_VIEWS = _BINDING.header.defines.get("OPDET_MAX_VIEWS")
+MAX_TRIALS = _BINDING.header.defines.get("OPDET_MAX_TRIALS")
+DEFAULT_TRIALS = _BINDING.header.defines.get("OPDET_DEFAULT_TRIALS")
+MAX_ROWS = _BINDING.header.defines.get("OPDET_MAX_ROWS")
+MAX_SIDE = _BINDING.header.defines.get("OPDET_MAX_SIDE")
+SCORE_CHUNK = _BINDING.header.defines.get("OPDET_SCORE_CHUNK")
+STATUS_NO_MODEL = _BINDING.header.defines.get("OPDET_STATUS_NO_MODEL")
+STATUS_DEGENERATE = _BINDING.header.defines.get("OPDET_STATUS_DEGENERATE")
+STATUS_NEEDS_MORE = _BINDING.header.defines.get("OPDET_STATUS_NEEDS_MORE")
+
+
+def _stream(stream):
+    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else hip.stream_handle()
+
+
+def _seed(seed):
+    return ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))
+
+
+def _check_options(min_matches, reproj, confidence, trials):
+    if int(min_matches) != min_matches or min_matches < 0:
+        raise ValueError("min_matches: an integer >= 0")
+    if not (math.isfinite(reproj) and reproj > 0):
+        raise ValueError("ransac_reproj_threshold: a finite number > 0")
+    if not 0 < confidence < 1:
+        raise ValueError("confidence: in (0, 1)")
+    if int(trials) != trials or not 1 <= trials <= MAX_TRIALS:
+        raise ValueError(f"trials: an integer in [1, {MAX_TRIALS}]")
+
+
+class _Inputs:
+    """The checked tensors of one call: types, shapes and dtypes first, then the device, all before the library is loaded"""
+
+    def __init__(self, mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size, count):
+        tensors = [("mkpts0", mkpts0), ("mkpts1", mkpts1), ("b_ids", b_ids)]
+        tensors += [(k, v) for k, v in (("view_hw", view_hw), ("K", K), ("count", count)) if isinstance(v, torch.Tensor)]
+        for name, t in tensors:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}: expected a tensor")
+        if mkpts0.dim() != 2 or mkpts0.shape[1] != 2 or tuple(mkpts1.shape) != tuple(mkpts0.shape):
+            raise ValueError("mkpts0 and mkpts1: [cap, 2], the same length")
+        if mkpts0.dtype != torch.float32 or mkpts1.dtype != torch.float32:
+            raise ValueError("mkpts0 and mkpts1: float32")
+        n = mkpts0.shape[0]
+        if n > MAX_ROWS:
+            raise ValueError(f"at most {MAX_ROWS} rows")
+        if b_ids.dtype != torch.int64 or tuple(b_ids.shape) != (n,):
+            raise ValueError(f"b_ids: int64 [{n}]")
+        if not isinstance(view_hw, torch.Tensor):
+            view_hw = torch.as_tensor(np.asarray(view_hw, dtype=np.int32).reshape(-1, 2))
+            view_hw = view_hw.to(mkpts0.device)
+        if view_hw.dtype != torch.int32 or view_hw.dim() != 2 or view_hw.shape[1] != 2 or not 1 <= view_hw.shape[0] <= MAX_VIEWS:
+            raise ValueError(f"view_hw: int32 [V, 2] (H, W of every view), V in [1, {MAX_VIEWS}]")
+        H, W = (int(v) for v in query_hw)
+        if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+            raise ValueError(f"query_hw: (H, W) in [1, {MAX_SIDE}]")
+        if int(crop_size) != crop_size or not 1 <= crop_size <= MAX_CROP:
+            raise ValueError(f"crop_size: an integer in [1, {MAX_CROP}]")
+        if not isinstance(K, torch.Tensor):
+            K = torch.as_tensor(np.ascontiguousarray(np.asarray(K, dtype=np.float64))).to(mkpts0.device)
+        if K.dtype != torch.float64 or K.numel() != 9:
+            raise ValueError("K: float64 [3, 3]")
+        if isinstance(count, torch.Tensor) and (count.dtype != torch.int32 or count.numel() != 1):
+            raise ValueError("count: one int32 on the device")
+        if not all(t.is_cuda for t in (mkpts0, mkpts1, b_ids, view_hw, K)) or (isinstance(count, torch.Tensor) and not count.is_cuda):
+            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        dev = mkpts0.device
+        if count is not None and not isinstance(count, torch.Tensor):
+            count = torch.full((1,), int(count), dtype=torch.int32, device=dev)
+        if n == 0:                                          # the library wants a table of at least one row; the count says it is unused
+            mkpts0 = mkpts1 = torch.zeros(1, 2, dtype=torch.float32, device=dev)
+            b_ids, count = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+        self.mk0, self.mk1, self.b_ids, self.count = mkpts0.contiguous(), mkpts1.contiguous(), b_ids.contiguous(), count
+        self.view_hw, self.K = view_hw.contiguous(), K.contiguous().view(9)
+        self.cap, self.V, self.H, self.W, self.S, self.dev = self.mk0.shape[0], int(view_hw.shape[0]), H, W, int(crop_size), dev
+
+
+class DeviceDetection:
+    """What :func:`vote` returns, on the device: ``state`` (the ``track_device.TrackState`` of the winning box), ``boxes [V, 4]``,
+    ``n_inliers [V]`` and ``status [V]`` int32, ``affine [V, 6]`` float64 (row-major 2 x 3; the identity where a view has no model),
+    ``winner [1]`` int32, ``inlier_mask [cap]`` uint8 over the rows (``ranges [V, 2]``: the rows of every view)."""
+
+    def __init__(self, state, boxes, n_inliers, affine, status, winner, inlier_mask, ranges, keep=()):
+        self.state, self.boxes, self.n_inliers, self.affine, self.status = state, boxes, n_inliers, affine, status
+        self.winner, self.inlier_mask, self.ranges = winner, inlier_mask, ranges
+        self.status_host = None
+        self._keep = keep                                   # the inputs and the workspace stay referenced while the work may be queued
+
+    def to_host(self):
+        """``({view: {"inliers", "bbox"}}, winner)``: ``match_worker``'s dict (``inliers``: uint8 ``[n, 1]`` over the view's rows, or an
+        empty array where the view votes the centre box) and the winning view.  The one read-back."""
+        V, cap = self.boxes.shape[0], self.inlier_mask.shape[0]
+        packed = torch.cat([self.boxes.reshape(-1).view(torch.uint8), self.status.view(torch.uint8), self.ranges.reshape(-1).view(torch.uint8),
+                            self.winner.view(torch.uint8), self.inlier_mask]).cpu().numpy()
+        o = 0
+        boxes = packed[o:o + 16 * V].view(np.int32).reshape(V, 4); o += 16 * V
+        status = packed[o:o + 4 * V].view(np.int32); o += 4 * V
+        ranges = packed[o:o + 8 * V].view(np.int32).reshape(V, 2); o += 8 * V
+        winner = int(packed[o:o + 4].view(np.int32)[0]); o += 4
+        mask = packed[o:o + cap]
+        self.status_host = status.copy()
+        votes = {}
+        for v in range(V):
+            b, e = int(ranges[v, 0]), int(ranges[v, 1])
+            inl = np.empty((0)) if int(status[v]) & STATUS_NO_MODEL else mask[b:e].reshape(-1, 1).copy()
+            votes[v] = {"inliers": inl, "bbox": boxes[v].copy()}
+        return votes, winner
+
+
+def vote(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size: int = 512, count=None, trials: int = DEFAULT_TRIALS, seed: int = 1,
+         min_matches: int = 6, ransac_reproj_threshold: float = 6.0, confidence: float = 0.99, stream=None) -> DeviceDetection:
+    """The module docstring's vote on device tensors: ``mkpts0 [cap, 2]`` (reference view) and ``mkpts1 [cap, 2]`` (query) float32,
+    ``b_ids [cap]`` int64 ascending; ``view_hw [V, 2]`` int32 (a device tensor, or host numbers, uploaded); ``query_hw = (H, W)``; ``K``
+    the full-frame intrinsics (a float64 device tensor, or host numbers, uploaded); ``count`` int32[1] on the device (default: all
+    rows).  Everything is enqueued on ``stream`` (default: the current one); nothing is read back."""
+    _check_options(min_matches, float(ransac_reproj_threshold), float(confidence), trials)
+    a = _Inputs(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size, count)
+    V, cap, dev = a.V, a.cap, a.dev
+    nbytes = load().opdet_workspace_bytes(cap, V, int(trials))
+    P = hip.ptr
+    with torch.cuda.device(dev), (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        boxes = torch.empty(V, 4, dtype=torch.int32, device=dev)
+        n_in, status = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev)
+        affine = torch.empty(V, 6, dtype=torch.float64, device=dev)
+        mask = torch.zeros(cap, dtype=torch.uint8, device=dev)
+        winner = torch.empty(1, dtype=torch.int32, device=dev)
+        st = TrackState(dev)
+        call("opdet_detect", P(a.mk0), P(a.mk1), P(a.b_ids, torch.int64), P(a.count, torch.int32), cap, V, P(a.view_hw, torch.int32), a.H, a.W,
+             P(a.K, torch.float64), a.S, int(min_matches), float(ransac_reproj_threshold), float(confidence), int(trials), _seed(seed), P(ws, None),
+             nbytes, P(boxes, torch.int32), P(n_in, torch.int32), P(affine, torch.float64), P(status, torch.int32), P(mask, torch.uint8),
+             P(winner, torch.int32), P(st.box, torch.int32), P(st.flag, torch.int32), P(st.K_crop, torch.float64), P(st.trans, torch.float64),
+             _stream(stream))
+    ranges = ws[:8 * V].view(torch.int32).view(V, 2)       # the first table of the workspace
+    return DeviceDetection(st, boxes, n_in, affine, status, winner, mask, ranges, keep=(ws, a))
+
+
+class stages:
+    """Thin wrappers over the per-stage entries (device tensors in, device tensors out); what ``opdet_detect`` enqueues in this order"""
+
+    @staticmethod
+    def ranges(b_ids, count, cap, views, stream=None):
+        out = torch.empty(views, 2, dtype=torch.int32, device=b_ids.device)
+        call("opdet_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(views), hip.ptr(out, torch.int32), _stream(stream))
+        return out
+
+    @staticmethod
+    def score(mkpts0, mkpts1, ranges, trials, seed, min_matches=6, reproj=6.0, stream=None):
+        """-> ``samples [V, trials, 3]``, ``cnt [V, trials]``"""
+        V, dev = ranges.shape[0], mkpts0.device
+        samples = torch.empty(V, trials, 3, dtype=torch.int32, device=dev)
+        cnt = torch.empty(V, trials, dtype=torch.int32, device=dev)
+        call("opdet_score", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), mkpts0.shape[0], V, int(trials), int(min_matches),
+             float(reproj), _seed(seed), hip.ptr(samples, torch.int32), hip.ptr(cnt, torch.int32), _stream(stream))
+        return samples, cnt
+
+    @staticmethod
+    def select(mkpts0, mkpts1, ranges, count, samples, cnt, min_matches=6, reproj=6.0, confidence=0.99, stream=None):
+        """-> ``best [V]``, ``n_inliers [V]``, ``status [V]``, ``inlier_mask [cap]``"""
+        V, trials, dev = cnt.shape[0], cnt.shape[1], mkpts0.device
+        best, n_in, status = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(3))
+        mask = torch.zeros(mkpts0.shape[0], dtype=torch.uint8, device=dev)
+        call("opdet_select", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), hip.ptr(count, torch.int32), hip.ptr(samples, torch.int32),
+             hip.ptr(cnt, torch.int32), mkpts0.shape[0], V, trials, int(min_matches), float(reproj), float(confidence), hip.ptr(best, torch.int32),
+             hip.ptr(n_in, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), _stream(stream))
+        return best, n_in, status, mask
+
+    @staticmethod
+    def fit_box(mkpts0, mkpts1, ranges, view_hw, query_hw, n_inliers, status, mask, stream=None):
+        """Updates ``n_inliers``, ``status`` and ``mask`` in place; returns ``affine [V, 6]``, ``boxes [V, 4]``"""
+        V, dev = ranges.shape[0], mkpts0.device
+        affine = torch.empty(V, 6, dtype=torch.float64, device=dev)
+        boxes = torch.empty(V, 4, dtype=torch.int32, device=dev)
+        call("opdet_fit_box", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), hip.ptr(view_hw, torch.int32), mkpts0.shape[0], V,
+             int(query_hw[0]), int(query_hw[1]), hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8),
+             hip.ptr(affine, torch.float64), hip.ptr(boxes, torch.int32), _stream(stream))
+        return affine, boxes
+
+    @staticmethod
+    def vote(boxes, n_inliers, status, query_hw, K, crop_size=512, stream=None):
+        """Updates ``status`` in place; returns ``winner [1]`` and the ``TrackState``"""
+        dev = boxes.device
+        winner = torch.empty(1, dtype=torch.int32, device=dev)
+        st = TrackState(dev)
+        K = K.contiguous().view(9)
+        call("opdet_vote", hip.ptr(boxes, torch.int32), hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), boxes.shape[0], int(query_hw[0]),
+             int(query_hw[1]), hip.ptr(K, torch.float64), int(crop_size), hip.ptr(winner, torch.int32), hip.ptr(st.box, torch.int32),
+             hip.ptr(st.flag, torch.int32), hip.ptr(st.K_crop, torch.float64), hip.ptr(st.trans, torch.float64), _stream(stream))
+        return winner, st

@@ -31,9 +31,16 @@ def sample_reference_views(n_images: int, n_ref_view: int = 15) -> list:
 
 
 class LocalFeatureObjectDetector:
-    def __init__(self, matcher, db_imgs, device=None, min_matches: int = 6, ransac_reproj_threshold: float = 6.0):
+    def __init__(self, matcher, db_imgs, device=None, min_matches: int = 6, ransac_reproj_threshold: float = 6.0, vote: str = "host"):
         """``matcher``: a ``LoFTR_for_OnePose_Plus`` on the device; ``db_imgs``: the reference views, grayscale ``[H, W]`` uint8 arrays
-        (or float tensors in [0, 1]) -- already sampled (:func:`sample_reference_views`)."""
+        (or float tensors in [0, 1]) -- already sampled (:func:`sample_reference_views`).  ``vote="device"`` adds
+        :meth:`match_worker_device` and :meth:`detect_state`: the per-view RANSACs, the vote and the box's track state on the device
+        (``detect_device``), nothing read back; the host path stays as it is."""
+        if vote not in ("host", "device"):
+            raise ValueError(f"vote={vote!r}: 'host' or 'device'")
+        self.vote = vote
+        if vote == "device":                          # only then: ``hasattr(detector, "detect_state")`` is how SequenceRunner asks
+            self.match_worker_device, self.detect_state, self._view_hw_dev = self._match_worker_device, self._detect_state, None
         self.matcher = matcher
         self.device = torch.device(device) if device is not None else next(matcher.parameters()).device
         self.min_matches, self.thr = int(min_matches), float(ransac_reproj_threshold)
@@ -90,6 +97,42 @@ class LocalFeatureObjectDetector:
             votes = list(ex.map(lambda i: self._vote(i, packed[bounds[i]:bounds[i + 1], 1:3], packed[bounds[i]:bounds[i + 1], 3:5], hw),
                                 range(len(self.db_imgs))))
         return dict(enumerate(votes))
+
+    # ---- vote="device" -------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _match_worker_device(self, query: torch.Tensor, K=None, crop_size: int = 512):
+        """:meth:`match_worker` with the vote on the device -> a ``detect_device.DeviceDetection``.  The matcher call is the batched
+        one; views of other sizes than the query take one call each, concatenated with their view index as ``b_ids``; then ONE vote
+        call.  ``K`` (default: the identity) and ``crop_size`` go into the winning box's track state.  Nothing is read back after
+        the matcher's own count."""
+        from . import detect_device
+        hw = tuple(query.shape[-2:])
+        same = all(tuple(v.shape[-2:]) == hw for v in self.db_imgs)
+        if same and len(self.db_imgs) > 1:
+            pair = {"image0": torch.cat(self.db_imgs, 0), "image1": query}
+            self.matcher(pair)
+            mk0, mk1, b_ids = pair["mkpts0_f"], pair["mkpts1_f"], pair["b_ids"]
+        else:
+            parts = []
+            for idx, view in enumerate(self.db_imgs):
+                pair = {"image0": view, "image1": query}
+                self.matcher(pair)
+                parts.append((pair["mkpts0_f"], pair["mkpts1_f"], torch.full((pair["mkpts0_f"].shape[0],), idx, dtype=torch.int64, device=self.device)))
+            mk0, mk1, b_ids = (torch.cat([p[k] for p in parts], 0) for k in range(3))
+        if self._view_hw_dev is None:
+            self._view_hw_dev = torch.tensor([list(v.shape[-2:]) for v in self.db_imgs], dtype=torch.int32).to(self.device)
+        if K is None:
+            K = torch.eye(3, dtype=torch.float64, device=self.device)
+        return detect_device.vote(mk0.float().contiguous(), mk1.float().contiguous(), b_ids.to(torch.int64), self._view_hw_dev, hw, K,
+                                  crop_size=crop_size, min_matches=self.min_matches, ransac_reproj_threshold=self.thr)
+
+    def _detect_state(self, frame_u8_dev: torch.Tensor, K_dev, crop_size: int = 512):
+        """The ``track_device.TrackState`` of the detected box for a uint8 ``[H, W]`` frame on the device and the full-frame intrinsics
+        ``K_dev`` (float64 on the device): what ``track_device.set_box(self(frame), K, crop_size)`` gives, without a host round trip."""
+        if not torch.is_tensor(frame_u8_dev) or frame_u8_dev.dtype != torch.uint8 or frame_u8_dev.dim() != 2:
+            raise ValueError("detect_state: a uint8 [H, W] grayscale frame on the device")
+        query = (frame_u8_dev.float() / 255.0)[None, None].contiguous()
+        return self._match_worker_device(query, K_dev, crop_size).state
 
     def detect_by_matching(self, query: torch.Tensor) -> np.ndarray:
         """(:146-162): the box of the view with the most inliers; among equals the first view (the reference's stable descending sort)"""

@@ -124,22 +124,33 @@ class SequenceRunner:
     ``crop_fn`` is not used then.  ``data`` also carries ``frame_index`` (host int) and ``crop_trans`` / ``K_crop`` (device float64
     ``[3, 3]``); a ``model`` without ``enqueue`` is called as ``model(data)`` and may fill ``mkpts_query_f`` / ``mkpts_3d_db`` from those
     without leaving the device.
+
+    ``detect="host"`` (the default): ``detector(frame, t)`` gives the box of frame 0 and of every frame after a lost track as host
+    integers.  ``detect="device"`` (needs ``track="device"`` and a detector with ``detect_state``, such as
+    ``detector.LocalFeatureObjectDetector(vote="device")``): ``detector.detect_state(frame_u8_dev, K_dev, crop_size)`` gives that box's
+    ``track_device.TrackState`` on the device, enqueued behind the frame's upload, and ``detector(...)`` is never called.
     """
 
     MAX_LOOKAHEAD = 8         # the one-call frame keeps 16 frames in flight at most
 
     def __init__(self, model, object_block: dict, K, bbox3d, detector, crop_size: int = 512, pnp_reprojection_error: float = 7,
                  pnp_scale: float = 1000, min_inliers: int = MIN_INLIERS, crop_fn=crop_query, pnp: str = "host", track: str = "host",
-                 lookahead: int = 2):
+                 lookahead: int = 2, detect: str = "host"):
         if pnp not in ("host", "device"):
             raise ValueError(f"pnp={pnp!r}: 'host' or 'device'")
         if track not in ("host", "device"):
             raise ValueError(f"track={track!r}: 'host' or 'device'")
         if track == "device" and pnp != "device":
             raise ValueError("track='device' needs pnp='device': the box is computed from the device pose")
+        if detect not in ("host", "device"):
+            raise ValueError(f"detect={detect!r}: 'host' or 'device'")
+        if detect == "device" and track != "device":
+            raise ValueError("detect='device' needs track='device': the detected box stays on the device")
+        if detect == "device" and not hasattr(detector, "detect_state"):
+            raise ValueError("detect='device' needs a detector with detect_state(frame_u8_dev, K_dev, crop_size)")
         if int(lookahead) != lookahead or not 1 <= lookahead <= self.MAX_LOOKAHEAD:
             raise ValueError(f"lookahead: an integer in [1, {self.MAX_LOOKAHEAD}]")
-        self.pnp, self.track, self.lookahead = pnp, track, int(lookahead)
+        self.pnp, self.track, self.lookahead, self.detect = pnp, track, int(lookahead), detect
         self.model, self.block, self.crop_fn = model, object_block, crop_fn
         self.K, self.bbox3d, self.detector = np.asarray(K, np.float64), np.asarray(bbox3d, np.float64), detector
         self.crop_size, self.reproj, self.scale, self.min_inliers = crop_size, pnp_reprojection_error, pnp_scale, min_inliers
@@ -259,6 +270,10 @@ class SequenceRunner:
                 for k in (t, t + 1):
                     if k < n and k not in uploads:
                         uploads[k] = self._upload(frames[k])
+                if state is None and self.detect == "device":      # the same place, the box never leaves the device
+                    if uploads[t][1] is not None:
+                        torch.cuda.current_stream().wait_event(uploads[t][1])
+                    state, redetected[t] = self.detector.detect_state(uploads[t][0], self._K_dev, self.crop_size), True
                 if state is None:                           # frame 0 and the frame after a lost one: the queue is empty here
                     bbox = np.asarray(self.detector(frames[t], t)).astype(np.int32)
                     state, redetected[t] = track_device.set_box(bbox, self._K_dev, self.crop_size), True
