@@ -1,7 +1,7 @@
 """Reader of the project's C headers (``include/onepose_*.h``: one per entry of ``LIBRARIES`` below, plus ``onepose_pnp.h`` of the host
 library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures and the loaded handle of one
-HIP library.  The headers are the only place a C signature is written; the modules ``LIBRARIES`` (and ``EXTRA_LIBRARIES``) name and
-``pnp.py`` bind from what this reads.
+HIP library.  The headers are the only place a C signature is written; the modules ``LIBRARIES`` names and ``pnp.py`` bind from
+what this reads.
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -23,18 +23,14 @@ LIBRARIES = (Library("ophip", "onepose_hip.h", "libonepose_hip.so", "OPHIP_LIB",
              Library("opstr", "onepose_sfm_triangulate.h", "libonepose_sfm_triangulate.so", "OPSTR_LIB", "sfm_triangulate"),
              Library("opsff", "onepose_sfm_fine.h", "libonepose_sfm_fine.so", "OPSFF_LIB", "sfm_fine"),
              Library("oppnpd", "onepose_pnp_device.h", "libonepose_pnp_device.so", "OPPNPD_LIB", "pnp_device"),
-             Library("optrk", "onepose_track.h", "libonepose_track.so", "OPTRK_LIB", "track_device"))
-# Libraries bound, built and loaded exactly like the rows above, but not yet rows of LIBRARIES: tests/test_cabi_binding.py keeps one
-# hand-written rejected call per row of LIBRARIES and compares the two sets, so a row and its line there arrive together.  Until then
-# the header lies in a directory of its own under include/ (include/onepose_*.h is the set of LIBRARIES' headers), and
-# tests/test_detect_device_cpu.py runs that file's per-row checks on this table.
-EXTRA_LIBRARIES = (Library("opdet", "detect/onepose_detect.h", "libonepose_detect.so", "OPDET_LIB", "detect_device"),)
+             Library("optrk", "onepose_track.h", "libonepose_track.so", "OPTRK_LIB", "track_device"),
+             Library("opdet", "onepose_detect.h", "libonepose_detect.so", "OPDET_LIB", "detect_device"))
 
 SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 RETURN_TYPES = (*SCALARS, "const char*", "void", "void*")
 _POINTEES = (*SCALARS, "char", "unsigned char", "void")
-_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES + EXTRA_LIBRARIES] + ['oppnp'])})_\w+"          # oppnp: the host library (pnp.py)
+_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp'])})_\w+"          # oppnp: the host library (pnp.py)
 
 
 class HeaderError(ValueError):
@@ -158,8 +154,8 @@ class Binding:
 
     @classmethod
     def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
-        """The binding of the ``LIBRARIES`` (or ``EXTRA_LIBRARIES``) entry whose module is ``module`` (a ``__name__``)"""
-        entry, = [e for e in LIBRARIES + EXTRA_LIBRARIES if e.module == module.rpartition(".")[2]]
+        """The binding of the ``LIBRARIES`` entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES if e.module == module.rpartition(".")[2]]
         return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors)
 
     def library_path(self) -> str:

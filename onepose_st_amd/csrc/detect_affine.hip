@@ -1,9 +1,9 @@
-// Device detection (include/detect/onepose_detect.h): the detector's vote from the LoFTR matcher's device-side matches
+// Device detection (include/onepose_detect.h): the detector's vote from the LoFTR matcher's device-side matches
 // without a host round trip.  The arithmetic is the host estimator's (csrc_host/pnp.cpp: affine_from3, affine_inliers and the normal
 // equations of oppnp_estimate_affine2d), statement by statement in float64; what differs is the sampler (counter-based, so scheduling
 // cannot change a draw) and that every trial runs.
 //
-//   ranges    ranges_kernel: one thread per view, two binary searches in b_ids
+//   ranges    ranges_kernel (device_loop.h, as the sampler and the crop geometry): one thread per view, two binary searches in b_ids
 //   score     score_kernel: one workgroup per (view, 256 trials); a thread draws its trial's three rows, forms the affinity in registers
 //             and walks the view's rows, staged through LDS in chunks of OPDET_SCORE_CHUNK (16 bytes a row) and read at a wave-uniform
 //             address; the count is a per-thread integer
@@ -17,13 +17,22 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include "detect/onepose_detect.h"
+#include "onepose_detect.h"
 #include "onepose_track.h"
 #include "capi_error.h"
+#include "device_loop.h"
 
 using capi::bad_arg;
 using capi::blocks_of;
 using capi::g_error;
+using devloop::align_up;
+using devloop::block_best;
+using devloop::draw3;
+using devloop::fits_int32;
+using devloop::geometry_entry;
+using devloop::mask_clear_kernel;
+using devloop::ranges_kernel;
+using devloop::row_range;
 
 #pragma clang fp contract(off)
 
@@ -34,40 +43,7 @@ constexpr int kChunk = OPDET_SCORE_CHUNK;
 constexpr int kSums = 12;                         // xx, xy, x, yy, y, 1; xu, yu, u; xv, yv, v
 static_assert(kChunk == kThreads, "a thread stages one row of a chunk");
 
-// [begin, end) of view v, forced into the row table whatever the ranges table holds
-__device__ __forceinline__ void view_range(const int* ranges, int v, int cap, int& begin, int& end) {
-    int b = ranges[2 * v], e = ranges[2 * v + 1];
-    b = b < 0 ? 0 : (b > cap ? cap : b);
-    e = e < b ? b : (e > cap ? cap : e);
-    begin = b; end = e;
-}
-
-__device__ __forceinline__ int clamped_count(const int* count, int cap) {
-    const int n = count ? *count : cap;
-    return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
 __device__ __forceinline__ int trial_floor(int min_matches) { return min_matches > 3 ? min_matches : 3; }
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-// three distinct rows in [0, n), n >= 3
-__device__ __forceinline__ void draw3(uint64_t seed, int v, int t, int n, int& a, int& b, int& c) {
-    const uint64_t base = (((uint64_t)v << 32) | (uint64_t)t) * 4ull;
-    const uint64_t G = 0x9E3779B97F4A7C15ull;
-    a = (int)(mix64(seed + G * (base + 1ull)) % (uint64_t)n);
-    b = (int)(mix64(seed + G * (base + 2ull)) % (uint64_t)(n - 1));
-    if (b >= a) ++b;
-    c = (int)(mix64(seed + G * (base + 3ull)) % (uint64_t)(n - 2));
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    if (c >= lo) ++c;
-    if (c >= hi) ++c;
-}
 
 // affine_from3 of the host estimator on rows r0, r1, r2 (indices into the row table, checked by the caller)
 __device__ __forceinline__ bool affine_from3(const float* __restrict__ s, const float* __restrict__ d, int r0, int r1, int r2, double* A) {
@@ -92,24 +68,6 @@ __device__ __forceinline__ bool row_inlier(const double* A, double x, double y, 
     return ex * ex + ey * ey < thr2;
 }
 
-// ---- ranges ------------------------------------------------------------------------------------------------------------------------------
-__global__ void ranges_kernel(const long long* __restrict__ b_ids, const int* __restrict__ count, int cap, int V, int* __restrict__ ranges) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    const int n = clamped_count(count, cap);
-    int res[2];
-    for (int s = 0; s < 2; ++s) {                 // the first row whose id is >= v + s
-        const long long key = (long long)v + s;
-        int lo = 0, hi = n;
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-            const int mid = lo + (hi - lo) / 2;
-            if (b_ids[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        res[s] = lo;
-    }
-    ranges[2 * v] = res[0]; ranges[2 * v + 1] = res[1] < res[0] ? res[0] : res[1];
-}
-
 // ---- sample, hypothesis, score -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void score_kernel(const float* __restrict__ mk0, const float* __restrict__ mk1, const int* __restrict__ ranges,
                                                          int cap, int V, int trials, int min_matches, double thr2, uint64_t seed,
@@ -117,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void score_kernel(const float* __restrict
     __shared__ float4 sh[kChunk];
     const int t = blockIdx.x * kThreads + threadIdx.x, v = blockIdx.y;
     int begin, end;
-    view_range(ranges, v, cap, begin, end);
+    row_range(ranges, v, cap, begin, end);
     const int n = end - begin;
     const size_t slot = (size_t)v * trials + t;
     if (n < trial_floor(min_matches)) {           // the whole workgroup leaves: no trials in this view
@@ -164,23 +122,6 @@ __device__ __forceinline__ bool better(const Best& a, const Best& b) {      // a
     return a.idx < b.idx;
 }
 
-__device__ __forceinline__ Best block_best(Best mine, Best* sh) {
-    sh[threadIdx.x] = mine;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s && better(sh[threadIdx.x + s], sh[threadIdx.x])) sh[threadIdx.x] = sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const Best r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__global__ void mask_clear_kernel(const int* __restrict__ count, int cap, unsigned char* __restrict__ mask) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < clamped_count(count, cap)) mask[i] = 0;
-}
-
 __global__ __launch_bounds__(kThreads) void select_kernel(const float* __restrict__ mk0, const float* __restrict__ mk1, const int* __restrict__ ranges,
                                                           const int* __restrict__ samples, const int* __restrict__ cnt, int cap, int V, int trials,
                                                           int min_matches, double thr2, double confidence, int* __restrict__ best,
@@ -188,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void select_kernel(const float* __restric
     __shared__ Best sh[kThreads];
     const int v = blockIdx.x;
     int begin, end;
-    view_range(ranges, v, cap, begin, end);
+    row_range(ranges, v, cap, begin, end);
     const int n = end - begin;
     const bool ran = n >= trial_floor(min_matches);
     Best mine{0, -1};
@@ -198,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void select_kernel(const float* __restric
             if (c.cnt > 0 && better(c, mine)) mine = c;
         }
     }
-    const Best r = block_best(mine, sh);
+    const Best r = block_best<kThreads>(mine, sh);
     const int won = r.idx < 0 ? 0 : (r.cnt > n ? n : r.cnt);
     if (threadIdx.x == 0) {
         int st = (n < min_matches || won < 3) ? OPDET_STATUS_NO_MODEL : 0;
@@ -225,9 +166,6 @@ __global__ __launch_bounds__(kThreads) void select_kernel(const float* __restric
 }
 
 // ---- fit, box ----------------------------------------------------------------------------------------------------------------------------
-// true when v truncates toward zero to an int32 (false for NaN and the infinities)
-__device__ __forceinline__ bool fits_int32(double v) { return v > -2147483649.0 && v < 2147483648.0; }
-
 __device__ __forceinline__ void centre_box(int H, int W, int* b) {
     b[0] = W / 2 - 500; b[1] = H / 2 - 500; b[2] = W / 2 + 500; b[3] = H / 2 + 500;
 }
@@ -241,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void fit_box_kernel(const float* __restri
     __shared__ int sh_model;
     const int v = blockIdx.x, tid = threadIdx.x;
     int begin, end;
-    view_range(ranges, v, cap, begin, end);
+    row_range(ranges, v, cap, begin, end);
     const int st_in = status[v];
     const bool model = !(st_in & OPDET_STATUS_NO_MODEL) && n_inliers[v] >= 3;
     double acc[kSums];
@@ -324,25 +262,6 @@ __global__ __launch_bounds__(kThreads) void fit_box_kernel(const float* __restri
 }
 
 // ---- vote --------------------------------------------------------------------------------------------------------------------------------
-// crop_geometry's expression (include/onepose_track.h): entry e = 3 i + j of trans and of K_crop = trans K for box b
-__device__ __forceinline__ void geometry_entry(const int* b, const double* __restrict__ K, int S, int e, double* __restrict__ K_crop,
-                                               double* __restrict__ trans) {
-    const double x0 = (double)b[0], y0 = (double)b[1], x1 = (double)b[2], y1 = (double)b[3];
-    const double wb = x1 - x0, hb = y1 - y0;
-    const double s = (double)S / wb;
-    const int i = e / 3, j = e - 3 * i;
-    double t0, t1, t2;
-    if (i == 0) {
-        t0 = s; t1 = 0.0; t2 = -s * x0;
-    } else if (i == 1) {
-        t0 = 0.0; t1 = s; t2 = 0.5 * (double)S - s * (y0 + 0.5 * hb);
-    } else {
-        t0 = 0.0; t1 = 0.0; t2 = 1.0;
-    }
-    trans[e] = j == 0 ? t0 : (j == 1 ? t1 : t2);
-    K_crop[e] = ((t0 * K[j]) + (t1 * K[3 + j])) + (t2 * K[6 + j]);
-}
-
 __global__ __launch_bounds__(kThreads) void vote_kernel(const int* __restrict__ boxes, const int* __restrict__ n_inliers, int* __restrict__ status, int V,
                                                         int H, int W, const double* __restrict__ K, int S, int* __restrict__ winner,
                                                         int* __restrict__ box, int* __restrict__ flag, double* __restrict__ K_crop,
@@ -351,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void vote_kernel(const int* __restrict__ 
     __shared__ int sbox[4];
     const int tid = threadIdx.x;
     const Best mine = tid < V ? Best{n_inliers[tid], tid} : Best{0, -1};      // V <= OPDET_MAX_VIEWS = the workgroup's threads
-    const Best r = block_best(mine, sh);
+    const Best r = block_best<kThreads>(mine, sh);
     if (tid == 0) {
         const int w = r.idx < 0 || r.idx >= V ? 0 : r.idx;
         int b[4] = {boxes[4 * w], boxes[4 * w + 1], boxes[4 * w + 2], boxes[4 * w + 3]};
@@ -374,8 +293,6 @@ bool sizes_ok(int cap, int V) { return cap >= 1 && cap <= OPDET_MAX_ROWS && V >=
 bool trials_ok(int trials) { return trials >= 1 && trials <= OPDET_MAX_TRIALS; }
 bool thr_ok(double e) { return isfinite(e) && e > 0.0; }
 bool frame_ok(int H, int W) { return H >= 1 && H <= OPDET_MAX_SIDE && W >= 1 && W <= OPDET_MAX_SIDE; }
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout { size_t ranges, samples, cnt, best, total; };
 
@@ -405,7 +322,7 @@ size_t opdet_workspace_bytes(int cap, int V, int trials) {
 int opdet_ranges(const long long* b_ids, const int* count, int cap, int V, int* ranges, void* stream) {
     if (!sizes_ok(cap, V)) return bad_arg(__func__, "table sizes");
     if (!b_ids || !ranges) return bad_arg(__func__, "null pointer");
-    ranges_kernel<<<blocks_of(V, kThreads), kThreads, 0, (hipStream_t)stream>>>(b_ids, count, cap, V, ranges);
+    ranges_kernel<kThreads><<<blocks_of(V, kThreads), kThreads, 0, (hipStream_t)stream>>>(b_ids, count, cap, V, ranges);
     CAPI_CHECK_LAUNCH();
     return 0;
 }
@@ -433,7 +350,7 @@ int opdet_select(const float* mk0, const float* mk1, const int* ranges, const in
     if (!thr_ok(reproj_thr)) return bad_arg(__func__, "reproj_thr: a finite number > 0");
     if (!(confidence > 0.0 && confidence < 1.0)) return bad_arg(__func__, "confidence: in (0, 1)");
     hipStream_t S = (hipStream_t)stream;
-    mask_clear_kernel<<<blocks_of(cap, kThreads), kThreads, 0, S>>>(count, cap, inlier_mask);
+    mask_clear_kernel<kThreads><<<blocks_of(cap, kThreads), kThreads, 0, S>>>(count, cap, inlier_mask);
     CAPI_CHECK_LAUNCH();
     select_kernel<<<V, kThreads, 0, S>>>(mk0, mk1, ranges, samples, cnt, cap, V, trials, min_matches, reproj_thr * reproj_thr, confidence, best,
                                          n_inliers, status, inlier_mask);

@@ -2,8 +2,8 @@
 // host round trip.  The arithmetic is the host solver's (csrc_host/pnp.cpp: p3p_poses, count_inliers, refine_lm, finish), statement by
 // statement in float64; what differs is the sampler (counter-based, so scheduling cannot change a draw) and that every trial runs.
 //
-//   ranges, prep   ranges_kernel: one thread per frame, two binary searches in b_ids; prep_kernel: one thread per row
-//   sample         sample_kernel: one thread per (frame, trial), three splitmix64 draws without a rejection loop
+//   ranges, prep   ranges_kernel (device_loop.h): one thread per frame, two binary searches in b_ids; prep_kernel: one thread per row
+//   sample         sample_kernel: one thread per (frame, trial), three splitmix64 draws without a rejection loop (draw3, device_loop.h)
 //   p3p            p3p_kernel: one thread per (frame, trial): Grunert's quartic, Ferrari + three Newton steps, triangle alignment
 //   score          score_kernel: one lane per hypothesis with the pose in registers; the frame's rows go through LDS in chunks of
 //                  OPPNPD_SCORE_CHUNK and are read at a wave-uniform address; count and cost are per-lane sums in row order
@@ -18,11 +18,19 @@
 #include <stdint.h>
 #include "onepose_pnp_device.h"
 #include "capi_error.h"
+#include "device_loop.h"
 
 using capi::bad_arg;
 using capi::blocks_of;
 using capi::fail;
 using capi::g_error;
+using devloop::align_up;
+using devloop::block_best;
+using devloop::clamped_count;
+using devloop::draw3;
+using devloop::mask_clear_kernel;
+using devloop::ranges_kernel;
+using devloop::row_range;
 
 #pragma clang fp contract(off)
 
@@ -40,19 +48,6 @@ struct Intr { double fx, sk, cx, fy, cy; };
 __device__ __forceinline__ Intr load_intr(const double* K, int k_shared, int f) {
     const double* k = K + (k_shared ? 0 : (size_t)f * 9);
     return Intr{k[0], k[1], k[2], k[4], k[5]};
-}
-
-// [begin, end) of frame f, forced into the row table whatever the ranges table holds
-__device__ __forceinline__ void frame_range(const int* ranges, int f, int cap, int& begin, int& end) {
-    int b = ranges[2 * f], e = ranges[2 * f + 1];
-    b = b < 0 ? 0 : (b > cap ? cap : b);
-    e = e < b ? b : (e > cap ? cap : e);
-    begin = b; end = e;
-}
-
-__device__ __forceinline__ int clamped_count(const int* count, int cap) {
-    const int n = *count;
-    return n < 0 ? 0 : (n > cap ? cap : n);
 }
 
 // count_inliers' expression (csrc_host/pnp.cpp): true when the row is an inlier; `add` = what the row adds to the truncated cost
@@ -74,27 +69,6 @@ __device__ __forceinline__ bool row_inlier(const double* ps, double x0, double x
 }
 
 // ---- ranges, prep ------------------------------------------------------------------------------------------------------------------------
-__global__ void ranges_kernel(const long long* b_ids, const int* count, int cap, int F, int* ranges) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    const int n = clamped_count(count, cap);
-    if (!b_ids) {                                 // one frame (F == 1 is checked before the launch)
-        ranges[2 * f] = 0; ranges[2 * f + 1] = f == 0 ? n : 0;
-        return;
-    }
-    int res[2];
-    for (int s = 0; s < 2; ++s) {                 // the first row whose id is >= f + s
-        const long long key = (long long)f + s;
-        int lo = 0, hi = n;
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-            const int mid = lo + (hi - lo) / 2;
-            if (b_ids[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        res[s] = lo;
-    }
-    ranges[2 * f] = res[0]; ranges[2 * f + 1] = res[1] < res[0] ? res[0] : res[1];
-}
-
 __global__ void prep_kernel(const float* pts2d, const float* pts3d, const int* count, int cap, const long long* b_ids, int F, const double* K,
                             int k_shared, double scale, double* rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -122,30 +96,16 @@ __global__ void prep_kernel(const float* pts2d, const float* pts3d, const int* c
 }
 
 // ---- sample ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
 __global__ void sample_kernel(const int* ranges, int cap, int F, int trials, uint64_t seed, int* samples) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
     if (t >= trials) return;
     int begin, end;
-    frame_range(ranges, f, cap, begin, end);
+    row_range(ranges, f, cap, begin, end);
     const int n = end - begin;
     int* o = samples + ((size_t)f * trials + t) * 3;
     if (n < kMinIn) { o[0] = o[1] = o[2] = -1; return; }
-    const uint64_t base = (((uint64_t)f << 32) | (uint64_t)t) * 4ull;
-    const uint64_t G = 0x9E3779B97F4A7C15ull;
-    const int a = (int)(mix64(seed + G * (base + 1ull)) % (uint64_t)n);
-    int b = (int)(mix64(seed + G * (base + 2ull)) % (uint64_t)(n - 1));
-    if (b >= a) ++b;
-    int c = (int)(mix64(seed + G * (base + 3ull)) % (uint64_t)(n - 2));
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    if (c >= lo) ++c;
-    if (c >= hi) ++c;
+    int a, b, c;
+    draw3(seed, f, t, n, a, b, c);
     o[0] = a; o[1] = b; o[2] = c;
 }
 
@@ -225,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void p3p_kernel(const double* rows, const
     double* out = hyps + ((size_t)f * trials + t) * 48;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
     int begin, end;
-    frame_range(ranges, f, cap, begin, end);
+    row_range(ranges, f, cap, begin, end);
     const int n = end - begin;
     const int* s = samples + ((size_t)f * trials + t) * 3;
     const int i0 = s[0], i1 = s[1], i2 = s[2];
@@ -337,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void score_kernel(const double* rows, con
     __shared__ double sh[kChunk][5];
     const int h = blockIdx.x * kThreads + threadIdx.x, f = blockIdx.y;
     int begin, end;
-    frame_range(ranges, f, cap, begin, end);
+    row_range(ranges, f, cap, begin, end);
     const Intr I = load_intr(K, k_shared, f);
     double ps[12];
     bool finite = h < H;
@@ -381,18 +341,6 @@ __device__ __forceinline__ bool better(const Best& a, const Best& b) {      // a
     return a.idx < b.idx;
 }
 
-__device__ __forceinline__ Best block_best(Best mine, Best* sh) {
-    sh[threadIdx.x] = mine;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s && better(sh[threadIdx.x + s], sh[threadIdx.x])) sh[threadIdx.x] = sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const Best r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kThreads) void select_partial_kernel(const int* cnt, const double* cost, int F, int H, int nblk, Best* partial) {
     __shared__ Best sh[kThreads];
     const int f = blockIdx.y, blk = blockIdx.x;
@@ -403,13 +351,8 @@ __global__ __launch_bounds__(kThreads) void select_partial_kernel(const int* cnt
         const Best c{cnt[(size_t)f * H + h], h, cost[(size_t)f * H + h]};
         if (c.cnt > 0 && better(c, mine)) mine = c;
     }
-    const Best r = block_best(mine, sh);
+    const Best r = block_best<kThreads>(mine, sh);
     if (threadIdx.x == 0) partial[(size_t)f * nblk + blk] = r;
-}
-
-__global__ void mask_clear_kernel(const int* count, int cap, unsigned char* mask) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < clamped_count(count, cap)) mask[i] = 0;
 }
 
 __global__ __launch_bounds__(kThreads) void select_final_kernel(const Best* partial, int nblk, const double* rows, const int* ranges, const double* K,
@@ -422,9 +365,9 @@ __global__ __launch_bounds__(kThreads) void select_final_kernel(const Best* part
         const Best c = partial[(size_t)f * nblk + b];
         if (c.idx >= 0 && c.idx < H && better(c, mine)) mine = c;
     }
-    const Best r = block_best(mine, sh);
+    const Best r = block_best<kThreads>(mine, sh);
     int begin, end;
-    frame_range(ranges, f, cap, begin, end);
+    row_range(ranges, f, cap, begin, end);
     const int n = end - begin;
     const int won = r.idx >= 0 ? r.cnt : 0;
     if (threadIdx.x == 0) {
@@ -494,7 +437,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(const double* rows, co
     __shared__ int sh_ok, sh_cnt, sh_changed;
     const int f = blockIdx.x, tid = threadIdx.x;
     int begin, end;
-    frame_range(ranges, f, cap, begin, end);
+    row_range(ranges, f, cap, begin, end);
     const int n = end - begin;
     const int b = best[f];
     const int keep_bits = status[f] & OPPNPD_STATUS_NEEDS_MORE;
@@ -655,8 +598,6 @@ bool sizes_ok(int cap, int F) { return cap >= 1 && cap <= OPPNPD_MAX_ROWS && F >
 bool hyps_ok(int F, long long H) { return H >= 1 && H <= 4ll * OPPNPD_MAX_TRIALS && (long long)F * H <= (1ll << 26); }
 bool thr_ok(double e) { return isfinite(e) && e > 0.0; }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout { size_t ranges, rows, samples, hyps, nsol, cnt, cost, partial, best, total; };
 
 Layout layout_of(int cap, int F, int trials) {
@@ -692,7 +633,7 @@ int oppnpd_ranges(const long long* b_ids, const int* count, int cap, int F, int*
     if (!sizes_ok(cap, F)) return bad_arg(__func__, "table sizes");
     if (!count || !ranges) return bad_arg(__func__, "null pointer");
     if (!b_ids && F != 1) return bad_arg(__func__, "b_ids = NULL means one frame");
-    ranges_kernel<<<blocks_of(F, kThreads), kThreads, 0, (hipStream_t)stream>>>(b_ids, count, cap, F, ranges);
+    ranges_kernel<kThreads><<<blocks_of(F, kThreads), kThreads, 0, (hipStream_t)stream>>>(b_ids, count, cap, F, ranges);
     CAPI_CHECK_LAUNCH();
     return 0;
 }
@@ -747,7 +688,7 @@ int oppnpd_select(const int* cnt, const double* cost, const double* rows, const 
     hipStream_t S = (hipStream_t)stream;
     select_partial_kernel<<<dim3(nblk, F), kThreads, 0, S>>>(cnt, cost, F, H, nblk, (Best*)partial);
     CAPI_CHECK_LAUNCH();
-    mask_clear_kernel<<<blocks_of(cap, kThreads), kThreads, 0, S>>>(count, cap, inlier_mask);
+    mask_clear_kernel<kThreads><<<blocks_of(cap, kThreads), kThreads, 0, S>>>(count, cap, inlier_mask);
     CAPI_CHECK_LAUNCH();
     select_final_kernel<<<F, kThreads, 0, S>>>((const Best*)partial, nblk, rows, ranges, K, k_shared, hyps, cap, F, H, reproj_err_px * reproj_err_px,
                                                confidence, trials, best, n_inliers, status, inlier_mask);

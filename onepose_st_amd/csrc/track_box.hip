@@ -12,34 +12,16 @@
 #include "onepose_pnp_device.h"
 #include "onepose_track.h"
 #include "capi_error.h"
+#include "device_loop.h"
+
+using devloop::fits_int32;
+using devloop::geometry_entry;
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kThreads = 64;                      // one wave
-
-// crop_geometry's expression: entry e = 3 i + j of trans and of K_crop = trans K for box b
-__device__ __forceinline__ void geometry_entry(const int* b, const double* __restrict__ K, int S, int e, double* __restrict__ K_crop,
-                                               double* __restrict__ trans) {
-    const double x0 = (double)b[0], y0 = (double)b[1], x1 = (double)b[2], y1 = (double)b[3];
-    const double wb = x1 - x0, hb = y1 - y0;
-    const double s = (double)S / wb;
-    const int i = e / 3, j = e - 3 * i;
-    double t0, t1, t2;
-    if (i == 0) {
-        t0 = s; t1 = 0.0; t2 = -s * x0;
-    } else if (i == 1) {
-        t0 = 0.0; t1 = s; t2 = 0.5 * (double)S - s * (y0 + 0.5 * hb);
-    } else {
-        t0 = 0.0; t1 = 0.0; t2 = 1.0;
-    }
-    trans[e] = j == 0 ? t0 : (j == 1 ? t1 : t2);
-    K_crop[e] = ((t0 * K[j]) + (t1 * K[3 + j])) + (t2 * K[6 + j]);
-}
-
-// true when v truncates toward zero to an int32 (false for NaN and the infinities)
-__device__ __forceinline__ bool fits_int32(double v) { return v > -2147483649.0 && v < 2147483648.0; }
 
 __global__ __launch_bounds__(kThreads) void box_set_kernel(int x0, int y0, int x1, int y1, const double* __restrict__ K, int S, int* __restrict__ box,
                                                            int* __restrict__ flag, double* __restrict__ K_crop, double* __restrict__ trans) {

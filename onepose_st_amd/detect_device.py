@@ -2,7 +2,7 @@
 the track state of its box -- from the LoFTR matcher's device-side matches, without a host round trip (opt-in; the host vote of
 ``detector.LocalFeatureObjectDetector.match_worker`` with ``pnp.estimate_affine2d`` stays the default).
 
-The work is HIP (``csrc/detect_affine.hip`` in ``libonepose_detect.so``, include/detect/onepose_detect.h).  CPU tensors raise
+The work is HIP (``csrc/detect_affine.hip`` in ``libonepose_detect.so``, include/onepose_detect.h).  CPU tensors raise
 :class:`hip.HipLibraryError` (no CPU fallback).  The specification (DESIGN.md section 6n, written out in the header;
 ``tests/detect_device_oracle.py`` restates it in numpy float64, one function per stage) is the host estimator's model, inlier rule and
 fit with a fixed number of counter-based trials in place of the sequential generator and the adaptive stop:
@@ -26,14 +26,13 @@ Nothing is synchronised or read back: every launch is sized by the capacity.
 from __future__ import annotations
 
 import contextlib
-import ctypes
-import math
 
 import numpy as np
 import torch
 
 from . import cabi, hip
-from .track_device import MAX_CROP, TrackState
+from .pnp_device import check_ransac_options
+from .track_device import MAX_CROP, TrackState, check_crop_size, check_K
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
@@ -50,23 +49,10 @@ STATUS_DEGENERATE = _BINDING.header.defines.get("OPDET_STATUS_DEGENERATE")
 STATUS_NEEDS_MORE = _BINDING.header.defines.get("OPDET_STATUS_NEEDS_MORE")
 
 
-def _stream(stream):
-    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else hip.stream_handle()
-
-
-def _seed(seed):
-    return ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))
-
-
 def _check_options(min_matches, reproj, confidence, trials):
     if int(min_matches) != min_matches or min_matches < 0:
         raise ValueError("min_matches: an integer >= 0")
-    if not (math.isfinite(reproj) and reproj > 0):
-        raise ValueError("ransac_reproj_threshold: a finite number > 0")
-    if not 0 < confidence < 1:
-        raise ValueError("confidence: in (0, 1)")
-    if int(trials) != trials or not 1 <= trials <= MAX_TRIALS:
-        raise ValueError(f"trials: an integer in [1, {MAX_TRIALS}]")
+    check_ransac_options("ransac_reproj_threshold", reproj, confidence, trials, MAX_TRIALS)
 
 
 class _Inputs:
@@ -95,12 +81,8 @@ class _Inputs:
         H, W = (int(v) for v in query_hw)
         if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
             raise ValueError(f"query_hw: (H, W) in [1, {MAX_SIDE}]")
-        if int(crop_size) != crop_size or not 1 <= crop_size <= MAX_CROP:
-            raise ValueError(f"crop_size: an integer in [1, {MAX_CROP}]")
-        if not isinstance(K, torch.Tensor):
-            K = torch.as_tensor(np.ascontiguousarray(np.asarray(K, dtype=np.float64))).to(mkpts0.device)
-        if K.dtype != torch.float64 or K.numel() != 9:
-            raise ValueError("K: float64 [3, 3]")
+        S = check_crop_size(crop_size)
+        K = check_K(K) if isinstance(K, torch.Tensor) else check_K(K).to(mkpts0.device)
         if isinstance(count, torch.Tensor) and (count.dtype != torch.int32 or count.numel() != 1):
             raise ValueError("count: one int32 on the device")
         if not all(t.is_cuda for t in (mkpts0, mkpts1, b_ids, view_hw, K)) or (isinstance(count, torch.Tensor) and not count.is_cuda):
@@ -112,8 +94,8 @@ class _Inputs:
             mkpts0 = mkpts1 = torch.zeros(1, 2, dtype=torch.float32, device=dev)
             b_ids, count = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
         self.mk0, self.mk1, self.b_ids, self.count = mkpts0.contiguous(), mkpts1.contiguous(), b_ids.contiguous(), count
-        self.view_hw, self.K = view_hw.contiguous(), K.contiguous().view(9)
-        self.cap, self.V, self.H, self.W, self.S, self.dev = self.mk0.shape[0], int(view_hw.shape[0]), H, W, int(crop_size), dev
+        self.view_hw, self.K = view_hw.contiguous(), K
+        self.cap, self.V, self.H, self.W, self.S, self.dev = self.mk0.shape[0], int(view_hw.shape[0]), H, W, S, dev
 
 
 class DeviceDetection:
@@ -168,10 +150,10 @@ def vote(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size: int = 512, coun
         winner = torch.empty(1, dtype=torch.int32, device=dev)
         st = TrackState(dev)
         call("opdet_detect", P(a.mk0), P(a.mk1), P(a.b_ids, torch.int64), P(a.count, torch.int32), cap, V, P(a.view_hw, torch.int32), a.H, a.W,
-             P(a.K, torch.float64), a.S, int(min_matches), float(ransac_reproj_threshold), float(confidence), int(trials), _seed(seed), P(ws, None),
+             P(a.K, torch.float64), a.S, int(min_matches), float(ransac_reproj_threshold), float(confidence), int(trials), hip.seed_arg(seed), P(ws, None),
              nbytes, P(boxes, torch.int32), P(n_in, torch.int32), P(affine, torch.float64), P(status, torch.int32), P(mask, torch.uint8),
              P(winner, torch.int32), P(st.box, torch.int32), P(st.flag, torch.int32), P(st.K_crop, torch.float64), P(st.trans, torch.float64),
-             _stream(stream))
+             hip.stream_arg(stream))
     ranges = ws[:8 * V].view(torch.int32).view(V, 2)       # the first table of the workspace
     return DeviceDetection(st, boxes, n_in, affine, status, winner, mask, ranges, keep=(ws, a))
 
@@ -182,7 +164,7 @@ class stages:
     @staticmethod
     def ranges(b_ids, count, cap, views, stream=None):
         out = torch.empty(views, 2, dtype=torch.int32, device=b_ids.device)
-        call("opdet_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(views), hip.ptr(out, torch.int32), _stream(stream))
+        call("opdet_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(views), hip.ptr(out, torch.int32), hip.stream_arg(stream))
         return out
 
     @staticmethod
@@ -192,7 +174,7 @@ class stages:
         samples = torch.empty(V, trials, 3, dtype=torch.int32, device=dev)
         cnt = torch.empty(V, trials, dtype=torch.int32, device=dev)
         call("opdet_score", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), mkpts0.shape[0], V, int(trials), int(min_matches),
-             float(reproj), _seed(seed), hip.ptr(samples, torch.int32), hip.ptr(cnt, torch.int32), _stream(stream))
+             float(reproj), hip.seed_arg(seed), hip.ptr(samples, torch.int32), hip.ptr(cnt, torch.int32), hip.stream_arg(stream))
         return samples, cnt
 
     @staticmethod
@@ -203,7 +185,7 @@ class stages:
         mask = torch.zeros(mkpts0.shape[0], dtype=torch.uint8, device=dev)
         call("opdet_select", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), hip.ptr(count, torch.int32), hip.ptr(samples, torch.int32),
              hip.ptr(cnt, torch.int32), mkpts0.shape[0], V, trials, int(min_matches), float(reproj), float(confidence), hip.ptr(best, torch.int32),
-             hip.ptr(n_in, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), _stream(stream))
+             hip.ptr(n_in, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
         return best, n_in, status, mask
 
     @staticmethod
@@ -214,7 +196,7 @@ class stages:
         boxes = torch.empty(V, 4, dtype=torch.int32, device=dev)
         call("opdet_fit_box", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), hip.ptr(view_hw, torch.int32), mkpts0.shape[0], V,
              int(query_hw[0]), int(query_hw[1]), hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8),
-             hip.ptr(affine, torch.float64), hip.ptr(boxes, torch.int32), _stream(stream))
+             hip.ptr(affine, torch.float64), hip.ptr(boxes, torch.int32), hip.stream_arg(stream))
         return affine, boxes
 
     @staticmethod
@@ -226,5 +208,5 @@ class stages:
         K = K.contiguous().view(9)
         call("opdet_vote", hip.ptr(boxes, torch.int32), hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), boxes.shape[0], int(query_hw[0]),
              int(query_hw[1]), hip.ptr(K, torch.float64), int(crop_size), hip.ptr(winner, torch.int32), hip.ptr(st.box, torch.int32),
-             hip.ptr(st.flag, torch.int32), hip.ptr(st.K_crop, torch.float64), hip.ptr(st.trans, torch.float64), _stream(stream))
+             hip.ptr(st.flag, torch.int32), hip.ptr(st.K_crop, torch.float64), hip.ptr(st.trans, torch.float64), hip.stream_arg(stream))
         return winner, st

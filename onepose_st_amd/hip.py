@@ -81,6 +81,16 @@ def stream_handle():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def stream_arg(stream):
+    """The handle of ``stream`` (a ``torch.cuda.Stream``); ``None``: the current stream"""
+    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else stream_handle()
+
+
+def seed_arg(seed):
+    """An ``unsigned long long`` seed: ``seed`` mod 2^64"""
+    return ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))
+
+
 def need_device(named) -> None:
     """``named``: (name, value) pairs.  Every value is a tensor, and then every one of them lies on the device."""
     for name, t in named:

@@ -32,7 +32,6 @@ Nothing is synchronised and the match count is never read on the host: every lau
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import math
 
 import numpy as np
@@ -55,10 +54,6 @@ STATUS_NO_POSE = _BINDING.header.defines.get("OPPNPD_STATUS_NO_POSE")
 STATUS_NEEDS_MORE = _BINDING.header.defines.get("OPPNPD_STATUS_NEEDS_MORE")
 MIN_INLIERS = _BINDING.header.defines.get("OPPNPD_MIN_INLIERS")
 MAX_NEEDED = _BINDING.header.defines.get("OPPNPD_MAX_NEEDED")
-
-
-def _stream(stream):
-    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else hip.stream_handle()
 
 
 def _check_policy(solver, use_pycolmap_ransac) -> None:
@@ -117,15 +112,21 @@ class _Inputs:
         self.dev = dev
 
 
+def check_ransac_options(reproj_name, reproj, confidence, trials, max_trials):
+    """The options this estimator and ``detect_device``'s share: the inlier threshold (under the caller's name for it), the confidence
+    and the number of trials"""
+    if not (math.isfinite(reproj) and reproj > 0):
+        raise ValueError(f"{reproj_name}: a finite number > 0")
+    if not 0 < confidence < 1:
+        raise ValueError("confidence: in (0, 1)")
+    if int(trials) != trials or not 1 <= trials <= max_trials:
+        raise ValueError(f"trials: an integer in [1, {max_trials}]")
+
+
 def _check_options(scale, reproj, confidence, trials):
     if not (math.isfinite(scale) and scale > 0):
         raise ValueError("scale: a finite number > 0")
-    if not (math.isfinite(reproj) and reproj > 0):
-        raise ValueError("pnp_reprojection_error: a finite number > 0")
-    if not 0 < confidence < 1:
-        raise ValueError("confidence: in (0, 1)")
-    if int(trials) != trials or not 1 <= trials <= MAX_TRIALS:
-        raise ValueError(f"trials: an integer in [1, {MAX_TRIALS}]")
+    check_ransac_options("pnp_reprojection_error", reproj, confidence, trials, MAX_TRIALS)
 
 
 class DevicePoses:
@@ -199,8 +200,8 @@ def ransac_pnp(K, pts_2d, pts_3d, *, count=None, b_ids=None, frames=1, scale=1, 
         mask = torch.zeros(cap, dtype=torch.uint8, device=dev)
         P = hip.ptr
         call("oppnpd_solve", P(a.pts_2d), P(a.pts_3d), P(a.count, torch.int32), cap, P(a.b_ids, torch.int64), F, P(a.K, torch.float64), a.k_shared,
-             float(scale), float(pnp_reprojection_error), float(confidence), int(trials), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), P(ws, None),
-             nbytes, P(pose, torch.float64), P(n_in, torch.int32), P(status, torch.int32), P(mask, torch.uint8), _stream(stream))
+             float(scale), float(pnp_reprojection_error), float(confidence), int(trials), hip.seed_arg(seed), P(ws, None),
+             nbytes, P(pose, torch.float64), P(n_in, torch.int32), P(status, torch.int32), P(mask, torch.uint8), hip.stream_arg(stream))
     ranges = ws[:8 * F].view(torch.int32).view(F, 2)       # the first table of the workspace
     return DevicePoses(pose, n_in, status, mask, ranges, keep=(ws, a))
 
@@ -230,7 +231,7 @@ class stages:
     @staticmethod
     def ranges(b_ids, count, cap, frames, stream=None):
         out = torch.empty(frames, 2, dtype=torch.int32, device=count.device)
-        call("oppnpd_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(frames), hip.ptr(out, torch.int32), _stream(stream))
+        call("oppnpd_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(frames), hip.ptr(out, torch.int32), hip.stream_arg(stream))
         return out
 
     @staticmethod
@@ -239,15 +240,15 @@ class stages:
         cap = pts_2d.shape[0]
         rows = torch.zeros(cap, ROW_DOUBLES, dtype=torch.float64, device=pts_2d.device)
         call("oppnpd_prep", hip.ptr(pts_2d), hip.ptr(pts_3d), hip.ptr(count, torch.int32), cap, hip.ptr(b_ids, torch.int64), int(frames),
-             hip.ptr(K, torch.float64), int(K.shape[0] == 1), float(scale), hip.ptr(rows, torch.float64), _stream(stream))
+             hip.ptr(K, torch.float64), int(K.shape[0] == 1), float(scale), hip.ptr(rows, torch.float64), hip.stream_arg(stream))
         return rows
 
     @staticmethod
     def sample(ranges, trials, seed, stream=None):
         F = ranges.shape[0]
         out = torch.empty(F, trials, 3, dtype=torch.int32, device=ranges.device)
-        call("oppnpd_sample", hip.ptr(ranges, torch.int32), F, int(trials), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), hip.ptr(out, torch.int32),
-             _stream(stream))
+        call("oppnpd_sample", hip.ptr(ranges, torch.int32), F, int(trials), hip.seed_arg(seed), hip.ptr(out, torch.int32),
+             hip.stream_arg(stream))
         return out
 
     @staticmethod
@@ -256,7 +257,7 @@ class stages:
         hyps = torch.empty(F, 4 * trials, 3, 4, dtype=torch.float64, device=rows.device)
         nsol = torch.empty(F, trials, dtype=torch.int32, device=rows.device)
         call("oppnpd_p3p", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(samples, torch.int32), rows.shape[0], F, trials,
-             hip.ptr(hyps, torch.float64), hip.ptr(nsol, torch.int32), _stream(stream))
+             hip.ptr(hyps, torch.float64), hip.ptr(nsol, torch.int32), hip.stream_arg(stream))
         return hyps, nsol
 
     @staticmethod
@@ -266,7 +267,7 @@ class stages:
         cnt = torch.empty(F, H, dtype=torch.int32, device=rows.device)
         cost = torch.empty(F, H, dtype=torch.float64, device=rows.device)
         call("oppnpd_score", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1),
-             hip.ptr(hyps, torch.float64), rows.shape[0], F, H, float(reproj), hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), _stream(stream))
+             hip.ptr(hyps, torch.float64), rows.shape[0], F, H, float(reproj), hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.stream_arg(stream))
         return cnt, cost
 
     @staticmethod
@@ -280,7 +281,7 @@ class stages:
         call("oppnpd_select", hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32),
              hip.ptr(count, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1), hip.ptr(hyps, torch.float64), rows.shape[0], F, H,
              float(reproj), float(confidence), int(trials), hip.ptr(partial, None), hip.ptr(best, torch.int32), hip.ptr(n_in, torch.int32),
-             hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), _stream(stream))
+             hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
         return best, n_in, status, mask
 
     @staticmethod
@@ -291,5 +292,5 @@ class stages:
         pose = torch.empty(F, 3, 4, dtype=torch.float64, device=rows.device)
         call("oppnpd_refine", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1),
              hip.ptr(hyps, torch.float64), hip.ptr(best, torch.int32), rows.shape[0], F, H, float(reproj), float(scale), hip.ptr(pose, torch.float64),
-             hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), _stream(stream))
+             hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
         return pose

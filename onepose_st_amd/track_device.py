@@ -61,23 +61,28 @@ class TrackState:
         return TrackState.unpack(self.blob.cpu().numpy())
 
 
+def check_K(K) -> torch.Tensor:
+    """The intrinsics as float64 ``[9]``: a tensor where it lies, host numbers as a host tensor"""
+    if not isinstance(K, torch.Tensor):
+        K = torch.as_tensor(np.ascontiguousarray(np.asarray(K, dtype=np.float64)))
+    if K.dtype != torch.float64 or K.numel() != 9:
+        raise ValueError("K: float64 [3, 3]")
+    return K.contiguous().view(9)
+
+
 def _device_K(K, device):
-    """float64 ``[9]`` on the device: a device tensor as it is, host numbers uploaded"""
+    """:func:`check_K` on the device: a device tensor as it is, host numbers uploaded"""
     if isinstance(K, torch.Tensor):
         if not K.is_cuda:
             raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
-        if K.dtype != torch.float64 or K.numel() != 9:
-            raise ValueError("K: float64 [3, 3]")
-        return K.contiguous().view(9)
-    K = np.asarray(K, dtype=np.float64)
-    if K.size != 9:
-        raise ValueError("K: float64 [3, 3]")
+        return check_K(K)
+    K = check_K(K)
     if device is None or torch.device(device).type != "cuda":
         raise hip.HipLibraryError("the HIP path needs a HIP device (no CPU fallback)")
-    return torch.as_tensor(np.ascontiguousarray(K.reshape(9))).to(device)
+    return K.to(device)
 
 
-def _crop_size(crop_size) -> int:
+def check_crop_size(crop_size) -> int:
     if int(crop_size) != crop_size or not 1 <= crop_size <= MAX_CROP:
         raise ValueError(f"crop_size: an integer in [1, {MAX_CROP}]")
     return int(crop_size)
@@ -89,7 +94,7 @@ def set_box(bbox, K, crop_size: int = 512, device=None) -> TrackState:
     x0, y0, x1, y1 = [int(v) for v in bbox]
     if not all(-2 ** 31 <= v < 2 ** 31 for v in (x0, y0, x1, y1)):
         raise ValueError("bbox: four int32")
-    S = _crop_size(crop_size)
+    S = check_crop_size(crop_size)
     if isinstance(K, torch.Tensor) and K.is_cuda:
         device = K.device
     Kd = _device_K(K, device)
@@ -120,7 +125,7 @@ def next_box(poses, prev_state: TrackState, K, bbox3d, *, frame: int = 0, min_in
         raise ValueError("min_inliers: an integer >= 0")
     if bbox3d.dtype != torch.float64 or tuple(bbox3d.shape) != (8, 3):
         raise ValueError("bbox3d: float64 [8, 3]")
-    S = _crop_size(crop_size)
+    S = check_crop_size(crop_size)
     Kd = _device_K(K, bbox3d.device)
     bbox3d = bbox3d.contiguous()
     pose = poses.pose[frame].contiguous()
@@ -139,7 +144,7 @@ def crop(frame_u8: torch.Tensor, state: TrackState, crop_size: int = 512) -> tor
     ``state``, bit for bit; an empty box gives zeros."""
     if not isinstance(frame_u8, torch.Tensor) or frame_u8.dtype != torch.uint8 or frame_u8.dim() != 2 or not frame_u8.is_cuda:
         raise hip.HipLibraryError("crop needs a uint8 [H, W] frame on the HIP device (no CPU fallback)")
-    S = _crop_size(crop_size)
+    S = check_crop_size(crop_size)
     frame_u8 = frame_u8.contiguous()
     out = torch.empty(1, 1, S, S, dtype=torch.float32, device=frame_u8.device)
     with torch.cuda.device(frame_u8.device):

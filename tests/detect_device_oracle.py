@@ -1,4 +1,4 @@
-"""The device detection's specification (include/detect/onepose_detect.h, DESIGN.md section 6n, ``onepose_st_amd/detect_device.py``) restated
+"""The device detection's specification (include/onepose_detect.h, DESIGN.md section 6n, ``onepose_st_amd/detect_device.py``) restated
 in numpy float64, one function per stage.  Elementwise numpy arithmetic only where rows or trials are independent (each element is the
 scalar expression in the written order); every sum of the fit is a Python loop in the header's order.  The package does not import
 this file.
@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pnp_device_oracle as pnp_orc  # noqa: E402
 import track_device_oracle as trk_orc  # noqa: E402
 
-G, M64, mix = pnp_orc.G, pnp_orc.M64, pnp_orc.mix
+M64 = pnp_orc.M64
 STATUS_NO_MODEL, STATUS_DEGENERATE, STATUS_NEEDS_MORE = 1, 2, 4
 THREADS = 256
 IDENTITY = np.array([1.0, 0, 0, 0, 1.0, 0])
@@ -33,19 +33,6 @@ def trial_floor(min_matches):
 
 
 # ---- sample ----------------------------------------------------------------------------------------------------------------------------------
-def sample_one(seed, v, t, n):
-    """three distinct view-local rows of trial t of view v (n >= 3)"""
-    base = (((v << 32) | t) * 4) & M64
-    picks = []
-    for k in range(3):
-        r = mix((seed + G * ((base + k + 1) & M64)) & M64) % (n - k)
-        for p in sorted(picks):
-            if r >= p:
-                r += 1
-        picks.append(r)
-    return tuple(picks)
-
-
 def sample(rng, trials, seed, min_matches=6):
     V = rng.shape[0]
     out = np.full((V, trials, 3), -1, dtype=np.int32)
@@ -54,7 +41,7 @@ def sample(rng, trials, seed, min_matches=6):
         if n < trial_floor(min_matches):
             continue
         for t in range(trials):
-            out[v, t] = sample_one(seed & M64, v, t, n)
+            out[v, t] = pnp_orc.draw3(seed & M64, v, t, n)          # the one sampler: the view in place of the frame
     return out
 
 

@@ -72,11 +72,9 @@ def mix(z):
     return z
 
 
-def sample_one(seed, f, t, n):
-    """three distinct frame-local rows of trial t of frame f, or (-1, -1, -1) when n < 4"""
-    if n < MIN_INLIERS:
-        return (-1, -1, -1)
-    base = (((f << 32) | t) * 4) & M64
+def draw3(seed, g, t, n):
+    """three distinct group-local rows of trial t of group g (a frame here, a view in the detection), n >= 3"""
+    base = (((g << 32) | t) * 4) & M64
     picks = []
     for k in range(3):
         r = mix((seed + G * ((base + k + 1) & M64)) & M64) % (n - k)
@@ -85,6 +83,11 @@ def sample_one(seed, f, t, n):
                 r += 1
         picks.append(r)
     return tuple(picks)
+
+
+def sample_one(seed, f, t, n):
+    """:func:`draw3` of trial t of frame f, or (-1, -1, -1) when n < 4"""
+    return draw3(seed, f, t, n) if n >= MIN_INLIERS else (-1, -1, -1)
 
 
 def sample(rng, trials, seed):

@@ -1,7 +1,8 @@
 """The Python bindings take every C signature, constant and structure layout from ``include/*.h`` (``onepose_st_amd/cabi.py``).
 CPU only: the reader on the real headers and on made-up ones, the structure mirrors, ``cabi.Binding`` (arity check, error mapping, load
-errors) on stand-in handles and on the built libraries for every entry of ``cabi.LIBRARIES``, and three faults seeded into copies of the
-header that the prototypes written out below must catch."""
+errors) on stand-in handles and on the built libraries for every row of ``cabi.LIBRARIES`` (the table-driven tests below: one case per
+row, and one hand-written rejected call per satellite library in ``REJECTED``), and three faults seeded into copies of the header that
+the prototypes written out below must catch."""
 import ctypes
 import glob
 import importlib
@@ -345,14 +346,16 @@ def test_the_table_of_libraries_is_complete():
         assert len(set(column)) == len(cabi.LIBRARIES)              # no header, prefix, file, variable or module twice
     for entry in cabi.LIBRARIES:
         mod, binding = importlib.import_module(f"onepose_st_amd.{entry.module}"), BINDINGS[entry.module]
-        assert (binding.so, binding.prefix, os.path.basename(binding.header_path)) == (entry.so, entry.prefix, entry.header)
+        assert (binding.so, binding.prefix, binding.header_path) == (entry.so, entry.prefix, os.path.join(REPO, "include", entry.header))
         assert (mod.load, mod.call, mod.library_path) == (binding.load, binding.call, binding.library_path)
         assert mod.EXPORTED_SYMBOLS is binding.exported_symbols and mod.ABI_VERSION == binding.abi_version and isinstance(mod.ABI_VERSION, int)
         assert hasattr(mod, "check_arity") or entry.module == "hip"
         assert mod.EXPORTED_SYMBOLS and all(s.startswith(entry.prefix + "_") for s in mod.EXPORTED_SYMBOLS)
         assert {f"{entry.prefix}_abi_version", f"{entry.prefix}_last_error"} <= set(mod.EXPORTED_SYMBOLS)
         text = open(binding.header_path).read()
-        assert set(mod.EXPORTED_SYMBOLS) == set(re.findall(rf"\b({entry.prefix}_\w+)\s*\(", text))     # no other library's prefix in it
+        assert set(mod.EXPORTED_SYMBOLS) == set(re.findall(rf"\b({entry.prefix}_\w+)\s*\(", text))
+        others = "|".join(e.prefix for e in cabi.LIBRARIES if e is not entry)                        # no other library's prefix in it
+        assert not re.findall(rf"\b(?:{others})_\w+\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 
 _PTR = ctypes.c_void_p(8)        # not null and never followed: the entries below return before they launch anything
@@ -366,6 +369,7 @@ REJECTED = {
     "pnp_device": ("oppnpd_ranges", {"cap": 1}, "oppnpd_ranges: table sizes"),
     "track_device": ("optrk_box_set", {"x1": 1, "y1": 1, "K": _PTR, "S": 0, "box": _PTR, "flag": _PTR, "K_crop": _PTR, "trans": _PTR},
                      "optrk_box_set: crop size S outside [1, OPTRK_MAX_CROP]"),
+    "detect_device": ("opdet_ranges", {"cap": 1}, "opdet_ranges: table sizes"),
 }
 
 
@@ -381,16 +385,21 @@ def test_the_built_libraries_answer_for_themselves():
     def last_error(module):
         return getattr(BINDINGS[module].load(), f"{BINDINGS[module].prefix}_last_error")().decode()
 
-    for module, (name, given, text) in REJECTED.items():
+    def reject(module):
+        name, given, text = REJECTED[module]
         mod, params = importlib.import_module(f"onepose_st_amd.{module}"), BINDINGS[module].header.prototypes[name].params
         assert set(given) <= {n for _, n in params}
         args = [given.get(n, None if c.endswith("*") else 0) for c, n in params]
         with pytest.raises(ValueError) as e:
             mod.call(name, *args)
         assert str(e.value) == f"{name}: {text}" and last_error(module) == text
+
+    for module, (_, _, text) in REJECTED.items():
+        reject(module)
         hip.call("ophip_timing_every", 1)                           # a correct call into another library (host side only)
         assert last_error(module) == text
-    for module, (_, _, text) in REJECTED.items():                   # and the five rejections that followed in other libraries
+    reject(next(iter(REJECTED)))                                    # so that the last row too has seen a rejection in another library
+    for module, (_, _, text) in REJECTED.items():                   # and the rejections that followed in the other six
         assert last_error(module) == text
 
 

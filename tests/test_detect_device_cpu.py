@@ -2,7 +2,6 @@
 rules of the vote in the oracle, and the binding: the header parses, arities are checked, arguments are refused before the library is
 loaded."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -11,7 +10,6 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import detect_device_oracle as orc  # noqa: E402
-import test_cabi_binding as tcb  # noqa: E402
 
 from onepose_st_amd import cabi, detect_device, detector, hip, pnp  # noqa: E402
 from onepose_st_amd import frameloop as fl  # noqa: E402
@@ -80,8 +78,8 @@ def test_binding_reads_the_header_and_checks_arguments_before_loading(monkeypatc
     assert (dd.STATUS_NO_MODEL, dd.STATUS_DEGENERATE, dd.STATUS_NEEDS_MORE) == (orc.STATUS_NO_MODEL, orc.STATUS_DEGENERATE, orc.STATUS_NEEDS_MORE)
     assert set(dd.EXPORTED_SYMBOLS) == {"opdet_abi_version", "opdet_last_error", "opdet_workspace_bytes", "opdet_ranges", "opdet_score", "opdet_select",
                                         "opdet_fit_box", "opdet_vote", "opdet_detect"}
-    entry, = [e for e in cabi.EXTRA_LIBRARIES if e.module == "detect_device"]
-    assert (entry.prefix, entry.header, entry.so, entry.env) == ("opdet", "detect/onepose_detect.h", "libonepose_detect.so", "OPDET_LIB")
+    entry, = [e for e in cabi.LIBRARIES if e.module == "detect_device"]
+    assert (entry.prefix, entry.header, entry.so, entry.env) == ("opdet", "onepose_detect.h", "libonepose_detect.so", "OPDET_LIB")
     with pytest.raises(TypeError, match="takes 29 arguments"):
         dd.check_arity("opdet_detect", (1, 2, 3))
     with pytest.raises(TypeError, match="takes 6 arguments"):
@@ -107,42 +105,6 @@ def test_binding_reads_the_header_and_checks_arguments_before_loading(monkeypatc
         dd.vote(**{**good, "mkpts0": np.zeros((8, 2), np.float32)})
     with pytest.raises(hip.HipLibraryError, match="no CPU fallback"):           # well-formed CPU tensors: refused, never computed on the host
         dd.vote(**good)
-
-
-def test_the_per_row_checks_of_the_binding_table_hold_for_the_detection_library(monkeypatch):
-    """``cabi.EXTRA_LIBRARIES`` is bound like a row of ``cabi.LIBRARIES``: what ``tests/test_cabi_binding.py`` checks for every row, here
-    for this library -- its parametrised tests called with this binding, the table's columns, and one rejected call of the built
-    library whose error text stays its own."""
-    dd = detect_device
-    entry, = cabi.EXTRA_LIBRARIES
-    binding = dd._BINDING
-    monkeypatch.setitem(tcb.BINDINGS, entry.module, binding)
-    tcb.test_every_binding_checks_the_number_of_arguments(entry.module, monkeypatch)
-    tcb.test_call_maps_the_status_to_an_exception(entry.module, monkeypatch)
-    tcb.test_abi_mismatch_is_reported_by_load(entry.module, monkeypatch)
-    monkeypatch.undo()
-    monkeypatch.setitem(tcb.BINDINGS, entry.module, binding)
-    tcb.test_missing_header_is_reported_by_load(entry)
-    # the table: nothing twice over both tables, the header where the row says, the module's names are the binding's
-    rows = cabi.LIBRARIES + cabi.EXTRA_LIBRARIES
-    for column in zip(*rows):
-        assert len(set(column)) == len(rows)
-    assert os.path.exists(os.path.join(tcb.REPO, "include", entry.header)) and binding.header_path == os.path.join(tcb.REPO, "include", entry.header)
-    assert (binding.so, binding.prefix) == (entry.so, entry.prefix)
-    assert (dd.load, dd.call, dd.library_path, dd.check_arity) == (binding.load, binding.call, binding.library_path, binding.check_arity)
-    assert dd.EXPORTED_SYMBOLS is binding.exported_symbols and dd.ABI_VERSION == binding.abi_version == 1
-    text = open(binding.header_path).read()
-    assert set(dd.EXPORTED_SYMBOLS) == set(re.findall(r"\b(opdet_\w+)\s*\(", text))
-    assert not re.findall(r"\b(?:ophip|opsfm|opsft|opstr|opsff|oppnpd|optrk)_\w+\s*\(", cabi.re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    # the built library: its ABI number, a rejected call, and its own error text after a call into another library
-    assert dd.load().opdet_abi_version() == dd.ABI_VERSION and dd.load() is binding.handle
-    with pytest.raises(ValueError) as e:
-        dd.call("opdet_ranges", None, None, 1, 0, None, None)
-    assert str(e.value) == "opdet_ranges: opdet_ranges: table sizes" and dd.load().opdet_last_error().decode() == "opdet_ranges: table sizes"
-    hip.call("ophip_timing_every", 1)
-    with pytest.raises(ValueError):
-        tcb.importlib.import_module("onepose_st_amd.pnp_device").call("oppnpd_ranges", None, None, 1, 0, None, None)
-    assert dd.load().opdet_last_error().decode() == "opdet_ranges: table sizes"
 
 
 class _NoState:

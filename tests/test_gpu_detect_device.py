@@ -97,6 +97,34 @@ def test_ranges_and_samples_equal_the_oracle(dd, seed):
     assert np.array_equal(host(dd.stages.ranges(dev_t(ids), dev_t(np.array([-4], dtype=np.int32)), cap, V)), np.zeros((V, 2), np.int32))
 
 
+@pytest.mark.parametrize("seed", [1, 2 ** 64 - 5])
+def test_ranges_and_sampler_are_the_pnp_librarys(dd, seed):
+    """One range rule and one sampler in both libraries (``csrc/device_loop.h``): on an ascending table of 4, 5, 64, 65 and 257 rows per
+    id, ``pnp_device``'s and this library's ranges are equal tables, and the draws of ``oppnpd_sample`` and of the fused
+    ``opdet_score`` are equal and the oracle's -- all integers, compared exactly.  Every id keeps at least 4 rows, so both floors (4
+    there, max(min_matches, 3) = 3 here) let every trial run; 4 and 5 rows step past the earlier picks, 64 / 65 cross a wave, 257 a
+    staging chunk, 300 trials the 256-trial workgroup.  ``count``: NULL (every row; ``oppnpd_ranges`` takes no NULL and gets the
+    capacity), the capacity, and one that cuts the last id short."""
+    from onepose_st_amd import pnp_device
+    rows, trials = (4, 5, 64, 65, 257), 300
+    G = len(rows)
+    ids = np.concatenate([np.full(n, g) for g, n in enumerate(rows)]).astype(np.int64)
+    cap = len(ids)
+    gen = np.random.default_rng(5)
+    mk0, mk1 = dev_t(gen.uniform(0, 600, (cap, 2)).astype(np.float32)), dev_t(gen.uniform(0, 600, (cap, 2)).astype(np.float32))
+    for count in (None, cap, cap - 100):
+        n = cap if count is None else count
+        r_pnp = pnp_device.stages.ranges(dev_t(ids), dev_t(np.array([n], dtype=np.int32)), cap, G)
+        r_det = dd.stages.ranges(dev_t(ids), None if count is None else dev_t(np.array([count], dtype=np.int32)), cap, G)
+        want_r = orc.pnp_orc.ranges(ids, n, cap, G)
+        assert torch.equal(r_pnp, r_det) and r_det.dtype == torch.int32 and np.array_equal(host(r_det), want_r)
+        assert (want_r[:, 1] - want_r[:, 0]).tolist() == [*rows[:-1], rows[-1] - (cap - n)]
+        s_pnp = pnp_device.stages.sample(r_pnp, trials, seed)
+        s_det, _ = dd.stages.score(mk0, mk1, r_det, trials, seed, min_matches=0)
+        assert torch.equal(s_pnp, s_det) and s_det.dtype == torch.int32
+        assert np.array_equal(host(s_det), orc.pnp_orc.sample(want_r, trials, seed)) and (host(s_det) >= 0).all()
+
+
 # ---- score and select ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("trials", [1, 256, 300])
 @pytest.mark.parametrize("rows", [(6,), (257,), (255, 256, 257), (256, 6, 255)], ids=lambda r: "x".join(map(str, r)))
