@@ -1,11 +1,13 @@
-"""Keypoint-free SfM post-optimisation: first-order depth refinement on the device.
+"""Keypoint-free SfM post-optimisation: depth refinement on the device, first-order (the reference's) and second-order.
 
 The reference (src/KeypointFreeSfM/post_optimization/optimizer/optimizer.py) refines the depth of every 3D point of a new object's
 map with a Python loop of up to 1 000 float64 autograd + Adam steps (first_order_solver.py:6-172) over the residual of
 residual.py:6-78.  Here the whole loop is HIP (``csrc/postopt.hip``): one prep kernel folds every residual row into
 ``h(d) = d * a + b``, then one step kernel per Adam step, enqueued with no synchronisation between steps, with the early stop decided
-on the device.  Also here: the caller's depth-to-world and reprojection updates (dataset/coarse_colmap_dataset.py:353-423), and
-float64 restatements of pytorch3d's ``so3_exp_map`` / ``so3_log_map`` (pytorch3d is not a dependency).
+on the device.  ``refine_depths_lm`` is the second-order solver the reference's configs ask for and the reference cannot run: one
+Levenberg-Marquardt solve per track, all in one launch (``csrc/postopt_lm.hip``, its own library).  Also here: the caller's
+depth-to-world and reprojection updates (dataset/coarse_colmap_dataset.py:353-423), and float64 restatements of pytorch3d's
+``so3_exp_map`` / ``so3_log_map`` (pytorch3d is not a dependency).
 
 Device tensors only: CPU inputs raise :class:`hip.HipLibraryError`.  COLMAP I/O and feature aggregation stay with the
 caller; the triangulation is ``sfm_triangulate``'s.
@@ -107,22 +109,8 @@ def adam_step_table(lr: float, max_steps: int, betas=ADAM_BETAS) -> list:
     return out
 
 
-def refine_depths(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: torch.Tensor, intrinsic1: torch.Tensor,
-                  mkpts0_c: torch.Tensor, mkpts1_f: torch.Tensor, left_pose_idx: torch.Tensor, right_pose_idx: torch.Tensor,
-                  angle_axis_to_world: torch.Tensor, lr: float = 3e-2, max_steps: int = MAX_STEPS, mode: str = "geometry_error",
-                  return_residuals: bool = False) -> dict:
-    """The reference's FirstOrderSolve of the depth procedure on flat arrays (the data loader's padding removed).
-
-    depth [P, 1] (or [P]); n_query [P] rows per track, each >= 1, rows laid out track after track; intrinsic0 / intrinsic1 [L, 3, 3];
-    mkpts0_c / mkpts1_f [L, 2]; left_pose_idx / right_pose_idx [L] into angle_axis_to_world [F, 6].  Everything is taken as float64.
-
-    Returns ``{"depth": [P, 1] float64, "initial_residual": l_0, "final_residual": l of the last executed step (the reference's quirk),
-    "steps": steps run, "loss": [steps] float64}`` plus ``"residuals"`` [L, 2] of the last evaluated depths when asked."""
-    if mode != "geometry_error":
-        raise NotImplementedError
-    if int(max_steps) < 1:
-        raise ValueError("max_steps must be >= 1")
-    max_steps = int(max_steps)
+def _flat_problem(depth, n_query, intrinsic0, intrinsic1, mkpts0_c, mkpts1_f, left_pose_idx, right_pose_idx, angle_axis_to_world):
+    """The validation and flat layout both solvers share: -> (d [P] (a copy), offs [P + 1], K0, K1, mk0, mk1, li, ri, aa, P, L, F)."""
     if not isinstance(n_query, torch.Tensor) or not n_query.is_cuda or not depth.is_cuda:
         raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
     d = _dev64(depth.reshape(-1, 1), "depth", (1,)).reshape(-1).clone()
@@ -144,6 +132,27 @@ def refine_depths(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: torch.
     ri = _dev_index(right_pose_idx, "right_pose_idx", L, F)
     offs = torch.zeros(P + 1, dtype=torch.int64, device=d.device)
     offs[1:] = torch.cumsum(nq.to(d.device), 0)
+    return d, offs, K0, K1, mk0, mk1, li, ri, aa, P, L, F
+
+
+def refine_depths(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: torch.Tensor, intrinsic1: torch.Tensor,
+                  mkpts0_c: torch.Tensor, mkpts1_f: torch.Tensor, left_pose_idx: torch.Tensor, right_pose_idx: torch.Tensor,
+                  angle_axis_to_world: torch.Tensor, lr: float = 3e-2, max_steps: int = MAX_STEPS, mode: str = "geometry_error",
+                  return_residuals: bool = False) -> dict:
+    """The reference's FirstOrderSolve of the depth procedure on flat arrays (the data loader's padding removed).
+
+    depth [P, 1] (or [P]); n_query [P] rows per track, each >= 1, rows laid out track after track; intrinsic0 / intrinsic1 [L, 3, 3];
+    mkpts0_c / mkpts1_f [L, 2]; left_pose_idx / right_pose_idx [L] into angle_axis_to_world [F, 6].  Everything is taken as float64.
+
+    Returns ``{"depth": [P, 1] float64, "initial_residual": l_0, "final_residual": l of the last executed step (the reference's quirk),
+    "steps": steps run, "loss": [steps] float64}`` plus ``"residuals"`` [L, 2] of the last evaluated depths when asked."""
+    if mode != "geometry_error":
+        raise NotImplementedError
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1")
+    max_steps = int(max_steps)
+    d, offs, K0, K1, mk0, mk1, li, ri, aa, P, L, F = _flat_problem(depth, n_query, intrinsic0, intrinsic1, mkpts0_c, mkpts1_f, left_pose_idx,
+                                                                   right_pose_idx, angle_axis_to_world)
     table = torch.tensor(adam_step_table(float(lr), max_steps), dtype=torch.float64, device=d.device)
     loss = torch.empty(max_steps, dtype=torch.float64, device=d.device)
     steps = torch.zeros(1, dtype=torch.int32, device=d.device)
@@ -159,6 +168,51 @@ def refine_depths(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: torch.
     hist = loss[:n]
     lh = hist.tolist()
     out = {"depth": d.reshape(P, 1), "initial_residual": lh[0], "final_residual": lh[-1], "steps": n, "loss": hist}
+    if return_residuals:
+        out["residuals"] = resid
+    return out
+
+
+LM_DEFAULTS = dict(lam0=1e-4, up=10.0, down=0.1, lam_min=1e-12, lam_max=1e12, step_tol=1e-8)
+
+
+def refine_depths_lm(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: torch.Tensor, intrinsic1: torch.Tensor,
+                     mkpts0_c: torch.Tensor, mkpts1_f: torch.Tensor, left_pose_idx: torch.Tensor, right_pose_idx: torch.Tensor,
+                     angle_axis_to_world: torch.Tensor, max_iters: int = 50, lam0: float = LM_DEFAULTS["lam0"],
+                     up: float = LM_DEFAULTS["up"], down: float = LM_DEFAULTS["down"], lam_min: float = LM_DEFAULTS["lam_min"],
+                     lam_max: float = LM_DEFAULTS["lam_max"], step_tol: float = LM_DEFAULTS["step_tol"],
+                     return_residuals: bool = False) -> dict:
+    """The second-order solver of the same problem as :func:`refine_depths` (same arguments, validation and flat layout): one scalar
+    Levenberg-Marquardt solve per track, all iterations of all tracks in one launch of ``csrc/postopt_lm.hip``.
+
+    Returns ``{"depth": [P, 1] float64, "iterations" / "rejects" / "status": [P] int32 (``postopt_lm.CONVERGED`` ...), "lambda" /
+    "initial_cost" / "final_cost": [P] float64, "initial_residual" / "final_residual": the per-track costs summed on the device in a
+    fixed order, "steps": the largest iteration count}`` plus ``"residuals"`` [L, 2] at the returned depths when asked."""
+    from . import postopt_lm
+
+    max_iters = int(max_iters)
+    if max_iters < 0:
+        raise ValueError("max_iters must be >= 0")
+    d, offs, K0, K1, mk0, mk1, li, ri, aa, P, L, F = _flat_problem(depth, n_query, intrinsic0, intrinsic1, mkpts0_c, mkpts1_f, left_pose_idx,
+                                                                   right_pose_idx, angle_axis_to_world)
+    dev = d.device
+    ints = torch.empty(3, P, dtype=torch.int32, device=dev)              # iterations, rejects, status
+    reals = torch.empty(3, P, dtype=torch.float64, device=dev)           # lambda, initial_cost, final_cost
+    totals = torch.empty(2, dtype=torch.float64, device=dev)
+    resid = torch.empty(L, 2, dtype=torch.float64, device=dev) if return_residuals else None
+    ws_bytes = postopt_lm.load().oplm_workspace_bytes(L, P)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    p = hip.ptr
+    postopt_lm.call("oplm_refine", p(d, torch.float64), p(offs, torch.int64), P, L, p(K0, torch.float64), p(K1, torch.float64),
+                    p(mk0, torch.float64), p(mk1, torch.float64), p(li, torch.int64), p(ri, torch.int64), p(aa, torch.float64), F,
+                    float(lam0), float(up), float(down), float(lam_min), float(lam_max), float(step_tol), max_iters,
+                    p(ints[0], torch.int32), p(ints[1], torch.int32), p(ints[2], torch.int32), p(reals[0], torch.float64),
+                    p(reals[1], torch.float64), p(reals[2], torch.float64), p(totals[0:1], torch.float64), p(totals[1:2], torch.float64),
+                    p(resid, torch.float64), p(ws, None), ctypes.c_size_t(ws_bytes), hip.stream_handle())
+    # the one read-back: both totals and the largest iteration count follow the solve on the same stream
+    initial, final, steps = torch.cat([totals, ints[0].max().to(torch.float64)[None]]).tolist()
+    out = {"depth": d.reshape(P, 1), "iterations": ints[0], "rejects": ints[1], "status": ints[2], "lambda": reals[0],
+           "initial_cost": reals[1], "final_cost": reals[2], "initial_residual": initial, "final_residual": final, "steps": int(steps)}
     if return_residuals:
         out["residuals"] = resid
     return out
@@ -210,7 +264,9 @@ class Optimizer:
 
     cfgs: ``solver_type``, ``residual_mode``, ``optimize_lr`` ({"depth": lr}), ``optim_procedure`` (a list of "depth"); other keys of the
     reference's cfg (num_workers, batch_size, image_i_f_scale, verbose) are accepted and unused.  DeepLM is not vendored in the reference,
-    so every solver type runs the first-order solver, as there; anything but "FirstOrder" warns."""
+    so every solver type runs the first-order solver, as there; anything but "FirstOrder" warns.  ``hip_second_order`` (this project's
+    key, default ``False``): with ``True`` and ``solver_type == "SecondOrder"`` every "depth" procedure runs :func:`refine_depths_lm`
+    instead, without that warning, and ``steps`` holds the largest iteration count of each."""
 
     def __init__(self, cfgs: dict):
         self.solver_type = cfgs["solver_type"]
@@ -218,6 +274,7 @@ class Optimizer:
         self.optimize_lr = cfgs["optimize_lr"]
         self.optim_procedure = cfgs["optim_procedure"]
         self.verbose = cfgs.get("verbose", False)
+        self.hip_second_order = bool(cfgs.get("hip_second_order", False))
         self.initial_residual = None
         self.final_residual = None
         self.steps = []
@@ -234,7 +291,8 @@ class Optimizer:
                 raise NotImplementedError
         if self.residual_mode != "geometry_error":
             raise NotImplementedError
-        if self.solver_type != "FirstOrder":
+        second_order = self.hip_second_order and self.solver_type == "SecondOrder"
+        if self.solver_type != "FirstOrder" and not second_order:
             warnings.warn("Failed to import DeepLM module. Use our first-order optimizer instead. "
                           "Please check whether installation is correct!")
             self.solver_type = "FirstOrder"
@@ -251,8 +309,9 @@ class Optimizer:
         depth = depth.to(torch.float64)
         self.steps = []
         for i, procedure in enumerate(self.optim_procedure):
-            r = refine_depths(depth, aggregated["n_query"], aggregated["intrinsic0"], aggregated["intrinsic1"], aggregated["mkpts0_c"],
-                              aggregated["mkpts1_f"], left, right, aa, lr=self.optimize_lr[procedure], mode=self.residual_mode)
+            rows = (depth, aggregated["n_query"], aggregated["intrinsic0"], aggregated["intrinsic1"], aggregated["mkpts0_c"],
+                    aggregated["mkpts1_f"], left, right, aa)
+            r = refine_depths_lm(*rows) if second_order else refine_depths(*rows, lr=self.optimize_lr[procedure], mode=self.residual_mode)
             if i == 0:
                 self.initial_residual = r["initial_residual"]
             self.final_residual = r["final_residual"]
