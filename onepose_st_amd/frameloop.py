@@ -129,13 +129,23 @@ class SequenceRunner:
     integers.  ``detect="device"`` (needs ``track="device"`` and a detector with ``detect_state``, such as
     ``detector.LocalFeatureObjectDetector(vote="device")``): ``detector.detect_state(frame_u8_dev, K_dev, crop_size)`` gives that box's
     ``track_device.TrackState`` on the device, enqueued behind the frame's upload, and ``detector(...)`` is never called.
+
+    ``refine=None`` (the default): the records are the first pass's.  ``refine="device"`` (needs ``pnp="device"``; either ``track``): the
+    reference's second pass (``inference.py:237-368``) runs after the loop on what the unchanged first pass left of every frame (its
+    match tables, ``K_crop``, ``trans`` and final inlier rows): ``temporal.refine_sequence`` carries the inliers of the previous
+    ``temp_thresh`` frames into every frame ``t >= temp_thresh`` and solves the pose again (``inliers_only`` and ``refine_options``: its
+    keywords).  It feeds nothing back, so every other key of a record is what a ``refine=None`` run gives; every record gains
+    ``pose_refined``, ``inliers_refined`` (rows of the injected table: the frame's own rows first) and ``refined`` (false for the
+    initialisation frames, which repeat the first-pass pose).  A refined frame whose status asks for more trials is solved by the host
+    solver on the injected table, as in the first pass.
     """
 
     MAX_LOOKAHEAD = 8         # the one-call frame keeps 16 frames in flight at most
 
     def __init__(self, model, object_block: dict, K, bbox3d, detector, crop_size: int = 512, pnp_reprojection_error: float = 7,
                  pnp_scale: float = 1000, min_inliers: int = MIN_INLIERS, crop_fn=crop_query, pnp: str = "host", track: str = "host",
-                 lookahead: int = 2, detect: str = "host"):
+                 lookahead: int = 2, detect: str = "host", refine: str | None = None, temp_thresh: int = 5, inliers_only: bool = True,
+                 refine_options: dict | None = None):
         if pnp not in ("host", "device"):
             raise ValueError(f"pnp={pnp!r}: 'host' or 'device'")
         if track not in ("host", "device"):
@@ -150,6 +160,14 @@ class SequenceRunner:
             raise ValueError("detect='device' needs a detector with detect_state(frame_u8_dev, K_dev, crop_size)")
         if int(lookahead) != lookahead or not 1 <= lookahead <= self.MAX_LOOKAHEAD:
             raise ValueError(f"lookahead: an integer in [1, {self.MAX_LOOKAHEAD}]")
+        if refine not in (None, "device"):
+            raise ValueError(f"refine={refine!r}: None or 'device'")
+        if refine == "device" and pnp != "device":
+            raise ValueError("refine='device' needs pnp='device': the second pose is solved on the device")
+        if int(temp_thresh) != temp_thresh or temp_thresh < 1:
+            raise ValueError("temp_thresh: an integer >= 1")
+        self.refine, self.temp_thresh, self.inliers_only, self.refine_options = refine, int(temp_thresh), bool(inliers_only), dict(refine_options or {})
+        self._kept = None                                 # refine: the match tables of every recorded frame, in record order
         self.pnp, self.track, self.lookahead, self.detect = pnp, track, int(lookahead), detect
         self.model, self.block, self.crop_fn = model, object_block, crop_fn
         self.K, self.bbox3d, self.detector = np.asarray(K, np.float64), np.asarray(bbox3d, np.float64), detector
@@ -169,8 +187,47 @@ class SequenceRunner:
 
     def run(self, frames):
         frames = list(frames)
-        if self.track == "device":
-            return self._run_device_tracked(frames)
+        self._kept = [] if self.refine else None
+        records = self._run_device_tracked(frames) if self.track == "device" else self._run_host_tracked(frames)
+        if self.refine:
+            self._refine(frames, records)
+        return records
+
+    def _keep_tables(self, data):
+        """refine: a frame's match tables as its record saw them (copies: a model may reuse its buffers for a later frame)"""
+        if self._kept is not None:
+            self._kept.append((data["mkpts_query_f"].float().clone(), data["mkpts_3d_db"].float().clone()))
+
+    def _refine(self, frames, records):
+        """The second pass (class docstring): reads ``self._kept`` and the records, adds the three keys"""
+        from . import pnp_device, temporal
+        dev, entries = self.device, []
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        for rec, (mk2d, mk3d) in zip(records, self._kept):
+            n = int(mk2d.shape[0])
+            mask = np.zeros(max(n, 1), np.uint8)
+            mask[np.asarray(rec["inliers"], np.int64)] = 1
+            if n == 0:                                  # the library wants a table of at least one row; the count says it is unused
+                mk2d, mk3d = torch.zeros(1, 2, dtype=torch.float32, device=dev), torch.zeros(1, 3, dtype=torch.float32, device=dev)
+            entries.append({"pts_2d": mk2d, "pts_3d": mk3d, "count": torch.full((1,), n, dtype=torch.int32, device=dev), "mask": up(mask, np.uint8),
+                            "K_crop": up(rec["K_crop"], np.float64), "trans": up(rec["trans"], np.float64), "pose": up(rec["pose"], np.float64)})
+        self._kept = None
+        kw = dict(scale=self.scale, pnp_reprojection_error=self.reproj)
+        kw.update(self.refine_options)
+        seq = temporal.refine_sequence(frames, entries, self.K[:3, :3], temp_thresh=self.temp_thresh, inliers_only=self.inliers_only, device=dev, **kw)
+        for rec, dev_out, got in zip(records, seq.frames, seq.to_host()):
+            if got is None:
+                rec.update(pose_refined=rec["pose"], inliers_refined=rec["inliers"], refined=False)
+                continue
+            pose, inliers = got["pose"], got["inliers"]
+            if got["status"] & pnp_device.STATUS_NEEDS_MORE:        # the host's open-ended policy on the injected table, as in _device_pose
+                k = got["count"]
+                pose, _, inliers = ransac_PnP(rec["K_crop"], dev_out["pts_2d"][:k].cpu().numpy(), dev_out["pts_3d"][:k].cpu().numpy(), scale=kw["scale"],
+                                              pnp_reprojection_error=kw["pnp_reprojection_error"], img_hw=[self.crop_size, self.crop_size],
+                                              use_pycolmap_ransac=True)
+            rec.update(pose_refined=pose, inliers_refined=inliers, refined=True)
+
+    def _run_host_tracked(self, frames):
         records = []
         nxt = self._upload(frames[0]) if frames else None
         prev = None                                   # (pose, inliers) of the previous frame
@@ -191,6 +248,7 @@ class SequenceRunner:
                 self.model(data)
             if self.pnp == "device":
                 pose, inliers, num_matches = self._device_pose(K_crop, data)
+                self._keep_tables(data)
                 prev = (pose, inliers)
                 records.append({"pose": pose, "inliers": inliers, "bbox": bbox, "K_crop": K_crop, "trans": trans,
                                 "num_matches": num_matches, "redetected": bool(redetect)})
@@ -304,6 +362,7 @@ class SequenceRunner:
                 pose, inliers = self._host_pose(K_crop, data)
             records.append({"pose": pose, "inliers": inliers, "bbox": bbox, "K_crop": K_crop, "trans": trans,
                             "num_matches": int(data["mkpts_3d_db"].shape[0]), "redetected": bool(redetected.pop(t, False))})
+            self._keep_tables(data)
             uploads.pop(t, None)
             if not host_step and next_flag == 0:
                 continue
