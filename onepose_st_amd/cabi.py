@@ -30,7 +30,7 @@ SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 RETURN_TYPES = (*SCALARS, "const char*", "void", "void*")
 _POINTEES = (*SCALARS, "char", "unsigned char", "void")
-_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp', 'oplm', 'optmp'])})_\w+"  # the host library (pnp.py), postopt_lm.py, temporal.py
+_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp', 'oplm', 'optmp', 'opevl'])})_\w+"  # the host library (pnp.py), postopt_lm.py, temporal.py, pose_eval.py
 
 
 class HeaderError(ValueError):
