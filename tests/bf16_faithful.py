@@ -32,6 +32,15 @@ Per match a tile of 26 tokens x 128 features: rows 0..24 the 5 x 5 window, row 2
       std = sqrt(max(var_x, 1e-10)) + sqrt(max(var_y, 1e-10)).
   keypoint (``store_fine_keypoint``, tile.h:89-103): ``mkpts_c + expec * fine_scale``, or with ``query_scale [B][2]`` (h, w factors)
       ``mkpts_c + (2 expec) * ((fine_scale / 2) * query_scale[b][[1, 0]])``.
+
+``coarse_kv_faithful`` and ``coarse_layer_faithful`` restate the coarse encoder layer of csrc/encoder_bf16.hip (256 features, 8 heads of 32,
+streams of any length): the first the K^T V | Ksum block of a stream as a source (``kv_reduce_bf16_kernel`` or the previous layer's fused
+tail, then ``kv_sum_bf16_kernel``), the second ``attn_apply_bf16_kernel`` GIVEN a block; their docstrings list the ten rounding points with
+the kernel's lines.  The two are separate because the block is a sum over the whole stream: one of its 8192 elements that the f32 sum puts on
+the other side of a bf16 boundary (12 do at L = 545 in an f32 stand-in of the reference) moves every token that reads it, and the share of
+tokens at the f32 bar falls from 0.97 to 0.55 although nothing is wrong.  So tests/test_gpu_encoder_bf16.py checks the device's block on its
+own, element by element, and feeds THAT block to the layer reference ("teacher forcing"); what is left between the layer and its reference
+is again accumulation order and flips of single tokens.  Statistic: the share of TOKENS whose 256 outputs all meet the f32 bar.
 """
 from __future__ import annotations
 
@@ -150,6 +159,120 @@ def fine_stage_faithful(sd: dict, feat_f, desc3d, b_ids, i_ids, j_ids, mkpts_c, 
             "mkpts_f": keypoints(mkpts_c, expec, fine_scale, b_ids, query_scale)}
 
 
+# ---- the coarse encoder layer of the plain-bf16 mode (csrc/encoder_bf16.hip, nsplit = 1) ----------------------------------------------
+
+CC, CHEADS, CDIM, SLAB = 256, 8, 32, 32
+
+
+def _w(sd: dict, name: str, rounded, dtype) -> torch.Tensor:
+    w = sd[name].detach().to(torch.float32)
+    return (bf16_round(w) if rounded is not False else w).to(dtype)
+
+
+def _rounder(rounded):
+    """``rounded``: True = every rounding point, False = none (weights included), a collection of point numbers = all points BUT those
+    (weights rounded): what a kernel that misses a rounding point would compute"""
+    def at(point):
+        on = rounded is True or (rounded is not False and point not in rounded)
+        return bf16_round if on else (lambda t: t)
+    return at
+
+
+def _coarse_kv_operands(sd, p, source, kv_mask, dtype, rounded):
+    """``phi(K)`` and ``V / L`` as the KV product takes them, ``[B][slab][32 tokens][8][32]`` (points 1-3 of :func:`coarse_kv_faithful`)"""
+    B, L, _ = source.shape
+    r = _rounder(rounded)
+    x = r(1)(source.to(torch.float32)).to(dtype)
+    K = (x @ _w(sd, p + "k_proj.weight", rounded, dtype).T).view(B, L, CHEADS, CDIM)
+    V = (x @ _w(sd, p + "v_proj.weight", rounded, dtype).T).view(B, L, CHEADS, CDIM)
+    phiK = _phi(K)
+    if kv_mask is not None:
+        phiK = phiK * kv_mask.to(dtype)[:, :, None, None]
+    phiK = r(2)(phiK)
+    inv_len = (torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(L), dtype=torch.float32)).to(dtype) if rounded is not False else 1.0 / L
+    V = r(3)(V * inv_len)                                                                               # bf16_round goes through f32
+    pad = (-L) % SLAB
+    phiK, V = F.pad(phiK, (0, 0, 0, 0, 0, pad)), F.pad(V, (0, 0, 0, 0, 0, pad))
+    return phiK.view(B, -1, SLAB, CHEADS, CDIM), V.view(B, -1, SLAB, CHEADS, CDIM)
+
+
+def coarse_kv_faithful(sd: dict, p: str, source: torch.Tensor, kv_mask=None, dtype=torch.float64, rounded=True):
+    """``KV [B][8][32 (d)][32 (v)]`` and ``Ksum [B][8][32]`` of the stream ``source [B][L][256]`` as the attention's source:
+    ``kv_reduce_bf16_kernel`` / the fused tail of ``attn_apply_bf16_kernel`` (both ``kv_slab_from_planes``, encoder_bf16.hip:47-101) and
+    ``kv_sum_bf16_kernel`` (:139-166), BEFORE the block's (hi, lo) split.  ``kv_mask [B][L]`` (bool, 1 = real cell): the 2D stream's padding.
+    Rounding points (``rounded``: see :func:`_rounder`; False = none, which is oracle.onepose_oracle.linear_attention's KV):
+      1. source rows -> bf16 planes (``load_rows_to_planes``, tile_bf16.h:252-273, called at encoder_bf16.hip:121; in the fused tail the rows
+         of ``y`` at :418-427, rows >= L zero); Wk, Wv = the packer's hi plane (packing.split_planes); K, V f32 accumulators (:58);
+      2. ``phi(K) = elu + 1`` -> bf16 (``acc_frag_map`` with ``f_k``, :68-71, :80); 0 for tokens >= L and for masked cells;
+      3. ``V * inv_len``, ``inv_len = 1.0f / (float)L`` in f32 (:59), the product an f32 (``f_v``, :72) -> bf16 (:81);
+      4. ``KV = sum phiK (x) V`` and ``Ksum = sum phiK`` over those operands (:82-83): f32 partials per 32-token slab (:86-98), summed over the
+         slabs by ``kv_sum_bf16_kernel`` (:148, :154); here: per slab in ``dtype``, then over the slabs."""
+    phiK, V = _coarse_kv_operands(sd, p, source, kv_mask, dtype, rounded)
+    KV = torch.einsum("bsthd,bsthv->bshdv", phiK, V).sum(1)                                             # (4)
+    return KV, phiK.sum(2).sum(1)
+
+
+def coarse_layer_faithful(sd: dict, p: str, x: torch.Tensor, KV: torch.Tensor, Ksum: torch.Tensor, S: int, q_mask=None,
+                          dtype=torch.float64, rounded=True) -> torch.Tensor:
+    """``y [B][L][256]`` of ``attn_apply_bf16_kernel`` (encoder_bf16.hip:240-438) for the query stream ``x`` given the source's ``KV`` and
+    ``Ksum`` (:func:`coarse_kv_faithful`, or the device's block) and its length ``S``.  ``q_mask [B][L]``: the 2D stream's padding as queries.
+    Rounding points (``rounded``: see :func:`_rounder`; False = none, which is oracle.onepose_oracle.encoder_layer):
+      5. KV -> bf16: the block holds (hi, lo) (``kv_sum_bf16_kernel``, :157-161), nsplit = 1 reads hi only (:305-306);
+         Ksum is stored f32 (:163) and split when read, hi only (:310-315);
+      6. x rows -> bf16 X planes (:273): operand of the Q GEMM (:285) and first half of the W0 operand (:364); the residual (:413-414) is f32 x;
+      7. ``phi(Q)`` -> bf16 (``acc_frag``, :319), 0 for masked query cells (:298-301);
+      8. ``msg = num * rcp(den + 1e-6f) * S`` in f32 (:327) -> bf16 Y planes (:328): operand of the merge GEMM (:342);
+      9. LayerNorm1 (f32, biased variance, eps 1e-5: ``layernorm_featrow``, :190-238) -> bf16 Y planes (:349): second half of the W0 operand;
+     10. ``relu(hidden)`` -> bf16 H planes in four 128-feature chunks (:371-372): operand of the W2 GEMM (:376).
+    NOT rounded: the accumulators, LayerNorm2 (:382) and ``y = x + LN2`` (:414).  ``1 / L`` (point 3) and ``S`` do not cancel once
+    ``V / L`` is rounded: both are kept."""
+    B, L, _ = x.shape
+    r = _rounder(rounded)
+    g = lambda name: sd[p + name].detach().to(dtype)
+    KVr, Ksr = r(5)(KV.to(torch.float32)).to(dtype), r(5)(Ksum.to(torch.float32)).to(dtype)
+    xr = r(6)(x.to(torch.float32)).to(dtype)
+    phiQ = _phi((xr @ _w(sd, p + "q_proj.weight", rounded, dtype).T).view(B, L, CHEADS, CDIM))
+    if q_mask is not None:
+        phiQ = phiQ * q_mask.to(dtype)[:, :, None, None]
+    phiQ = r(7)(phiQ)
+    num = torch.einsum("blhd,bhdv->blhv", phiQ, KVr)
+    den = torch.einsum("blhd,bhd->blh", phiQ, Ksr)
+    eps = torch.tensor(1e-6, dtype=torch.float32).to(dtype)
+    msg = r(8)((num * (1 / (den + eps))[..., None] * float(S)).reshape(B, L, CC))
+    m = msg @ _w(sd, p + "merge.weight", rounded, dtype).T
+    m = r(9)(F.layer_norm(m, (CC,), g("norm1.weight"), g("norm1.bias"), 1e-5))
+    hid = r(10)(torch.relu(torch.cat([xr, m], 2) @ _w(sd, p + "mlp.0.weight", rounded, dtype).T))
+    o = hid @ _w(sd, p + "mlp.2.weight", rounded, dtype).T
+    return x.to(dtype) + F.layer_norm(o, (CC,), g("norm2.weight"), g("norm2.bias"), 1e-5)
+
+
+def coarse_streams_faithful(sd: dict, p: str, x3, x2, cross: bool, mask2=None, kv=None, dtype=torch.float64, rounded=True):
+    """Both streams of one layer as ``ophip_encoder_layer_bf16[_masked]`` runs them (``layer_bf16``, encoder_bf16.hip:455-545): the block
+    [b][s] is stream s as a source (s = 1, the 2D stream, under ``mask2`` as kv_mask, :126); stream s attends to block s ("self") or 1 - s
+    ("cross", :513-517) and the 2D stream's queries are masked (:262, :299).  ``kv`` = ((KV3, Ksum3), (KV2, Ksum2)) replaces the blocks
+    (teacher forcing: the float64 reference's, or the device's).  Returns ``(y3, y2, kv)``."""
+    if kv is None:
+        kv = (coarse_kv_faithful(sd, p, x3, None, dtype, rounded), coarse_kv_faithful(sd, p, x2, mask2, dtype, rounded))
+    s3, s2 = (kv[1], kv[0]) if cross else (kv[0], kv[1])
+    L = (x3.shape[1], x2.shape[1])
+    y3 = coarse_layer_faithful(sd, p, x3, s3[0], s3[1], L[1] if cross else L[0], None, dtype, rounded)
+    y2 = coarse_layer_faithful(sd, p, x2, s2[0], s2[1], L[0] if cross else L[1], mask2, dtype, rounded)
+    return y3, y2, kv
+
+
+def token_share_at_f32_bar(got: torch.Tensor, want: torch.Tensor) -> float:
+    """share of tokens (rows of the last dim) whose 256 outputs all meet the f32 bar"""
+    return meets(got.reshape(-1, got.shape[-1]), want.reshape(-1, want.shape[-1]), F32_RTOL, F32_ATOL).double().mean().item()
+
+
+def bf16_ulps_apart(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """distance of two tensors of bf16 VALUES in steps of the bf16 grid (int64; 0 = equal, 1 = neighbours; -0 and +0 are 0 apart)"""
+    def key(t):
+        i = t.to(torch.float32).to(torch.bfloat16).view(torch.int16).to(torch.int64) & 0xFFFF
+        return torch.where(i >= 0x8000, 0x8000 - i, i)                                                  # sign-magnitude -> a line
+    return (key(a) - key(b)).abs()
+
+
 def meets(got: torch.Tensor, want: torch.Tensor, rtol: float, atol: float) -> torch.Tensor:
     """per match (dim 0): every element within ``atol + rtol |want|``"""
     g, w = got.to(torch.float64).reshape(got.shape[0], -1), want.to(torch.float64).reshape(want.shape[0], -1)
@@ -160,6 +283,106 @@ def share_at_f32_bar(windows, f3, ref: dict) -> float:
     """share of matches whose windows AND 3D token all meet the f32 bar against ``ref``"""
     ok = meets(windows, ref["windows"].to(windows.device), F32_RTOL, F32_ATOL) & meets(f3, ref["f3"].to(f3.device), F32_RTOL, F32_ATOL)
     return ok.double().mean().item() if ok.numel() else 1.0
+
+
+# ---- the cases of tests/test_gpu_encoder_bf16.py, shared with the CPU file that checks what they rely on ------------------------------
+
+COARSE_LAYER = "loftr_coarse.layers.2."
+# (B, L3, L2): one-token stream | one token either side of a 32-token tile | one past one and two tiles | batch strides | exactly two tiles |
+# 18 slabs (kv_sum's 16-way loop wraps, ragged last slab) beside fewer than 16
+COARSE_SHAPES = [(1, 1, 32), (1, 31, 33), (1, 33, 65), (3, 49, 97), (2, 64, 45), (1, 545, 300)]
+COARSE_MASK_SHAPES = [(2, 64, 45), (3, 49, 97), (1, 545, 300)]
+COARSE_MASKS = ["random", "mid_tile", "last_tile"]
+COARSE_CHAIN_SHAPES = [(1, 100, 75), (2, 333, 260)]
+# Worst element of a token against the float64 reference fed the same KV: twice the worst that the f32 stand-in of the reference shows over
+# COARSE_SHAPES, COARSE_MASK_SHAPES x COARSE_MASKS and (2, 70, 45), both layer kinds (tests/test_bf16_faithful_cpu.py measures and pins it).
+COARSE_STANDIN_WORST = 8.0e-3        # measured: 7.6e-3
+COARSE_WORST_BAR = 2 * COARSE_STANDIN_WORST
+COARSE_KV_ULP_SHARE = 0.01          # at most 1 % of the KV elements one bf16 step from the reference's, none further
+
+
+def coarse_inputs(B: int, L3: int, L2: int, seed: int = 2):
+    """the streams of tests/test_gpu_parity.py::test_encoder_layer_bf16"""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(B, L3, CC, generator=g), torch.randn(B, L2, CC, generator=g)
+
+
+def coarse_mask(kind: str, B: int, L2: int) -> torch.Tensor:
+    """``[B][L2]`` bool, 1 = real cell.  "random": the mask of tests/test_gpu_masked.py; "mid_tile": the real cells end inside the last
+    32-token tile that holds any (13 cells short of a tile edge, 5 fewer per batch element); "last_tile": the whole last tile is padding
+    (and, from batch element 1 on, one more cell per element)."""
+    if kind == "random":
+        from tests.test_gpu_masked import _mask
+        return _mask(B, L2, 11)
+    m = torch.zeros(B, L2, dtype=torch.bool)
+    edge = SLAB * ((L2 - 1) // SLAB)                    # first token of the last tile
+    for b in range(B):
+        n = edge - 13 - 5 * b if kind == "mid_tile" else edge - b
+        assert 0 < n < L2 and (kind == "last_tile" or n % SLAB)
+        m[b, :n] = True
+    return m
+
+
+KV_PART_FLOATS = CHEADS * 2 * 64 * 8 + CHEADS * CDIM            # one 32-token slab: KV fragments (f32) + Ksum (encoder_bf16.hip:27)
+KV_FRAG_BYTES = CHEADS * 2 * 2 * 64 * 16                        # [head][k-step][plane hi, lo][lane][8 bf16] (:28)
+KV_BLOCK_BYTES = KV_FRAG_BYTES + CHEADS * CDIM * 4              # + Ksum f32 [head][lane half][16] (:29)
+
+
+def kv_block_offset(base_addr: int, B: int, L3: int, L2: int) -> int:
+    """byte offset of the ``[B][2][KV_BLOCK_BYTES]`` block inside the workspace at address ``base_addr``: behind the two slab sets, at the
+    next ADDRESS that is a multiple of 256 (``layer_bf16``, encoder_bf16.hip:468-473)"""
+    part_floats = B * ((L3 + SLAB - 1) // SLAB + (L2 + SLAB - 1) // SLAB) * KV_PART_FLOATS
+    off = 2 * part_floats * 4
+    return off + (-(base_addr + off)) % 256
+
+
+def decode_kv_block(blk: torch.Tensor):
+    """``blk [..][KV_BLOCK_BYTES]`` uint8 (CPU) -> ``KV_hi, KV_lo [..][8][32 (d)][32 (v)]`` and ``Ksum [..][8][32]`` (f32).  The fragments are
+    the KV accumulator ``D[d][v]`` of ``kv_slab_from_planes`` as lane and register hold it: element j of lane ``32 h + r`` in k-step ``st`` is
+    register ``8 st + j``, so ``v = r`` and ``d = (reg & 3) + 8 (reg >> 2) + 4 h`` (encoder_bf16.hip:86-98, :157-163; tile_bf16.h:9-18);
+    Ksum register ``reg`` of lane half ``h`` is the same ``d``."""
+    lead = blk.shape[:-1]
+    frag = blk[..., :KV_FRAG_BYTES].contiguous().view(torch.bfloat16).float().view(*lead, CHEADS, 2, 2, 64, 8)
+    ks = blk[..., KV_FRAG_BYTES:].contiguous().view(torch.float32).view(*lead, CHEADS, 2, 16)
+    st, lane, j = torch.meshgrid(torch.arange(2), torch.arange(64), torch.arange(8), indexing="ij")
+    reg = 8 * st + j
+    d, v = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), lane & 31
+    assert len(set((d * 32 + v).flatten().tolist())) == 32 * 32
+    out = []
+    for plane in (0, 1):
+        KV = torch.full((*lead, CHEADS, CDIM, CDIM), float("nan"))
+        KV[..., d, v] = frag[..., plane, :, :]
+        out.append(KV)
+    h, reg = torch.meshgrid(torch.arange(2), torch.arange(16), indexing="ij")
+    Ksum = torch.full((*lead, CHEADS, CDIM), float("nan"))
+    Ksum[..., (reg & 3) + 8 * (reg >> 2) + 4 * h] = ks
+    return out[0], out[1], Ksum
+
+
+def coarse_kv_slack(sd: dict, p: str, source: torch.Tensor, kv_mask=None):
+    """What f32 arithmetic may leave between the device's block and the reference's BEFORE the block is rounded, from reasoning alone
+    (float64, no measurement).  Two terms each:
+      accumulation: the rounding errors of an f32 sum of L terms add up to about ``sqrt(L) 2^-24`` of the sum of their magnitudes (the operands
+          are bf16, their products exact in f32); eight times that;
+      flips: an operand ``phi(K)[tok][d]`` or ``V[tok][v] / L`` that the f32 K or V puts on the other side of a bf16 rounding boundary moves its
+          term by one bf16 step of the operand, <= 2^-7 of the term; two may coincide in one sum.
+    ``kv [B][8][32][32]`` for ``KV = sum_tok phiK V`` and ``ksum [B][8][32]`` for ``Ksum = sum_tok phiK``.  For KV the slack matters where the
+    sum cancels to a value whose own bf16 step is smaller (and in streams of a few tokens); elsewhere it lies below the one bf16 step that
+    rounding the block allows anyway."""
+    L = source.shape[1]
+    phiK, V = _coarse_kv_operands(sd, p, source, kv_mask, torch.float64, True)
+    acc, flip = 8 * L ** 0.5 * 2.0 ** -24, 2 * 2.0 ** -7
+    terms = torch.einsum("bsthd,bsthv->bsthdv", phiK.abs(), V.abs())
+    return acc * terms.sum((1, 2)) + flip * terms.amax((1, 2)), acc * phiK.sum((1, 2)) + flip * phiK.amax((1, 2))
+
+
+def coarse_kv_check(kv_got: torch.Tensor, kv_ref: torch.Tensor, kv_acc: torch.Tensor):
+    """The block's hi plane ``kv_got`` (bf16 values) against ``bf16_round(kv_ref)``: returns (share of elements that differ, elements that
+    are neither within one bf16 step nor within the slack ``kv_acc`` of :func:`coarse_kv_slack` -- there must be none, max steps apart)."""
+    want = bf16_round(kv_ref)
+    steps = bf16_ulps_apart(kv_got, want)
+    bad = (steps > 1) & ((kv_got.double() - want.double()).abs() > kv_acc)
+    return (steps > 0).double().mean().item(), int(bad.sum()), int(steps.max())
 
 
 # ---- the cases of tests/test_gpu_fine_stage.py, shared with the CPU file that checks what they rely on -------------------------------

@@ -4,7 +4,16 @@ for the reference ALONE: the planted heat maps are deltas, and the share of matc
 reference and a stand-in with the same roundings and f32 arithmetic, stays above the caps the GPU test asserts.
 
 Measured here (K = 256, synthetic state dict): un-rounded float64 against the oracle 4e-6; shares at the f32 bar of the f32 stand-in
-against the float64 reference: two layers (self, cross) 0.70, one layer 0.81 (self) / 0.89 (cross), worst element 1.3e-2; the un-rounded float64 computation: 0."""
+against the float64 reference: two layers (self, cross) 0.70, one layer 0.81 (self) / 0.89 (cross), worst element 1.3e-2; the un-rounded float64 computation: 0.
+
+The same for the coarse encoder layer (tests/test_gpu_encoder_bf16.py).  Measured here on that file's inputs (layer ``loftr_coarse.layers.2.``,
+seeded ``randn`` streams, shapes (1,1,32) .. (1,545,300) and (2,70,45), three masks, self and cross): un-rounded float64 against the oracle
+2.7e-6; f32 stand-in fed the float64 reference's KV ("teacher-forced"): share of tokens at the f32 bar 0.909 - 1.000, worst element 7.6e-3
+(hence ``bf.COARSE_WORST_BAR`` = 2 x 8e-3); the un-rounded float64 computation: share 0.000 everywhere, worst 1.8e-2 - 2.4e-2; the stand-in's
+own KV block: 0 - 0.15 % of the elements differ from the reference's, by one bf16 step or, where the sum cancels, by up to 14 steps (28172 next
+to zero), at most 0.43 of the reasoned slack; Ksum: identical.  Fed its OWN block at L = 545 (12 and 6 of 8192 elements one step away) the
+stand-in's token share falls to 0.56 / 0.54 in the stream that reads the 3D block: why the GPU test feeds the device's block to the reference.
+Every single missing rounding point, an ``S`` off by one, a padded cell in ``phi(K)`` and slabs missing from ``kv_sum`` are rejected."""
 import pytest
 import torch
 
@@ -87,6 +96,188 @@ def test_planted_heat_maps_are_deltas_in_the_reference():
         assert err < 0.01
     # x and y are told apart: the expected points are not symmetric under a swap or a sign change
     assert not torch.equal(c["want_xy"], c["want_xy"][:, [1, 0]]) and not torch.equal(c["want_xy"], -c["want_xy"])
+
+
+# ---- the coarse encoder layer (tests/test_gpu_encoder_bf16.py) -------------------------------------------------------------------------
+
+P = bf.COARSE_LAYER
+
+
+def _oracle_streams(sd, x3, x2, cross, mask):
+    if cross:
+        return orc.encoder_layer(sd, P, x3, x2, 8, source_mask=mask), orc.encoder_layer(sd, P, x2, x3, 8, x_mask=mask)
+    return orc.encoder_layer(sd, P, x3, x3, 8), orc.encoder_layer(sd, P, x2, x2, 8, mask, mask)
+
+
+@pytest.mark.parametrize("mask_kind", [None] + bf.COARSE_MASKS)
+@pytest.mark.parametrize("B,L3,L2", [(2, 70, 45), (3, 49, 97)])
+def test_unrounded_coarse_layer_is_the_oracle(sd, B, L3, L2, mask_kind):
+    """Rounding off, float64 = oracle.onepose_oracle.encoder_layer (f32) within 2e-5, self and cross, with and without the 2D mask; the two
+    layer kinds differ, and so do the masked and the unmasked layer: the pin is indifferent to neither."""
+    x3, x2 = bf.coarse_inputs(B, L3, L2)
+    mask = None if mask_kind is None else bf.coarse_mask(mask_kind, B, L2)
+    got = {}
+    for cross in (False, True):
+        y3, y2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, mask, rounded=False)
+        r3, r2 = _oracle_streams(sd, x3, x2, cross, None if mask is None else mask.float())
+        e3, e2 = (y3 - r3).abs().max().item(), (y2 - r2).abs().max().item()
+        print(f"un-rounded float64 against the oracle, B={B} L=({L3},{L2}) cross={cross} mask={mask_kind}: 3D {e3:.2e} 2D {e2:.2e}")
+        assert max(e3, e2) <= 2e-5
+        got[cross] = (y3, y2)
+    assert min((got[True][i] - got[False][i]).abs().max().item() for i in (0, 1)) > 1e-2
+    if mask is not None:
+        for cross in (False, True):
+            u3, u2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, None, rounded=False)
+            assert (u2 - got[cross][1]).abs().max().item() > 1e-2                    # the masked queries
+            assert cross == (not (u3 - got[cross][0]).abs().max().item() == 0.0)     # 3D: the mask reaches it through a cross layer's source only
+
+
+def _standin_figures(sd, x3, x2, cross, mask):
+    """The float64 reference, the f32 stand-in fed the REFERENCE's KV (teacher-forced), the un-rounded float64 computation, and the
+    stand-in's own KV: (token shares 3D / 2D, worst element, un-rounded shares, un-rounded worst, KV one-step share, KV max steps,
+    Ksum error / bar)."""
+    r3, r2, kv = bf.coarse_streams_faithful(sd, P, x3, x2, cross, mask)
+    s3, s2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, mask, kv=kv, dtype=torch.float32)
+    u3, u2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, mask, rounded=False)
+    skv = (bf.coarse_kv_faithful(sd, P, x3, None, torch.float32), bf.coarse_kv_faithful(sd, P, x2, mask, torch.float32))
+    slack = [bf.coarse_kv_slack(sd, P, x, m) for x, m in ((x3, None), (x2, mask))]
+    chk = [bf.coarse_kv_check(bf.bf16_round(a[0]).double(), b[0], sl[0]) for a, b, sl in zip(skv, kv, slack)]
+    ks = max(((a[1].double() - b[1]).abs() / sl[1]).max().item() for a, b, sl in zip(skv, kv, slack))
+    tot = max(((a[0].double() - b[0]).abs() / sl[0]).max().item() for a, b, sl in zip(skv, kv, slack))
+    return dict(share=(bf.token_share_at_f32_bar(s3, r3), bf.token_share_at_f32_bar(s2, r2)),
+                worst=max((s3.double() - r3).abs().max().item(), (s2.double() - r2).abs().max().item()),
+                share0=(bf.token_share_at_f32_bar(u3, r3), bf.token_share_at_f32_bar(u2, r2)),
+                worst0=max((u3 - r3).abs().max().item(), (u2 - r2).abs().max().item()),
+                kv_off=max(c[0] for c in chk), kv_bad=sum(c[1] for c in chk), kv_max=max(c[2] for c in chk), ksum=ks, kv_tot=tot)
+
+
+def _check_standin(f, label):
+    print(f"{label}: token share at the f32 bar 3D {f['share'][0]:.3f} 2D {f['share'][1]:.3f}, worst element {f['worst']:.2e}; un-rounded float64: "
+          f"share {f['share0'][0]:.3f} / {f['share0'][1]:.3f}, worst {f['worst0']:.2e}; stand-in KV: {100 * f['kv_off']:.3f} % differ, "
+          f"max {f['kv_max']} steps, {f['kv_bad']} outside the slack; un-rounded KV error / slack {f['kv_tot']:.3f}, Ksum error / slack {f['ksum']:.3f}")
+    assert min(f["share"]) >= 0.9                           # the GPU test's cap is 0.5
+    assert f["worst"] <= bf.COARSE_STANDIN_WORST            # the GPU test's bar is twice this
+    assert max(f["share0"]) == 0.0 and f["worst0"] > bf.COARSE_WORST_BAR
+    assert f["kv_bad"] == 0 and f["kv_off"] <= bf.COARSE_KV_ULP_SHARE / 4
+    assert f["ksum"] <= 0.5 and f["kv_tot"] <= 0.5                    # the GPU test allows the whole slack
+
+
+def test_kv_block_decoder_inverts_the_kernels_element_order():
+    """``decode_kv_block`` on a block written as kv_reduce_bf16 -> kv_sum_bf16 write it, from the lane-level emulation of the matrix
+    instruction (tests/mfma_emul.py; test_packing_emulation_bf16.py pins that order against attn_apply's reads): values that are exact in bf16."""
+    import numpy as np
+    from tests import mfma_emul as E
+    rng = np.random.default_rng(1)
+    blk = torch.zeros(bf.KV_BLOCK_BYTES, dtype=torch.uint8)
+    frag = blk[:bf.KV_FRAG_BYTES].view(torch.bfloat16).view(8, 2, 2, 64, 8)
+    ksf = blk[bf.KV_FRAG_BYTES:].view(torch.float32).view(8, 2, 16)
+    KV, Ksum = torch.zeros(8, 32, 32), torch.zeros(8, 32)
+    for head in range(8):
+        Kt, Vt = rng.integers(0, 4, (32, 32)).astype(float), rng.integers(-3, 4, (32, 32)).astype(float)      # [tok][d], [tok][v]
+        kacc, vacc = Kt[E.ROWS, E.R[:, None]], Vt[E.ROWS, E.R[:, None]]
+        kv, ks = np.zeros((64, 16)), np.zeros((64, 16))
+        for st in range(2):
+            kv = E.mfma_32x32x16(E.acc_frag(kacc, st), E.acc_frag(vacc, st), kv)
+            ks = E.mfma_32x32x16(E.acc_frag(kacc, st), np.ones((64, 8)), ks)
+        for st in range(2):
+            frag[head, st, 0] = torch.from_numpy(kv[:, 8 * st:8 * st + 8]).to(torch.bfloat16)                 # slab [st][lane][8] -> hi plane
+            frag[head, st, 1] = torch.from_numpy(kv[:, 8 * st:8 * st + 8] / 512).to(torch.bfloat16)           # a lo plane that is told apart
+        ksf[head, 0], ksf[head, 1] = torch.from_numpy(ks[0]).float(), torch.from_numpy(ks[32]).float()       # lanes with r == 0
+        KV[head], Ksum[head] = torch.from_numpy(Kt.T @ Vt).float(), torch.from_numpy(Kt.sum(0)).float()
+    hi, lo, ksum = bf.decode_kv_block(blk)
+    assert torch.equal(hi, KV) and torch.equal(lo, KV / 512) and torch.equal(ksum, Ksum)
+    assert not torch.equal(KV, KV.transpose(1, 2))
+    # the block follows the two slab sets at the next 256-byte ADDRESS
+    pf = 2 * (2 + 3) * bf.KV_PART_FLOATS
+    assert bf.kv_block_offset(0, 2, 33, 65) == 2 * pf * 4 and bf.kv_block_offset(512 + 64, 2, 33, 65) == 2 * pf * 4 + 192 and (2 * pf * 4) % 256 == 0
+
+
+@pytest.mark.parametrize("cross", [False, True])
+@pytest.mark.parametrize("B,L3,L2", sorted(set(bf.COARSE_SHAPES + [(2, 70, 45)])))
+def test_coarse_token_share_of_an_f32_stand_in(sd, cross, B, L3, L2):
+    """What tests/test_gpu_encoder_bf16.py asserts of the device holds for the reference ALONE, at the GPU test's shapes: the same roundings
+    in f32 arithmetic, fed the float64 reference's KV, keep >= 0.9 of the tokens of either stream at the f32 bar and every element within
+    COARSE_STANDIN_WORST; the UN-rounded computation keeps none and is off by more than the GPU test's worst-element bar, so both statistics
+    see an error of the size of one rounding point; and the stand-in's own KV lies within one bf16 step of the reference's, rarely."""
+    x3, x2 = bf.coarse_inputs(B, L3, L2)
+    _check_standin(_standin_figures(sd, x3, x2, cross, None), f"B={B} L=({L3},{L2}) cross={cross}")
+
+
+@pytest.mark.parametrize("cross", [False, True])
+@pytest.mark.parametrize("mask_kind", bf.COARSE_MASKS)
+@pytest.mark.parametrize("B,L3,L2", bf.COARSE_MASK_SHAPES)
+def test_coarse_token_share_of_an_f32_stand_in_masked(sd, cross, mask_kind, B, L3, L2):
+    x3, x2 = bf.coarse_inputs(B, L3, L2)
+    mask = bf.coarse_mask(mask_kind, B, L2)
+    _check_standin(_standin_figures(sd, x3, x2, cross, mask), f"B={B} L=({L3},{L2}) cross={cross} mask={mask_kind}")
+
+
+@pytest.mark.parametrize("B,L3,L2", [(2, 70, 45), (1, 545, 300)])
+def test_coarse_checks_reject_wrong_kernels(sd, B, L3, L2):
+    """The assertions of tests/test_gpu_encoder_bf16.py, applied to f32 stand-ins that are wrong the way a kernel could be, reject each one:
+    (a) a missing rounding point 1-3, one padded 2D cell left in ``phi(K)``, the slabs from 16 on left out of ``kv_sum`` -- more than 1 % of
+    the block's elements differ (a right stand-in: <= 0.15 %); (b) a missing rounding point 5-10, ``S`` off by one token -- under half of the 3D
+    tokens (none, in fact) stay at the f32 bar, though no element moves by more than the worst-element bar; a padded query cell left alive --
+    the worst-element bar.  Masked 2D stream, self and cross."""
+    f32 = torch.float32
+    x3, x2 = bf.coarse_inputs(B, L3, L2)
+    mask = bf.coarse_mask("mid_tile", B, L2)
+    first_pad = int(mask[0].sum())
+    slack = [bf.coarse_kv_slack(sd, P, x, m) for x, m in ((x3, None), (x2, mask))]
+    kv = (bf.coarse_kv_faithful(sd, P, x3), bf.coarse_kv_faithful(sd, P, x2, mask))
+
+    def differ(s, got):
+        return bf.coarse_kv_check(bf.bf16_round(got[0]).double(), kv[s][0], slack[s][0])[0]
+    for pt in (1, 2, 3):
+        d = [differ(0, bf.coarse_kv_faithful(sd, P, x3, None, f32, {pt})), differ(1, bf.coarse_kv_faithful(sd, P, x2, mask, f32, {pt}))]
+        print(f"L=({L3},{L2}) without rounding point {pt}: {100 * d[0]:.1f} % / {100 * d[1]:.1f} % of the KV elements differ")
+        assert min(d) > 10 * bf.COARSE_KV_ULP_SHARE
+    leak = mask.clone()
+    leak[0, first_pad] = True
+    d = differ(1, bf.coarse_kv_faithful(sd, P, x2, leak, f32))
+    print(f"L=({L3},{L2}) one padded cell in phi(K): {100 * d:.1f} % of the KV elements differ")
+    assert d > 10 * bf.COARSE_KV_ULP_SHARE
+    if L3 > 16 * bf.SLAB:
+        head = torch.ones(B, L3, dtype=torch.bool)
+        head[:, 16 * bf.SLAB:] = False
+        d = differ(0, bf.coarse_kv_faithful(sd, P, x3, head, f32))
+        print(f"L=({L3},{L2}) kv_sum without the slabs from 16 on: {100 * d:.1f} % of the KV elements differ")
+        assert d > 10 * bf.COARSE_KV_ULP_SHARE
+    for cross in (False, True):
+        r3, r2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, mask, kv=kv)
+        src3, src2, S3, S2 = (kv[1], kv[0], L2, L3) if cross else (kv[0], kv[1], L3, L2)
+        wrong = {f"without rounding point {pt}": bf.coarse_layer_faithful(sd, P, x3, *src3, S3, None, f32, {pt}) for pt in (5, 6, 7, 8, 9, 10)}
+        wrong["S + 1"] = bf.coarse_layer_faithful(sd, P, x3, *src3, S3 + 1, None, f32)
+        wrong["S - 1"] = bf.coarse_layer_faithful(sd, P, x3, *src3, S3 - 1, None, f32)
+        for name, y in wrong.items():
+            share, worst = bf.token_share_at_f32_bar(y, r3), (y.double() - r3).abs().max().item()
+            print(f"L=({L3},{L2}) cross={cross} {name}: 3D token share {share:.3f}, worst element {worst:.2e}")
+            assert share < 0.1 and worst < 2e-2
+        y = bf.coarse_layer_faithful(sd, P, x2, *src2, S2, leak, f32)
+        assert (y.double() - r2).abs().max().item() > 10 * bf.COARSE_WORST_BAR and bf.token_share_at_f32_bar(y, r2) > 0.9
+
+
+@pytest.mark.parametrize("cross", [False, True])
+def test_coarse_why_the_reference_is_fed_the_kv_under_test(sd, cross):
+    """At L = 545 the stand-in's OWN KV differs from the reference's in a few elements by one bf16 step, and each reaches every token of the
+    stream that reads it: fed its own KV the stand-in's token share is far below the teacher-forced one.  Hence the GPU test checks KV on its
+    own and feeds the device's KV to the layer reference."""
+    x3, x2 = bf.coarse_inputs(1, 545, 300)
+    r3, r2, kv = bf.coarse_streams_faithful(sd, P, x3, x2, cross)
+    f3, f2, skv = bf.coarse_streams_faithful(sd, P, x3, x2, cross, dtype=torch.float32)
+    t3, t2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, kv=kv, dtype=torch.float32)
+    flips = [int((bf.bf16_ulps_apart(bf.bf16_round(a[0]), bf.bf16_round(b[0])) > 0).sum()) for a, b in zip(skv, kv)]
+    free = (bf.token_share_at_f32_bar(f3, r3), bf.token_share_at_f32_bar(f2, r2))
+    forced = (bf.token_share_at_f32_bar(t3, r3), bf.token_share_at_f32_bar(t2, r2))
+    print(f"cross={cross}: KV elements one step away (3D, 2D source) {flips} of 8192; token share free-running {free[0]:.3f} / {free[1]:.3f}, "
+          f"teacher-forced {forced[0]:.3f} / {forced[1]:.3f}")
+    assert min(forced) >= 0.9
+    for s in (0, 1):                                        # stream s reads block s (self) or 1 - s (cross)
+        if flips[s ^ int(cross)] == 0:
+            assert free[s] >= 0.9
+    # the reference fed the stand-in's KV brings the stand-in back to the bar: nothing but KV separates the two runs
+    b3, b2, _ = bf.coarse_streams_faithful(sd, P, x3, x2, cross, kv=skv)
+    assert min(bf.token_share_at_f32_bar(f3, b3), bf.token_share_at_f32_bar(f2, b2)) >= 0.9
 
 
 @pytest.mark.parametrize("cross_layers,floor", [([False, True], 0.55), ([False], 0.70), ([True], 0.70)])
