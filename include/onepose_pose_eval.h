@@ -1,6 +1,6 @@
 /* libonepose_pose_eval.so -- pose evaluation on the device (gfx950): the cm-degree errors, ADD, ADD-S and the 2D projection error of a
- * whole sequence of poses against their ground truth.  C ABI; its own library, outside the table of
- * cabi.LIBRARIES.
+ * whole sequence of poses against their ground truth.  C ABI; its own library (a row of
+ * cabi.LIBRARIES: DESIGN.md section 1b).
  *
  * This header is the specification; tests/pose_eval_oracle.py restates it in numpy, one function per stage.  All arithmetic is float64,
  * every expression evaluated in the written order with contraction off; the operations are + - * /, sqrt and comparisons, so the device
@@ -13,8 +13,8 @@
  * read).  A model is verts [V][3] float32, widened to float64.  A model vertex x under a pose:
  *     X'_k = ((R[k][0] * x0 + R[k][1] * x1) + R[k][2] * x2) + t_k.
  */
-#ifndef POSE_EVAL_H
-#define POSE_EVAL_H
+#ifndef ONEPOSE_POSE_EVAL_H
+#define ONEPOSE_POSE_EVAL_H
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,5 +1,5 @@
 /* libonepose_postopt_lm.so -- the second-order (Levenberg-Marquardt) solver of the keypoint-free SfM depth refinement, on the device
- * (gfx950).  C ABI; its own library, outside the table of cabi.LIBRARIES, so that libonepose_hip.so keeps its
+ * (gfx950).  C ABI; its own library (a row of cabi.LIBRARIES: DESIGN.md section 1b), so that libonepose_hip.so keeps its
  * symbol set.
  *
  * The problem is the one ophip_postopt_refine (onepose_hip.h) solves with Adam: every residual row folds to h(d) = d * a + b, every
@@ -10,8 +10,8 @@
  * Every entry returns 0, or -1 on invalid arguments, or a positive HIP error code; oplm_last_error() says which.  All pointers are
  * device pointers; `stream` is a hipStream_t.
  */
-#ifndef POSTOPT_LM_H
-#define POSTOPT_LM_H
+#ifndef ONEPOSE_POSTOPT_LM_H
+#define ONEPOSE_POSTOPT_LM_H
 #include <stddef.h>
 #ifdef __cplusplus
 extern "C" {

@@ -1,6 +1,6 @@
 /* libonepose_temporal.so -- the temporal pose refinement on the device (gfx950): a pyramidal, translation-only Lucas-Kanade tracker
  * with a forward-backward check, and the glue that carries a frame's 2D-3D matches into a later frame's match table in front of a second
- * PnP.  C ABI; its own library, outside the table of cabi.LIBRARIES.
+ * PnP.  C ABI; its own library (a row of cabi.LIBRARIES: DESIGN.md section 1b).
  *
  * This header is the specification; tests/temporal_oracle.py restates it in numpy, one function per entry.  All per-point arithmetic is
  * float64, every expression evaluated in the written order with contraction off; the operations are + - * /, sqrt, floor and
@@ -11,8 +11,8 @@
  * capacity (NULL: the capacity); rows at or past the count are never read and their outputs never written; every launch is sized by the
  * capacity; nothing is synchronised and no count is read on the host.
  */
-#ifndef TEMPORAL_REFINE_H
-#define TEMPORAL_REFINE_H
+#ifndef ONEPOSE_TEMPORAL_H
+#define ONEPOSE_TEMPORAL_H
 #include <stddef.h>
 #ifdef __cplusplus
 extern "C" {

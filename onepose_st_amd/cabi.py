@@ -1,7 +1,8 @@
 """Reader of the project's C headers (``include/onepose_*.h``: one per entry of ``LIBRARIES`` below, plus ``onepose_pnp.h`` of the host
-library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures and the loaded handle of one
-HIP library.  The headers are the only place a C signature is written; the modules ``LIBRARIES`` names and ``pnp.py`` bind from
-what this reads.
+library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures, the constants and the loaded
+handle of one HIP library.  The headers are the only place a C signature or a constant is written; the modules ``LIBRARIES`` names and
+``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES``; the host library alone keeps a loader of its own
+(``pnp.py``).
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -14,8 +15,9 @@ import re
 from collections import namedtuple
 
 # The HIP libraries, one line each: C prefix, header under include/, file under onepose_st_amd/lib/, the environment variable that names
-# another build of it (A/B runs), the module that binds it.  __graft_entry__.build() checks and loads every entry, the reader below knows
-# an entry point by these prefixes, and DESIGN.md section 1b says what else a new one needs.
+# another build of it (A/B runs), the module that binds it (``Binding.of(__name__)``).  __graft_entry__.build() checks and loads every
+# entry, the reader below knows an entry point by these prefixes (and the host library's ``oppnp``), tests/test_cabi_binding.py runs over
+# every entry, and DESIGN.md section 1b says what else a new one needs.
 Library = namedtuple("Library", "prefix header so env module")
 LIBRARIES = (Library("ophip", "onepose_hip.h", "libonepose_hip.so", "OPHIP_LIB", "hip"),
              Library("opsfm", "onepose_sfm.h", "libonepose_sfm.so", "OPSFM_LIB", "sfm_objectblock"),
@@ -24,13 +26,16 @@ LIBRARIES = (Library("ophip", "onepose_hip.h", "libonepose_hip.so", "OPHIP_LIB",
              Library("opsff", "onepose_sfm_fine.h", "libonepose_sfm_fine.so", "OPSFF_LIB", "sfm_fine"),
              Library("oppnpd", "onepose_pnp_device.h", "libonepose_pnp_device.so", "OPPNPD_LIB", "pnp_device"),
              Library("optrk", "onepose_track.h", "libonepose_track.so", "OPTRK_LIB", "track_device"),
-             Library("opdet", "onepose_detect.h", "libonepose_detect.so", "OPDET_LIB", "detect_device"))
+             Library("opdet", "onepose_detect.h", "libonepose_detect.so", "OPDET_LIB", "detect_device"),
+             Library("oplm", "onepose_postopt_lm.h", "libonepose_postopt_lm.so", "OPLM_LIB", "postopt_lm"),
+             Library("optmp", "onepose_temporal.h", "libonepose_temporal.so", "OPTMP_LIB", "temporal"),
+             Library("opevl", "onepose_pose_eval.h", "libonepose_pose_eval.so", "OPEVL_LIB", "pose_eval"))
 
 SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 RETURN_TYPES = (*SCALARS, "const char*", "void", "void*")
 _POINTEES = (*SCALARS, "char", "unsigned char", "void")
-_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp', 'oplm', 'optmp', 'opevl'])})_\w+"  # the host library (pnp.py), postopt_lm.py, temporal.py, pose_eval.py
+_NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp'])})_\w+"          # oppnp: the host library (pnp.py)
 
 
 class HeaderError(ValueError):
@@ -136,7 +141,7 @@ def check_mirror(mirror, struct_name: str, fields: tuple):
 
 class Binding:
     """One HIP library bound from its header: ``header`` (an empty parse when the file is missing, and ``load()`` says so),
-    ``signatures`` (name -> (restype, argtypes)), ``exported_symbols``, ``abi_version`` (the header's ``<PREFIX>_ABI_VERSION``), ``path``
+    ``signatures`` (name -> (restype, argtypes)), ``exported_symbols``, ``abi_version`` (``constant("ABI_VERSION")``), ``path``
     (the environment variable ``env``, read once here, or ``lib/<so>``) and ``handle`` (``None`` until ``load()``)."""
 
     def __init__(self, header: str, so: str, prefix: str, env: str, mirrors: dict | None = None):
@@ -147,7 +152,6 @@ class Binding:
         self.header = parse(open(self.header_path).read() if os.path.exists(self.header_path) else "")
         self.signatures = {name: signature(proto, mirrors) for name, proto in self.header.prototypes.items()}
         self.exported_symbols = tuple(self.signatures)
-        self.abi_version = self.header.defines.get(f"{prefix.upper()}_ABI_VERSION")
         self.handle = None
         self._params = {name: proto.params for name, proto in self.header.prototypes.items()}
         self._last_error = f"{prefix}_last_error"
@@ -157,6 +161,20 @@ class Binding:
         """The binding of the ``LIBRARIES`` entry whose module is ``module`` (a ``__name__``)"""
         entry, = [e for e in LIBRARIES if e.module == module.rpartition(".")[2]]
         return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors)
+
+    @property
+    def abi_version(self):
+        return self.constant("ABI_VERSION")
+
+    def constant(self, name: str):
+        """The header's ``#define <PREFIX>_<name> <integer literal>``: ``None`` when the header file is missing (``load()`` says so),
+        ``HeaderError`` when the header is there and has no such define"""
+        macro = f"{self.prefix.upper()}_{name}"
+        if macro in self.header.defines:
+            return self.header.defines[macro]
+        if os.path.exists(self.header_path):
+            raise HeaderError(f"{self.header_path}: no #define {macro} <integer literal>")
+        return None
 
     def library_path(self) -> str:
         return self.path

@@ -1,4 +1,4 @@
-// Pose evaluation on the device (include/pose_eval.h): the cm-degree errors, ADD, ADD-S and the 2D projection error
+// Pose evaluation on the device (include/onepose_pose_eval.h): the cm-degree errors, ADD, ADD-S and the 2D projection error
 // of a sequence of poses against their ground truth.  The header is the specification; everything is float64 in the written order.
 //
 // errors_kernel     one lane per frame: the flags, the cosine of the rotation error (no arc cosine here) and the translation error.
@@ -11,7 +11,7 @@
 // finish_kernel     one lane per frame adds its partials in ascending block order and divides by V.
 // No atomics and no MFMA (its rounding is not the written order) anywhere in this file.
 #include "capi_error.h"
-#include "pose_eval.h"
+#include "onepose_pose_eval.h"
 #include <math.h>
 
 #pragma clang fp contract(off)

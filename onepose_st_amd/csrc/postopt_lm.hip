@@ -1,4 +1,4 @@
-// The second-order solver of the keypoint-free SfM depth refinement (include/postopt_lm.h): Levenberg-Marquardt on the problem that
+// The second-order solver of the keypoint-free SfM depth refinement (include/onepose_postopt_lm.h): Levenberg-Marquardt on the problem that
 // postopt.hip solves with Adam, in float64, every expression in the written order.
 //
 // fold_row (postopt_fold.h) turns every residual row into h(d) = d * a + b, and every track owns one scalar depth, so the normal
@@ -10,7 +10,7 @@
 // the per-track costs in index order into the two totals.
 #include "capi_error.h"
 #include "postopt_fold.h"
-#include "postopt_lm.h"
+#include "onepose_postopt_lm.h"
 #include <stdint.h>
 
 namespace {

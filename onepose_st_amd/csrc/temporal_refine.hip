@@ -1,4 +1,4 @@
-// The temporal pose refinement (include/temporal_refine.h): the float32 image pyramid, the pyramidal translation-only
+// The temporal pose refinement (include/onepose_temporal.h): the float32 image pyramid, the pyramidal translation-only
 // Lucas-Kanade tracker with its forward-backward check, and the two table kernels (collect, inject) around it.  The header is the
 // specification; everything per point is float64 in the written order.
 //
@@ -14,7 +14,7 @@
 // inject_source_    position of a row never depends on timing.  inject is one launch for the frame's own rows and one per source, each
 // kernel            starting at the count the launch before it left.  No atomics anywhere in this file.
 #include "capi_error.h"
-#include "temporal_refine.h"
+#include "onepose_temporal.h"
 #include <math.h>
 #include <stdint.h>
 

@@ -38,15 +38,8 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-MAX_VIEWS = _BINDING.header.defines.get("OPDET_MAX_VIEWS")
-MAX_TRIALS = _BINDING.header.defines.get("OPDET_MAX_TRIALS")
-DEFAULT_TRIALS = _BINDING.header.defines.get("OPDET_DEFAULT_TRIALS")
-MAX_ROWS = _BINDING.header.defines.get("OPDET_MAX_ROWS")
-MAX_SIDE = _BINDING.header.defines.get("OPDET_MAX_SIDE")
-SCORE_CHUNK = _BINDING.header.defines.get("OPDET_SCORE_CHUNK")
-STATUS_NO_MODEL = _BINDING.header.defines.get("OPDET_STATUS_NO_MODEL")
-STATUS_DEGENERATE = _BINDING.header.defines.get("OPDET_STATUS_DEGENERATE")
-STATUS_NEEDS_MORE = _BINDING.header.defines.get("OPDET_STATUS_NEEDS_MORE")
+MAX_VIEWS, MAX_TRIALS, DEFAULT_TRIALS, MAX_ROWS, MAX_SIDE, SCORE_CHUNK, STATUS_NO_MODEL, STATUS_DEGENERATE, STATUS_NEEDS_MORE = map(_BINDING.constant, (
+    "MAX_VIEWS", "MAX_TRIALS", "DEFAULT_TRIALS", "MAX_ROWS", "MAX_SIDE", "SCORE_CHUNK", "STATUS_NO_MODEL", "STATUS_DEGENERATE", "STATUS_NEEDS_MORE"))
 
 
 def _check_options(min_matches, reproj, confidence, trials):

@@ -54,11 +54,11 @@ _MIRRORS = {"ophip_sample_job": SampleJob, "ophip_frame_desc": FrameDesc, "ophip
 _BINDING = cabi.Binding.of(__name__, _MIRRORS)
 for _name, _fields in _BINDING.header.structs.items():
     cabi.check_mirror(_MIRRORS[_name], _name, _fields)
-library_path, load, call = _BINDING.library_path, _BINDING.load, _BINDING.call
+library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version                                      # what the FrameDesc / FrameLayout mirrors above are written for
-SAMPLE_MAX_JOBS = _BINDING.header.defines.get("OPHIP_SAMPLE_MAX_JOBS")
-COARSE_PLANES_READY = _BINDING.header.defines.get("OPHIP_COARSE_PLANES_READY")    # or-ed into ophip_coarse_match's nsplit
+# COARSE_PLANES_READY is or-ed into ophip_coarse_match's nsplit
+SAMPLE_MAX_JOBS, COARSE_PLANES_READY = map(_BINDING.constant, ("SAMPLE_MAX_JOBS", "COARSE_PLANES_READY"))
 
 
 def ptr(t: torch.Tensor | None, dtype=torch.float32):

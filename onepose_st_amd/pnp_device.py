@@ -43,17 +43,10 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-MAX_TRIALS = _BINDING.header.defines.get("OPPNPD_MAX_TRIALS")
-DEFAULT_TRIALS = _BINDING.header.defines.get("OPPNPD_DEFAULT_TRIALS")
-MAX_ROWS = _BINDING.header.defines.get("OPPNPD_MAX_ROWS")
-MAX_FRAMES = _BINDING.header.defines.get("OPPNPD_MAX_FRAMES")
-ROW_DOUBLES = _BINDING.header.defines.get("OPPNPD_ROW_DOUBLES")
-SELECT_BLOCK = _BINDING.header.defines.get("OPPNPD_SELECT_BLOCK")
-SCORE_CHUNK = _BINDING.header.defines.get("OPPNPD_SCORE_CHUNK")
-STATUS_NO_POSE = _BINDING.header.defines.get("OPPNPD_STATUS_NO_POSE")
-STATUS_NEEDS_MORE = _BINDING.header.defines.get("OPPNPD_STATUS_NEEDS_MORE")
-MIN_INLIERS = _BINDING.header.defines.get("OPPNPD_MIN_INLIERS")
-MAX_NEEDED = _BINDING.header.defines.get("OPPNPD_MAX_NEEDED")
+(MAX_TRIALS, DEFAULT_TRIALS, MAX_ROWS, MAX_FRAMES, ROW_DOUBLES, SELECT_BLOCK, SCORE_CHUNK, STATUS_NO_POSE, STATUS_NEEDS_MORE, MIN_INLIERS,
+ MAX_NEEDED) = map(_BINDING.constant, (
+    "MAX_TRIALS", "DEFAULT_TRIALS", "MAX_ROWS", "MAX_FRAMES", "ROW_DOUBLES", "SELECT_BLOCK", "SCORE_CHUNK", "STATUS_NO_POSE", "STATUS_NEEDS_MORE",
+    "MIN_INLIERS", "MAX_NEEDED"))
 
 
 def _check_policy(solver, use_pycolmap_ransac) -> None:

@@ -2,15 +2,14 @@
 out" and the numbers of the paper -- ``query_pose_error`` (cm-degree), ``add_metric`` (ADD, and ADD-S with ``syn=True``),
 ``projection_2d_error`` and ``aggregate_metrics`` -- for every pose of a sequence at once, next to ``pnp_device.DevicePoses``.
 
-The specification is ``include/pose_eval.h`` (``tests/pose_eval_oracle.py`` restates it in numpy, one function per stage): float64 in the
+The specification is ``include/onepose_pose_eval.h`` (``tests/pose_eval_oracle.py`` restates it in numpy, one function per stage): float64 in the
 written order, every mean summed in one fixed order (blocks of 256 vertices, a stride-128 .. 1 tree, the partials in ascending order), so
 the device outputs are bit-equal to the oracle.  ADD-S is the exact nearest-neighbour mean (the reference builds a ``cKDTree`` per frame
 on one host core): every target vertex against every predicted vertex, the predicted ones staged through LDS, launches chunked over
 frames by ``MAX_PAIRS_PER_LAUNCH``.  The arc cosine is taken on the host after the one read-back, on ``F`` scalars.
 
-The kernels are HIP (``csrc/pose_eval.hip`` in ``libonepose_pose_eval.so``).  The library sits outside ``cabi.LIBRARIES`` (DESIGN.md
-section 1b), so the binding is written out here.  CPU tensors raise :class:`hip.HipLibraryError` (no CPU fallback); nothing is
-synchronised and nothing is read on the host until :meth:`DevicePoseErrors.to_host`.
+The kernels are HIP (``csrc/pose_eval.hip`` in ``libonepose_pose_eval.so``).  CPU tensors raise :class:`hip.HipLibraryError` (no CPU
+fallback); nothing is synchronised and nothing is read on the host until :meth:`DevicePoseErrors.to_host`.
 """
 from __future__ import annotations
 
@@ -19,12 +18,11 @@ import torch
 
 from . import cabi, hip
 
-_BINDING = cabi.Binding("pose_eval.h", "libonepose_pose_eval.so", "opevl", "OPEVL_LIB")
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-_DEFINES = _BINDING.header.defines
-MAX_FRAMES, MAX_VERTICES, BLOCK, MAX_PAIRS_PER_LAUNCH, NO_POSE, BAD_INPUT = (_DEFINES.get(f"OPEVL_{n}") for n in (
+MAX_FRAMES, MAX_VERTICES, BLOCK, MAX_PAIRS_PER_LAUNCH, NO_POSE, BAD_INPUT = map(_BINDING.constant, (
     "MAX_FRAMES", "MAX_VERTICES", "BLOCK", "MAX_PAIRS_PER_LAUNCH", "NO_POSE", "BAD_INPUT"))
 UNIT_SCALE = {"m": 100.0, "cm": 1.0, "mm": 0.1}
 

@@ -46,9 +46,7 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-MAX_ROWS = _BINDING.header.defines.get("OPSFF_MAX_ROWS")
-CTRL_INTS = _BINDING.header.defines.get("OPSFF_CTRL_INTS")
-NO_ROW = _BINDING.header.defines.get("OPSFF_NO_ROW")
+MAX_ROWS, CTRL_INTS, NO_ROW = map(_BINDING.constant, ("MAX_ROWS", "CTRL_INTS", "NO_ROW"))
 COARSE_SCALE = 8.0                                  # image rows per coarse row (ResNetFPN 8 -> 2)
 PAIR_KEYS = ("mkpts0_c", "mkpts1_c", "row_left", "row_right")
 RESULT_KEYS = ("mkpts0_c", "mkpts1_c", "mkpts0_f", "mkpts1_f", "expec_f", "i_ids", "j_ids", "feature_c0", "feature_c1", "feature0", "feature1")

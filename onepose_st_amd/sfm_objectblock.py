@@ -57,9 +57,7 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-MAX_ITEMS = _BINDING.header.defines.get("OPSFM_MAX_ITEMS")
-PAIR_TILE = _BINDING.header.defines.get("OPSFM_PAIR_TILE")
-PAIR_MAX_CHUNKS = _BINDING.header.defines.get("OPSFM_PAIR_MAX_CHUNKS")
+MAX_ITEMS, PAIR_TILE, PAIR_MAX_CHUNKS = map(_BINDING.constant, ("MAX_ITEMS", "PAIR_TILE", "PAIR_MAX_CHUNKS"))
 DIM_COARSE, DIM_FINE = 256, 128
 
 

@@ -69,9 +69,7 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-MAX_IMAGES = _BINDING.header.defines.get("OPSFT_MAX_IMAGES")
-MAX_ITEMS = _BINDING.header.defines.get("OPSFT_MAX_ITEMS")
-CTRL_INTS = _BINDING.header.defines.get("OPSFT_CTRL_INTS")
+MAX_IMAGES, MAX_ITEMS, CTRL_INTS = map(_BINDING.constant, ("MAX_IMAGES", "MAX_ITEMS", "CTRL_INTS"))
 MAX_ID = 2 ** 53
 MODEL_KEYS = ("image_ids", "kpt_offsets", "xys", "point3D_ids", "K", "R", "t", "point_ids", "xyz", "track_offsets", "track_image", "track_kpt")
 PLAN_KEYS = ("keyframes", "state", "is_keyframe", "assigned_image", "assigned_kpt", "initial_depth")

@@ -57,12 +57,8 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-MAX_ITEMS = _BINDING.header.defines.get("OPSTR_MAX_ITEMS")
-SHORT_TRACK = _BINDING.header.defines.get("OPSTR_SHORT_TRACK")
-MAX_HYPOTHESES = _BINDING.header.defines.get("OPSTR_MAX_HYPOTHESES")
-MAX_REFINE_STEPS = _BINDING.header.defines.get("OPSTR_MAX_REFINE_STEPS")
-MAX_ROUNDS = _BINDING.header.defines.get("OPSTR_MAX_ROUNDS")
-CAMERA_DOUBLES = _BINDING.header.defines.get("OPSTR_CAMERA_DOUBLES")
+MAX_ITEMS, SHORT_TRACK, MAX_HYPOTHESES, MAX_REFINE_STEPS, MAX_ROUNDS, CAMERA_DOUBLES = map(_BINDING.constant, (
+    "MAX_ITEMS", "SHORT_TRACK", "MAX_HYPOTHESES", "MAX_REFINE_STEPS", "MAX_ROUNDS", "CAMERA_DOUBLES"))
 MERGED_KEYS = ("keypoints", "kpt_offsets", "match_ids", "pair_offsets", "pair_images")
 CAMERA_KEYS = ("image_ids", "K", "R", "t")
 DEFAULTS = {"max_reproj_error": 4.0, "min_tri_angle": 1.5, "max_hypotheses": 256, "refine_steps": 5, "max_rounds": 3}

@@ -5,12 +5,11 @@ the PnP runs a second time on the larger table.
 
 The reference tracks with CoTracker2 (a submodule and a checkpoint this project does not have).  The tracker here is the project's own: a
 pyramidal, translation-only Lucas-Kanade tracker with a forward-backward check, float64 per point in a fixed order, specified entry by
-entry in ``include/temporal_refine.h`` and restated in numpy by ``tests/temporal_oracle.py``.  Which rows are carried, the crop <->
+entry in ``include/onepose_temporal.h`` and restated in numpy by ``tests/temporal_oracle.py``.  Which rows are carried, the crop <->
 original mapping (``MKPT.map_to_original`` / ``map_to_crop``), the concatenation order and the second PnP are the reference's.
 
-The kernels are HIP (``csrc/temporal_refine.hip`` in ``libonepose_temporal.so``).  The library sits outside ``cabi.LIBRARIES`` (DESIGN.md
-section 1b), so the binding is written out here.  CPU tensors raise :class:`hip.HipLibraryError` (no CPU fallback); nothing is
-synchronised and no count is read on the host until :meth:`RefinedSequence.to_host`.
+The kernels are HIP (``csrc/temporal_refine.hip`` in ``libonepose_temporal.so``).  CPU tensors raise :class:`hip.HipLibraryError` (no CPU
+fallback); nothing is synchronised and no count is read on the host until :meth:`RefinedSequence.to_host`.
 """
 from __future__ import annotations
 
@@ -22,14 +21,13 @@ import torch
 
 from . import cabi, hip
 
-_BINDING = cabi.Binding("temporal_refine.h", "libonepose_temporal.so", "optmp", "OPTMP_LIB")
+_BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-_DEFINES = _BINDING.header.defines
-DEGENERATE, OUT_OF_IMAGE, FB_FAIL, BAD_INPUT, FLAG_MAX_ITERS, LOST = (_DEFINES.get(f"OPTMP_{n}") for n in (
-    "DEGENERATE", "OUT_OF_IMAGE", "FB_FAIL", "BAD_INPUT", "FLAG_MAX_ITERS", "LOST"))
-MAX_LEVELS, MIN_WINDOW, MAX_WINDOW, MAX_ITERS, MAX_ROWS, MAX_SOURCES = (_DEFINES.get(f"OPTMP_{n}") for n in (
+(DEGENERATE, OUT_OF_IMAGE, FB_FAIL, BAD_INPUT, FLAG_MAX_ITERS, LOST,
+ MAX_LEVELS, MIN_WINDOW, MAX_WINDOW, MAX_ITERS, MAX_ROWS, MAX_SOURCES) = map(_BINDING.constant, (
+    "DEGENERATE", "OUT_OF_IMAGE", "FB_FAIL", "BAD_INPUT", "FLAG_MAX_ITERS", "LOST",
     "MAX_LEVELS", "MIN_WINDOW", "MAX_WINDOW", "MAX_ITERS", "MAX_ROWS", "MAX_SOURCES"))
 DEFAULTS = dict(levels=4, window=21, max_iters=30, eps=0.01, min_eig=1.0, fb_threshold=1.0)
 

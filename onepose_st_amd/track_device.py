@@ -28,12 +28,8 @@ _BINDING = cabi.Binding.of(__name__)                # the header is the one plac
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
-LOST_POSE = _BINDING.header.defines.get("OPTRK_LOST_POSE")
-LOST_BOX = _BINDING.header.defines.get("OPTRK_LOST_BOX")
-STALE = _BINDING.header.defines.get("OPTRK_STALE")
-NEEDS_HOST = _BINDING.header.defines.get("OPTRK_NEEDS_HOST")
-MAX_BOX_SIDE = _BINDING.header.defines.get("OPTRK_MAX_BOX_SIDE")
-MAX_CROP = _BINDING.header.defines.get("OPTRK_MAX_CROP")
+LOST_POSE, LOST_BOX, STALE, NEEDS_HOST, MAX_BOX_SIDE, MAX_CROP = map(_BINDING.constant, (
+    "LOST_POSE", "LOST_BOX", "STALE", "NEEDS_HOST", "MAX_BOX_SIDE", "MAX_CROP"))
 # byte offsets of a state's fields in its block: box 16, flag 4 (+ 4 of padding), K_crop 72, trans 72
 _O_BOX, _O_FLAG, _O_KCROP, _O_TRANS, STATE_BYTES = 0, 16, 24, 96, 168
 

@@ -1,4 +1,4 @@
-"""The specification of the pose evaluation (include/pose_eval.h) restated in numpy float64, one function per stage,
+"""The specification of the pose evaluation (include/onepose_pose_eval.h) restated in numpy float64, one function per stage,
 every expression in the written order.  The device kernels are compared with these bit for bit; nothing here calls a library routine whose
 evaluation order is not pinned (no ``np.dot``, ``np.linalg.norm``, ``np.mean`` or pairwise ``np.sum``)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""numpy restatement of include/temporal_refine.h, one function per entry: the float32 pyramid, the float64
+"""numpy restatement of include/onepose_temporal.h, one function per entry: the float32 pyramid, the float64
 pyramidal Lucas-Kanade tracker with the device's summation order, collect and inject.  Plain loops over points, vectors over the window;
 every expression in the header's order, so the device equals this bit for bit.  Also the analytic test scene of the temporal tests."""
 import numpy as np

@@ -1,8 +1,9 @@
 """The Python bindings take every C signature, constant and structure layout from ``include/*.h`` (``onepose_st_amd/cabi.py``).
 CPU only: the reader on the real headers and on made-up ones, the structure mirrors, ``cabi.Binding`` (arity check, error mapping, load
-errors) on stand-in handles and on the built libraries for every row of ``cabi.LIBRARIES`` (the table-driven tests below: one case per
-row, and one hand-written rejected call per satellite library in ``REJECTED``), and three faults seeded into copies of the header that
-the prototypes written out below must catch."""
+errors, checked constants) on stand-in handles and on the built libraries for every row of ``cabi.LIBRARIES`` (the table-driven tests
+below: one case per row, and per satellite library the symbols written out in ``SYMBOLS`` and one hand-written rejected call in
+``REJECTED``), and three faults seeded into copies of the header that the prototypes written out below must catch."""
+import ast
 import ctypes
 import glob
 import importlib
@@ -139,6 +140,30 @@ def test_reader_on_made_up_headers():
                                          ("long long", "pe_bs", None), ("const void*", "w", 16), ("size_t", "total", None), ("size_t", "used", None))}
 
 
+def test_constant_on_a_made_up_header(tmp_path):
+    (tmp_path / "made_up.h").write_text(MADE_UP)
+    binding = cabi.Binding(str(tmp_path / "made_up.h"), "libmade_up.so", "ophip", "OPHIP_LIB")       # an absolute path stands as it is
+    assert binding.header_path == str(tmp_path / "made_up.h") and list(binding.header.prototypes)[0] == "ophip_nothing"
+    assert (binding.constant("SOME_FLAG"), binding.constant("COUNT")) == (0x20, 12)
+    for name in ("NO_SUCH", "NOT_A_LITERAL"):                      # absent, and present but no integer literal
+        with pytest.raises(cabi.HeaderError) as e:
+            binding.constant(name)
+        assert binding.header_path in str(e.value) and f"OPHIP_{name}" in str(e.value)
+    with pytest.raises(cabi.HeaderError, match="OPHIP_ABI_VERSION"):
+        binding.abi_version
+    absent = cabi.Binding("no_such_header.h", "libmade_up.so", "ophip", "OPHIP_LIB")
+    assert absent.constant("COUNT") is None and absent.abi_version is None
+
+
+def test_the_reader_knows_the_prefixes_of_the_table_and_of_the_host_library():
+    prefixes = [e.prefix for e in cabi.LIBRARIES] + ["oppnp"]
+    assert cabi._NAME == rf"\b(?:{'|'.join(prefixes)})_\w+"
+    for prefix in prefixes:
+        assert list(cabi.parse(f"int {prefix}_f(int x);").prototypes) == [f"{prefix}_f"]
+    for text in ("int opzz_f(int x);", "int op_f(int x);", "int xophip_f(int x);"):
+        assert cabi.parse(text).prototypes == {}
+
+
 @pytest.mark.parametrize("text,line", [
     ("int ophip_a(int x);\n\nint ophip_fn_pointer(int (*cb)(int), void* stream);\n", 3),      # a parameter it cannot read
     ("/* two\n lines */\nint ophip_b(struct foo* x);\n", 3),                                   # a type it does not know
@@ -213,31 +238,35 @@ def test_call_checks_the_number_of_arguments(monkeypatch):
     assert len(lib.entered) == 1                                    # nothing else reached the handle
 
 
+def _status_entries(binding):
+    """the entry points of a binding that return a status and take arguments"""
+    return [p for p in binding.header.prototypes.values() if p.ret == "int" and p.params]
+
+
 def _status_entry(binding):
-    """the first entry point of a binding that returns a status and takes arguments"""
-    return next(p for p in binding.header.prototypes.values() if p.ret == "int" and p.params)
+    return _status_entries(binding)[0]
 
 
 @pytest.mark.parametrize("module", BINDINGS)
 def test_every_binding_checks_the_number_of_arguments(module, monkeypatch):
-    """the same statement for each library, through the names its module exports"""
-    binding, mod, lib = BINDINGS[module], importlib.import_module(f"onepose_st_amd.{module}"), _StandIn()
-    monkeypatch.setattr(binding, "handle", lib)
-    proto = _status_entry(binding)
-    args = (None,) * len(proto.params)
-    mod.call(proto.name, *args)
-    assert lib.entered == [(proto.name, args)]
-    for wrong in (args + (None,), args[:-1]):
-        for check in ((lambda: mod.call(proto.name, *wrong)), (lambda: binding.check_arity(proto.name, wrong))):
-            with pytest.raises(TypeError) as e:
-                check()
-            msg = str(e.value)
-            assert proto.name in msg and f"takes {len(args)} arguments" in msg and f"{len(wrong)} given" in msg
-            assert ", ".join(n for _, n in proto.params) in msg
-    binding.check_arity(proto.name, args)
-    if module != "hip":
-        assert mod.check_arity == binding.check_arity
-    assert len(lib.entered) == 1                                    # nothing else reached the handle
+    """the same statement for each library and each of its entry points, through the names its module exports"""
+    binding, mod = BINDINGS[module], importlib.import_module(f"onepose_st_amd.{module}")
+    assert mod.check_arity == binding.check_arity
+    for proto in _status_entries(binding):
+        lib = _StandIn()
+        monkeypatch.setattr(binding, "handle", lib)
+        args = (None,) * len(proto.params)
+        mod.call(proto.name, *args)
+        assert lib.entered == [(proto.name, args)]
+        for wrong in (args + (None,), args[:-1]):
+            for check in ((lambda: mod.call(proto.name, *wrong)), (lambda: mod.check_arity(proto.name, wrong))):
+                with pytest.raises(TypeError) as e:
+                    check()
+                msg = str(e.value)
+                assert f"{proto.name} takes {len(args)} arguments" in msg and f"{len(wrong)} given" in msg
+                assert ", ".join(n for _, n in proto.params) in msg
+        mod.check_arity(proto.name, args)
+        assert len(lib.entered) == 1                                # nothing else reached the handle
 
 
 @pytest.mark.parametrize("module", BINDINGS)
@@ -329,13 +358,17 @@ def test_missing_header_is_reported_by_load(entry):
     assert binding.handle is None
 
 
-def test_missing_library_is_reported_by_load(monkeypatch, tmp_path):
-    monkeypatch.setenv("OPSFT_LIB", str(tmp_path / "libonepose_absent.so"))        # read once, when the binding is made
-    binding = cabi.Binding.of("onepose_st_amd.sfm_tracks")
-    with pytest.raises(cabi.HipLibraryError, match=r"libonepose_absent\.so not found.*__graft_entry__\.build\(\)"):
+@pytest.mark.parametrize("entry", cabi.LIBRARIES, ids=lambda e: e.module)
+def test_missing_library_is_reported_by_load(entry, monkeypatch, tmp_path):
+    absent = str(tmp_path / "libonepose_absent.so")
+    monkeypatch.setenv(entry.env, absent)                           # read once, when the binding is made
+    binding = cabi.Binding.of(f"onepose_st_amd.{entry.module}")
+    with pytest.raises(cabi.HipLibraryError) as e:
         binding.load()
-    monkeypatch.delenv("OPSFT_LIB")
-    assert binding.library_path().endswith("libonepose_absent.so") and BINDINGS["sfm_tracks"].path.endswith("libonepose_sfm_tracks.so")
+    assert str(e.value) == f"{absent} not found: the HIP extension is not built (run __graft_entry__.build())"
+    monkeypatch.delenv(entry.env)
+    assert binding.library_path() == absent and binding.handle is None
+    assert cabi.Binding.of(f"onepose_st_amd.{entry.module}").library_path() == os.path.join(REPO, "onepose_st_amd", "lib", entry.so)
 
 
 def test_the_table_of_libraries_is_complete():
@@ -347,15 +380,69 @@ def test_the_table_of_libraries_is_complete():
     for entry in cabi.LIBRARIES:
         mod, binding = importlib.import_module(f"onepose_st_amd.{entry.module}"), BINDINGS[entry.module]
         assert (binding.so, binding.prefix, binding.header_path) == (entry.so, entry.prefix, os.path.join(REPO, "include", entry.header))
-        assert (mod.load, mod.call, mod.library_path) == (binding.load, binding.call, binding.library_path)
+        assert (mod.library_path, mod.load, mod.check_arity, mod.call) == (binding.library_path, binding.load, binding.check_arity, binding.call)
         assert mod.EXPORTED_SYMBOLS is binding.exported_symbols and mod.ABI_VERSION == binding.abi_version and isinstance(mod.ABI_VERSION, int)
-        assert hasattr(mod, "check_arity") or entry.module == "hip"
         assert mod.EXPORTED_SYMBOLS and all(s.startswith(entry.prefix + "_") for s in mod.EXPORTED_SYMBOLS)
         assert {f"{entry.prefix}_abi_version", f"{entry.prefix}_last_error"} <= set(mod.EXPORTED_SYMBOLS)
         text = open(binding.header_path).read()
         assert set(mod.EXPORTED_SYMBOLS) == set(re.findall(rf"\b({entry.prefix}_\w+)\s*\(", text))
         others = "|".join(e.prefix for e in cabi.LIBRARIES if e is not entry)                        # no other library's prefix in it
         assert not re.findall(rf"\b(?:{others})_\w+\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+# The symbols of every satellite library, written out by hand in header order
+SYMBOLS = {
+    "sfm_objectblock": ("opsfm_abi_version", "opsfm_last_error", "opsfm_workspace_bytes", "opsfm_aggregate", "opsfm_box_test", "opsfm_pair_count",
+                        "opsfm_pair_emit", "opsfm_merge_resolve", "opsfm_group_emit", "opsfm_point_mean"),
+    "sfm_tracks": ("opsft_abi_version", "opsft_last_error", "opsft_assign", "opsft_finish", "opsft_track_rows", "opsft_pair_keys", "opsft_pair_emit",
+                   "opsft_fine_rows"),
+    "sfm_triangulate": ("opstr_abi_version", "opstr_last_error", "opstr_workspace_bytes", "opstr_components", "opstr_prepare", "opstr_round"),
+    "sfm_fine": ("opsff_abi_version", "opsff_last_error", "opsff_row_ids", "opsff_sample_rows"),
+    "pnp_device": ("oppnpd_abi_version", "oppnpd_last_error", "oppnpd_workspace_bytes", "oppnpd_ranges", "oppnpd_prep", "oppnpd_sample", "oppnpd_p3p",
+                   "oppnpd_score", "oppnpd_select", "oppnpd_refine", "oppnpd_solve"),
+    "track_device": ("optrk_abi_version", "optrk_last_error", "optrk_box_set", "optrk_box_from_pose", "optrk_crop"),
+    "detect_device": ("opdet_abi_version", "opdet_last_error", "opdet_workspace_bytes", "opdet_ranges", "opdet_score", "opdet_select",
+                      "opdet_fit_box", "opdet_vote", "opdet_detect"),
+    "postopt_lm": ("oplm_abi_version", "oplm_last_error", "oplm_workspace_bytes", "oplm_refine"),
+    "temporal": ("optmp_abi_version", "optmp_last_error", "optmp_pyramid_bytes", "optmp_pyramid", "optmp_track", "optmp_collect", "optmp_inject"),
+    "pose_eval": ("opevl_abi_version", "opevl_last_error", "opevl_errors", "opevl_add", "opevl_adds", "opevl_proj2d"),
+}
+
+
+def test_the_symbols_written_out_are_those_of_every_satellite_library():
+    """against the module, the header text and the built file; every entry point returns a status and takes the stream last, but for the
+    ABI number, the error text and the size helpers"""
+    assert set(SYMBOLS) == set(BINDINGS) - {"hip"}
+    for module, want in SYMBOLS.items():
+        mod, binding = importlib.import_module(f"onepose_st_amd.{module}"), BINDINGS[module]
+        assert mod.EXPORTED_SYMBOLS == want == tuple(binding.header.prototypes)
+        assert set(re.findall(rf"\b({binding.prefix}_\w+)\s*\(", open(binding.header_path).read())) == set(want)
+        lib = ctypes.CDLL(mod.library_path())
+        assert all(hasattr(lib, s) for s in want)
+        for name, proto in binding.header.prototypes.items():
+            assert len(binding.signatures[name][1]) == len(cabi.signature(proto)[1]) == len(proto.params)
+            if not name.endswith(("_abi_version", "_last_error", "_bytes")):
+                assert proto.ret == "int" and proto.params[-1] == ("void*", "stream"), name
+
+
+def _names_read_with_constant(mod):
+    """the names a module assigns from ``_BINDING.constant``, in the form every module writes: ``A, B = map(_BINDING.constant, ("A", "B"))``"""
+    names = []
+    for node in ast.parse(open(mod.__file__).read()).body:
+        if isinstance(node, ast.Assign) and "_BINDING.constant" in ast.unparse(node.value):
+            targets, (fn, arg) = [t.id for t in node.targets[0].elts], node.value.args
+            assert ast.unparse(node.value.func) == "map" and ast.unparse(fn) == "_BINDING.constant" and targets == list(ast.literal_eval(arg))
+            names += targets
+    return names
+
+
+@pytest.mark.parametrize("entry", cabi.LIBRARIES, ids=lambda e: e.module)
+def test_every_module_imports_and_reads_its_constants(entry):
+    mod = importlib.import_module(f"onepose_st_amd.{entry.module}")
+    names = _names_read_with_constant(mod)
+    assert names and open(mod.__file__).read().count(".constant") == 1          # one assignment holds them all
+    for name in names:
+        assert type(getattr(mod, name)) is int and getattr(mod, name) == BINDINGS[entry.module].header.defines[f"{entry.prefix.upper()}_{name}"], name
 
 
 _PTR = ctypes.c_void_p(8)        # not null and never followed: the entries below return before they launch anything
@@ -370,6 +457,9 @@ REJECTED = {
     "track_device": ("optrk_box_set", {"x1": 1, "y1": 1, "K": _PTR, "S": 0, "box": _PTR, "flag": _PTR, "K_crop": _PTR, "trans": _PTR},
                      "optrk_box_set: crop size S outside [1, OPTRK_MAX_CROP]"),
     "detect_device": ("opdet_ranges", {"cap": 1}, "opdet_ranges: table sizes"),
+    "postopt_lm": ("oplm_refine", {}, "oplm_refine: null pointer"),
+    "temporal": ("optmp_pyramid", {}, "optmp_pyramid: null pointer"),
+    "pose_eval": ("opevl_errors", {}, "opevl_errors: null pointer"),
 }
 
 
@@ -399,7 +489,7 @@ def test_the_built_libraries_answer_for_themselves():
         hip.call("ophip_timing_every", 1)                           # a correct call into another library (host side only)
         assert last_error(module) == text
     reject(next(iter(REJECTED)))                                    # so that the last row too has seen a rejection in another library
-    for module, (_, _, text) in REJECTED.items():                   # and the rejections that followed in the other six
+    for module, (_, _, text) in REJECTED.items():                   # and the rejections that followed in the other nine
         assert last_error(module) == text
 
 

@@ -1,7 +1,7 @@
 """The pose evaluation without a GPU: the numpy restatement of its specification (tests/pose_eval_oracle.py) against what the reference's
 own functions returned (tests/golden/pose_eval_small.npz) and against independent forms, the PLY reader, ``aggregate_metrics``, the
-header and binding of ``libonepose_pose_eval.so`` (outside ``cabi.LIBRARIES``) and its argument checks, which come before any HIP call and
-so answer on a machine with no device.
+header and binding of ``libonepose_pose_eval.so`` (what tests/test_cabi_binding.py does not state for every row of ``cabi.LIBRARIES``)
+and its argument checks, which come before any HIP call and so answer on a machine with no device.
 
 Bounds.  Two evaluation orders of the same exact mean differ by the rounding of the coordinates and of the sum: each coordinate of a
 transformed vertex carries at most a few units of rounding of size ``S = max_k(sum_j |R[k][j] x_j| + |t_k|)``, and a sum of ``V`` terms
@@ -18,11 +18,10 @@ import numpy as np
 import pytest
 import torch
 
-from onepose_st_amd import cabi, hip, pose_eval
+from onepose_st_amd import hip, pose_eval
 from tests import pose_eval_oracle as po
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WANT = ("opevl_abi_version", "opevl_last_error", "opevl_errors", "opevl_add", "opevl_adds", "opevl_proj2d")
 EPS, coordinate_scale, pixel_scale, mean_bound = po.EPS, po.coordinate_scale, po.pixel_scale, po.mean_bound
 
 
@@ -195,13 +194,7 @@ def test_ply_reader(tmp_path):
 
 
 def test_header_and_binding():
-    text = open(os.path.join(REPO, "include", "pose_eval.h")).read()
-    assert pose_eval.EXPORTED_SYMBOLS == WANT
-    assert set(re.findall(r"\b(opevl_\w+)\s*\(", text)) == set(WANT)
-    assert pose_eval.ABI_VERSION == 1 and pose_eval.load().opevl_abi_version() == 1
-    assert "pose_eval" not in {e.module for e in cabi.LIBRARIES} and "opevl" not in {e.prefix for e in cabi.LIBRARIES}
-    lib = ctypes.CDLL(pose_eval.library_path())
-    assert all(hasattr(lib, s) for s in WANT)
+    assert pose_eval.ABI_VERSION == 1
     assert (pose_eval.NO_POSE, pose_eval.BAD_INPUT, pose_eval.BLOCK) == (po.NO_POSE, po.BAD_INPUT, po.BLOCK)
     assert pose_eval.MAX_VERTICES == 2 ** 18 and pose_eval.MAX_FRAMES >= 65536 and pose_eval.UNIT_SCALE == po.UNIT_SCALE
     assert pose_eval.MAX_VERTICES * pose_eval.BLOCK <= pose_eval.MAX_PAIRS_PER_LAUNCH        # one block of the largest model fits one launch
@@ -227,8 +220,6 @@ def test_rejected_calls_answer_before_any_launch():
         with pytest.raises(ValueError, match="null pointer"):
             pose_eval.call(name, *args(name))
         assert last_error() == f"{name}: null pointer"
-        with pytest.raises(TypeError, match=f"{name} takes {len(protos[name].params)} arguments"):
-            pose_eval.call(name, *args(name)[:-1])
     good = dict(V=300, frames=4, pred_stride=12, gt_stride=16, unit_scale=100.0, k_shared=1)
     for name in entries:
         optional = ("status", "stream") if name == "opevl_errors" else ("flags", "stream")       # flags: an output of errors, optional elsewhere
@@ -247,19 +238,6 @@ def test_rejected_calls_answer_before_any_launch():
             with pytest.raises(ValueError, match=re.escape(text)):
                 pose_eval.call(name, *args(name, **{**base, **change}))
             assert text in last_error()
-    hip.call("ophip_timing_every", 1)                                        # another library's call leaves this one's text alone
-    assert "V outside" in last_error()
-
-
-def test_load_error_wording(monkeypatch, tmp_path):
-    monkeypatch.setenv("OPEVL_LIB", str(tmp_path / "missing.so"))
-    b = cabi.Binding("pose_eval.h", "libonepose_pose_eval.so", "opevl", "OPEVL_LIB")
-    assert b.library_path() == str(tmp_path / "missing.so")
-    with pytest.raises(hip.HipLibraryError, match=r"missing\.so not found: the HIP extension is not built \(run __graft_entry__\.build\(\)\)"):
-        b.load()
-    monkeypatch.delenv("OPEVL_LIB")
-    assert cabi.Binding("pose_eval.h", "libonepose_pose_eval.so", "opevl", "OPEVL_LIB").library_path().endswith(
-        os.path.join("onepose_st_amd", "lib", "libonepose_pose_eval.so"))
 
 
 def test_python_api_refuses_cpu_tensors_and_bad_options():

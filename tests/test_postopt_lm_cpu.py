@@ -1,7 +1,7 @@
 """The second-order depth solver without a GPU: the numpy restatement (tests/postopt_lm_oracle.py) against the literal residual and
-the first-order oracle, the header and binding of ``libonepose_postopt_lm.so`` (four symbols, outside ``cabi.LIBRARIES``), its argument
-checks (which come before any HIP call, so they answer on a machine with no device), and the ``hip_second_order`` key of
-``postopt.Optimizer`` on CPU tensors."""
+the first-order oracle, the header and binding of ``libonepose_postopt_lm.so`` (what tests/test_cabi_binding.py does not state for every
+row of ``cabi.LIBRARIES``), its argument checks (which come before any HIP call, so they answer on a machine with no device), and the
+``hip_second_order`` key of ``postopt.Optimizer`` on CPU tensors."""
 import ctypes
 import os
 import re
@@ -71,15 +71,8 @@ def test_oracle_reports_budget_and_degenerate_tracks():
     assert (np.delete(bad["status"], 2) == lm.CONVERGED).all()
 
 
-def test_header_and_binding_have_exactly_four_symbols():
-    text = open(os.path.join(REPO, "include", "postopt_lm.h")).read()
-    want = ("oplm_abi_version", "oplm_last_error", "oplm_workspace_bytes", "oplm_refine")
-    assert postopt_lm.EXPORTED_SYMBOLS == want
-    assert set(re.findall(r"\b(oplm_\w+)\s*\(", text)) == set(want)
-    assert postopt_lm.ABI_VERSION == 1 and postopt_lm.load().oplm_abi_version() == 1
-    assert "postopt_lm" not in {e.module for e in cabi.LIBRARIES} and "oplm" not in {e.prefix for e in cabi.LIBRARIES}
-    lib = ctypes.CDLL(postopt_lm.library_path())
-    assert all(hasattr(lib, s) for s in want)
+def test_header_and_binding():
+    assert postopt_lm.ABI_VERSION == 1
     # the problem's arguments are ophip_postopt_refine's, names and types in order
     first = cabi.parse(open(os.path.join(REPO, "include", "onepose_hip.h")).read()).prototypes["ophip_postopt_refine"].params
     mine = postopt_lm._BINDING.header.prototypes["oplm_refine"].params
@@ -134,9 +127,6 @@ def test_rejected_calls_answer_before_any_launch():
     def last_error():
         return postopt_lm.load().oplm_last_error().decode()
 
-    with pytest.raises(ValueError) as e:
-        postopt_lm.call("oplm_refine", *args())
-    assert str(e.value) == "oplm_refine: oplm_refine: null pointer" and last_error() == "oplm_refine: null pointer"
     ptrs = {n: _PTR for c, n in params if c.endswith("*") and n not in ("residuals", "stream")}
     sizes = dict(P=2, L=5, F=3)
     consts = dict(lam0=1e-4, up=10.0, down=0.1, lam_min=1e-12, lam_max=1e12, step_tol=1e-8, max_iters=50)
@@ -147,12 +137,6 @@ def test_rejected_calls_answer_before_any_launch():
         with pytest.raises(ValueError, match=re.escape(text)):
             postopt_lm.call("oplm_refine", *args(**{**ptrs, **sizes, **consts, "workspace_bytes": 4096, **change}))
         assert text in last_error()
-    hip.call("ophip_timing_every", 1)                                        # another library's call leaves this one's text alone
-    assert "workspace 256-byte" in last_error()
-    with pytest.raises(TypeError, match="oplm_refine takes 31 arguments"):
-        postopt_lm.call("oplm_refine", *args()[:-1])
-    with pytest.raises(TypeError):
-        postopt_lm.check_arity("oplm_refine", args() + [None])
 
 
 def test_cpu_tensors_are_refused_without_the_deeplm_warning():

@@ -1,6 +1,7 @@
 """The temporal refinement without a GPU: the numpy restatement of its specification (tests/temporal_oracle.py) on the analytic scene,
-the header and binding of ``libonepose_temporal.so`` (outside ``cabi.LIBRARIES``), its argument checks (which come before any HIP call,
-so they answer on a machine with no device) and the ``refine`` option of ``SequenceRunner``."""
+the header and binding of ``libonepose_temporal.so`` (what tests/test_cabi_binding.py does not state for every row of
+``cabi.LIBRARIES``), its argument checks (which come before any HIP call, so they answer on a machine with no device) and the ``refine``
+option of ``SequenceRunner``."""
 import ctypes
 import os
 import re
@@ -9,11 +10,10 @@ import numpy as np
 import pytest
 import torch
 
-from onepose_st_amd import cabi, frameloop as fl, hip, temporal
+from onepose_st_amd import frameloop as fl, hip, temporal
 from tests import temporal_oracle as to
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WANT = ("optmp_abi_version", "optmp_last_error", "optmp_pyramid_bytes", "optmp_pyramid", "optmp_track", "optmp_collect", "optmp_inject")
 # the oracle's own maximum error on the pure-shift scene (seed 0, 3 levels, window 15, 60 points): 0.0290 px
 SHIFT_MAX_ERROR = 0.0290
 
@@ -113,13 +113,7 @@ def test_crop_mapping_round_trip():
 
 
 def test_header_and_binding():
-    text = open(os.path.join(REPO, "include", "temporal_refine.h")).read()
-    assert temporal.EXPORTED_SYMBOLS == WANT
-    assert set(re.findall(r"\b(optmp_\w+)\s*\(", text)) == set(WANT)
-    assert temporal.ABI_VERSION == 1 and temporal.load().optmp_abi_version() == 1
-    assert "temporal" not in {e.module for e in cabi.LIBRARIES} and "optmp" not in {e.prefix for e in cabi.LIBRARIES}
-    lib = ctypes.CDLL(temporal.library_path())
-    assert all(hasattr(lib, s) for s in WANT)
+    assert temporal.ABI_VERSION == 1
     assert (temporal.DEGENERATE, temporal.OUT_OF_IMAGE, temporal.FB_FAIL, temporal.BAD_INPUT, temporal.FLAG_MAX_ITERS, temporal.LOST) == \
         (to.DEGENERATE, to.OUT_OF_IMAGE, to.FB_FAIL, to.BAD_INPUT, to.FLAG_MAX_ITERS, to.LOST)
     assert temporal.LOST == temporal.DEGENERATE | temporal.OUT_OF_IMAGE | temporal.FB_FAIL | temporal.BAD_INPUT
@@ -145,8 +139,6 @@ def test_rejected_calls_answer_before_any_launch():
         with pytest.raises(ValueError, match="null pointer"):
             temporal.call(name, *args(name))
         assert last_error() == f"{name}: null pointer"
-        with pytest.raises(TypeError, match=f"{name} takes {len(protos[name].params)} arguments"):
-            temporal.call(name, *args(name)[:-1])
     ptrs = {n: _PTR for c, n in protos["optmp_track"].params if c.endswith("*") and n not in ("guess", "pts_3d", "pose", "K", "count", "stream")}
     good = dict(H=120, W=160, levels=3, cap=8, scale=1.0, window=15, max_iters=30, eps=0.01, min_eig_threshold=1.0, fb_threshold=1.0)
     for change, text in ((dict(window=14), "window: odd"), (dict(window=33), "window: odd"), (dict(levels=7), "levels in [1, 6]"),
@@ -168,8 +160,6 @@ def test_rejected_calls_answer_before_any_launch():
     for change, text in ((dict(n_sources=9), "n_sources outside"), (dict(n_sources=1), "null source table"), (dict(cap_total=3), "cap_own <= cap_total")):
         with pytest.raises(ValueError, match=re.escape(text)):
             temporal.call("optmp_inject", *args("optmp_inject", **{**inj, "cap_own": 4, "cap_total": 8, **change}))
-    hip.call("ophip_timing_every", 1)                                        # another library's call leaves this one's text alone
-    assert "cap_own <= cap_total" in last_error()
 
 
 def test_python_api_refuses_cpu_tensors_and_bad_options():

@@ -3,7 +3,7 @@
 # = the working tree's csrc with the listed files taken from <git rev>; result: onepose_st_amd/lib/variants/libonepose_hip_<name>.so
 # EXTRA="-D..." in the environment adds compiler flags; <git rev> may be "-" with no files (working tree + EXTRA only).
 # (load it with OPHIP_LIB=<path>; `tools/box.sh <name> ab:R:S:variants` runs variants interleaved on one box).  Variants are scratch: git-ignored like every .so.
-# A first <csrc file> of `sfm`, `sfm_tracks`, `sfm_triangulate`, `sfm_fine`, `pnp_device`, `track` or `detect` is a goal, not a file: the variant is then that satellite
+# A first <csrc file> that is the <name> of any `satellite` line of csrc/Makefile is a goal, not a file: the variant is then that satellite
 # library, libonepose_<goal>.so (load it with its OP*_LIB variable, onepose_st_amd/cabi.py LIBRARIES), e.g. the seeded faults of tests/test_gpu_sfm_tracks.py:
 #   EXTRA=-DOPSFT_FAULT_TIE_INITIAL_ORDER tools/build_variant.sh tie - sfm_tracks   -> lib/variants/libonepose_sfm_tracks_tie.so
 set -e
