@@ -1,5 +1,7 @@
-// What the device frame loop's libraries (pnp_device.hip, track_box.hip, detect_affine.hip) must compute alike, written once.  The
-// specification asks for bit-identical behaviour in three places, and this header is the single copy of each:
+// What several satellite libraries must compute alike, written once.  It began as the shared code of the device frame loop
+// (pnp_device.hip, track_box.hip, detect_affine.hip), whose specification asks for bit-identical behaviour in three places; this header
+// is the single copy of each, and other libraries take from it what they would otherwise restate (temporal_refine.hip: clamped_count;
+// sfm_triangulate.hip: mix64):
 //
 //   the sampler        onepose_detect.h defines detection's draws as onepose_pnp_device.h's with the view in place of the frame: mix64, draw3
 //   the crop geometry  the state detection writes is bit-equal to optrk_box_set's (onepose_track.h, crop_geometry): geometry_entry, fits_int32

@@ -2,18 +2,16 @@
 // provided keypoints, and the backbone-feature sampler (loftr_for_sfm/utils/sample_feature_from_featuremap.py:6-80) behind
 // extract_coarse_feature / extract_fine_feature.  Both are launch-bound: a few thousand keypoints, one row of 128 or 256 floats each.
 //
-// Every step is written in the reference's order of operations and rounding, in the keypoints' own dtype (COLMAP's float64 xys and the
-// feature file's float32 keypoints can meet in one pair), with contraction into FMA switched off: the ids and the nearest samples are
-// compared bit for bit.
+// The arithmetic (sfm_sample.h, shared with sfm_fine.hip) is written in the reference's order of operations and rounding, in the
+// keypoints' own dtype (COLMAP's float64 xys and the feature file's float32 keypoints can meet in one pair), with contraction into FMA
+// switched off: the ids and the nearest samples are compared bit for bit.
 #include "tile.h"
 #include "onepose_hip.h"
 #include <math.h>
 #include <stdint.h>
+#include "sfm_sample.h"
 
 namespace {
-
-__device__ __forceinline__ float rint_t(float v) { return rintf(v); }          // torch.round / nearbyint: half to even
-__device__ __forceinline__ double rint_t(double v) { return rint(v); }
 
 // ---- coarse ids of provided matches ------------------------------------------------------------------------------------------------
 struct IdsArgs {
@@ -32,19 +30,12 @@ template <typename T>
 __device__ __forceinline__ void coarse_id(const IdsArgs& p, int img, int k) {
 #pragma clang fp contract(off)
     T* kp = static_cast<T*>(p.kp[img]);
-    T x = kp[2 * k], y = kp[2 * k + 1];
-    const T xmax = (T)p.xmax[img], ymax = (T)p.ymax[img];
-    x = x < T(0) ? T(0) : (x > xmax ? xmax : x);                // torch.clip (NaN stays NaN)
-    y = y < T(0) ? T(0) : (y > ymax ? ymax : y);
+    const T x = sfmsample::clip(kp[2 * k], (T)p.xmax[img]), y = sfmsample::clip(kp[2 * k + 1], (T)p.ymax[img]);
     kp[2 * k] = x;
     kp[2 * k + 1] = y;
-    // scale * scale[b_ids][:, [1, 0]]: x by the w factor, y by the h factor (f32), then the division in the promoted dtype
     const float* s = p.scale[img];
     const float sx = s ? p.cscale * s[1] : p.cscale, sy = s ? p.cscale * s[0] : p.cscale;
-    const T rx = rint_t(x / (T)sx), ry = rint_t(y / (T)sy);
-    const T v = ry * (T)p.wc[img] + rx;
-    long long id = -1;
-    if (v >= T(0) && v < T(9.0e18)) id = (long long)v;                // .long() truncates; NaN and negatives are flagged
+    const long long id = sfmsample::cell_id<T>(x, y, sx, sy, p.wc[img]);
     if (id < 0 || id >= p.L[img]) atomicAdd(p.bad, 1);
     p.ids[img][k] = id;
 }
@@ -70,23 +61,6 @@ struct SampleJobs {
     int n;
 };
 
-// coord_normalization (scale 1): ((k - 0.5 + 0.5) / (extent - 1)) * 2 - 1 in the keypoints' dtype, then .float()
-template <typename T>
-__device__ __forceinline__ float normalise(T k, float extent) {
-#pragma clang fp contract(off)
-    const T den = (T)(extent - 1.0f);
-    T g = k - T(0.5);
-    g = g + T(0.5);
-    g = g / den;
-    g = g * T(2);
-    g = g - T(1);
-    return (float)g;
-}
-
-__device__ __forceinline__ f32x4 row4(const SampleJob& j, int y, int x, int c4) {
-    return *reinterpret_cast<const f32x4*>(j.map + ((size_t)y * j.w + x) * j.C + 4 * c4);
-}
-
 __global__ __launch_bounds__(256) void sfm_sample_kernel(SampleJobs jobs) {
 #pragma clang fp contract(off)
     int g = blockIdx.x * 4 + (threadIdx.x >> 6);                    // one wave per keypoint
@@ -97,38 +71,9 @@ __global__ __launch_bounds__(256) void sfm_sample_kernel(SampleJobs jobs) {
     const SampleJob& j = jobs.job[ji];
     const int k = g;
     if (lane >= j.C / 4) return;
-    float gx, gy;
-    {
-        const float eh = j.scale[0] * (float)j.H, ew = j.scale[1] * (float)j.W;   // imghw = scale * hw_i
-        if (j.kpt_double) {
-            const double* kp = static_cast<const double*>(j.kpts);
-            gx = normalise<double>(kp[2 * k], ew);
-            gy = normalise<double>(kp[2 * k + 1], eh);
-        } else {
-            const float* kp = static_cast<const float*>(j.kpts);
-            gx = normalise<float>(kp[2 * k], ew);
-            gy = normalise<float>(kp[2 * k + 1], eh);
-        }
-    }
-    // grid_sampler_unnormalize, align_corners: ((g + 1) / 2) * (size - 1)
-    const float ix = ((gx + 1.f) / 2.f) * (float)(j.w - 1), iy = ((gy + 1.f) / 2.f) * (float)(j.h - 1);
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    if (j.nearest) {
-        const float rx = rintf(ix), ry = rintf(iy);
-        if (rx >= 0.f && rx <= (float)(j.w - 1) && ry >= 0.f && ry <= (float)(j.h - 1)) o = row4(j, (int)ry, (int)rx, lane);
-    } else if (ix > -1.f && ix < (float)j.w && iy > -1.f && iy < (float)j.h) {
-        // the four corners and weights of PyTorch's bilinear grid_sample, summed nw, ne, sw, se; corners outside the map add nothing
-        const float fx = floorf(ix), fy = floorf(iy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float x1f = fx + 1.f, y1f = fy + 1.f;
-        const float wnw = (x1f - ix) * (y1f - iy), wne = (ix - fx) * (y1f - iy);
-        const float wsw = (x1f - ix) * (iy - fy), wse = (ix - fx) * (iy - fy);
-        const bool xin0 = x0 >= 0, xin1 = x0 + 1 < j.w, yin0 = y0 >= 0, yin1 = y0 + 1 < j.h;
-        if (yin0 && xin0) { const f32x4 v = row4(j, y0, x0, lane); o = o + v * wnw; }
-        if (yin0 && xin1) { const f32x4 v = row4(j, y0, x0 + 1, lane); o = o + v * wne; }
-        if (yin1 && xin0) { const f32x4 v = row4(j, y0 + 1, x0, lane); o = o + v * wsw; }
-        if (yin1 && xin1) { const f32x4 v = row4(j, y0 + 1, x0 + 1, lane); o = o + v * wse; }
-    }
+    const float eh = j.scale[0] * (float)j.H, ew = j.scale[1] * (float)j.W;       // imghw = scale * hw_i
+    const char* kp = static_cast<const char*>(j.kpts) + (size_t)k * (j.kpt_double ? 16 : 8);
+    const f32x4 o = sfmsample::sample_row(j.map, j.h, j.w, j.C, kp, j.kpt_double, eh, ew, j.nearest, lane);
     *reinterpret_cast<f32x4*>(j.out + (size_t)k * j.C + 4 * lane) = o;
 }
 

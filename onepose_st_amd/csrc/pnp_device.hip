@@ -19,6 +19,7 @@
 #include "onepose_pnp_device.h"
 #include "capi_error.h"
 #include "device_loop.h"
+#include "reduce_f64.h"
 
 using capi::bad_arg;
 using capi::blocks_of;
@@ -398,22 +399,9 @@ __global__ __launch_bounds__(kThreads) void select_final_kernel(const Best* part
 }
 
 // ---- refine ------------------------------------------------------------------------------------------------------------------------------
-// sum of one value per thread by the fixed tree; every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // refine_lm's cost on the masked rows of [begin, end): per-thread partials in row order, then the tree
 __device__ __forceinline__ double lm_cost(const double* ps, const double* rows, const unsigned char* mask, int begin, int end, const Intr& I, double* red) {
-    double c = 0.0;
+    double c[1] = {0.0};
     for (int i = begin + threadIdx.x; i < end; i += kThreads) {
         if (!mask[i]) continue;
         const double* x = rows + (size_t)i * kRow;
@@ -424,9 +412,10 @@ __device__ __forceinline__ double lm_cost(const double* ps, const double* rows, 
         const double izc = 1.0 / (front ? zc : 1.0);
         const double xn = xc * izc, yn = yc * izc;
         const double du = I.fx * xn + I.sk * yn + I.cx - x[3], dv = I.fy * yn + I.cy - x[4];
-        c += front ? du * du + dv * dv : 1e12;
+        c[0] += front ? du * du + dv * dv : 1e12;
     }
-    return block_sum(c, red);
+    red64::block_sums<kThreads>(c, 1, red);
+    return c[0];
 }
 
 __global__ __launch_bounds__(kThreads) void refine_kernel(const double* rows, const int* ranges, const double* K, int k_shared, const double* hyps,

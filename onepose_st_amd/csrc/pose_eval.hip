@@ -12,6 +12,7 @@
 // No atomics and no MFMA (its rounding is not the written order) anywhere in this file.
 #include "capi_error.h"
 #include "onepose_pose_eval.h"
+#include "reduce_f64.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -23,7 +24,7 @@ using capi::blocks_of;
 
 constexpr int kThreads = OPEVL_BLOCK;
 constexpr int kMaxGridY = 65535;
-static_assert(kThreads == 256, "the tree below starts at stride 128");
+static_assert(kThreads == 256, "the header fixes the tree: it starts at stride 128");
 
 struct Pose {
     double r[3][3], t[3];
@@ -40,16 +41,6 @@ __device__ __forceinline__ Pose load_pose(const double* __restrict__ p) {
 
 __device__ __forceinline__ void transform(const Pose& p, double x0, double x1, double x2, double out[3]) {
     for (int k = 0; k < 3; ++k) out[k] = ((p.r[k][0] * x0 + p.r[k][1] * x1) + p.r[k][2] * x2) + p.t[k];
-}
-
-// the block's tree (header, "every mean"): s must hold one term per lane; returns s[0] to lane 0 (other lanes: unspecified)
-__device__ __forceinline__ double block_sum(double* s, int tid) {
-    __syncthreads();
-    for (int stride = kThreads / 2; stride >= 1; stride >>= 1) {
-        if (tid < stride) s[tid] = s[tid] + s[tid + stride];
-        __syncthreads();
-    }
-    return s[0];
 }
 
 __global__ __launch_bounds__(kThreads) void errors_kernel(const double* __restrict__ pred, int pred_stride, const double* __restrict__ gt,
@@ -86,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void add_kernel(const float* __restrict__
     const int tid = threadIdx.x, f = frame0 + blockIdx.y;
     if (flags != nullptr && flags[f]) return;               // uniform over the workgroup
     const int v = blockIdx.x * kThreads + tid;
-    double term = 0.0;
+    double term[1] = {0.0};                                 // the block's tree (header, "every mean") takes an array
     if (v < V) {
         const Pose P = load_pose(pred + (long long)f * pred_stride), G = load_pose(gt + (long long)f * gt_stride);
         const double x0 = verts[3 * v], x1 = verts[3 * v + 1], x2 = verts[3 * v + 2];
@@ -94,11 +85,10 @@ __global__ __launch_bounds__(kThreads) void add_kernel(const float* __restrict__
         transform(P, x0, x1, x2, a);
         transform(G, x0, x1, x2, b);
         const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-        term = sqrt((dx * dx + dy * dy) + dz * dz);
+        term[0] = sqrt((dx * dx + dy * dy) + dz * dz);
     }
-    s[tid] = term;
-    const double sum = block_sum(s, tid);
-    if (tid == 0) partials[(long long)f * nblk + blockIdx.x] = sum;
+    red64::block_sums<kThreads>(term, 1, s);
+    if (tid == 0) partials[(long long)f * nblk + blockIdx.x] = term[0];
 }
 
 __global__ __launch_bounds__(kThreads) void proj2d_kernel(const float* __restrict__ verts, int V, const double* __restrict__ pred,
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void proj2d_kernel(const float* __restric
     const int tid = threadIdx.x, f = frame0 + blockIdx.y;
     if (flags != nullptr && flags[f]) return;
     const int v = blockIdx.x * kThreads + tid;
-    double term = 0.0;
+    double term[1] = {0.0};                                 // the block's tree (header, "every mean") takes an array
     if (v < V) {
         const Pose P = load_pose(pred + (long long)f * pred_stride), G = load_pose(gt + (long long)f * gt_stride);
         const double* k = K + (k_shared ? 0 : (long long)f * 9);
@@ -122,11 +112,10 @@ __global__ __launch_bounds__(kThreads) void proj2d_kernel(const float* __restric
             ub[r] = (k[3 * r] * b[0] + k[3 * r + 1] * b[1]) + k[3 * r + 2] * b[2];
         }
         const double dx = ua[0] / ua[2] - ub[0] / ub[2], dy = ua[1] / ua[2] - ub[1] / ub[2];
-        term = sqrt(dx * dx + dy * dy);
+        term[0] = sqrt(dx * dx + dy * dy);
     }
-    s[tid] = term;
-    const double sum = block_sum(s, tid);
-    if (tid == 0) partials[(long long)f * nblk + blockIdx.x] = sum;
+    red64::block_sums<kThreads>(term, 1, s);
+    if (tid == 0) partials[(long long)f * nblk + blockIdx.x] = term[0];
 }
 
 __global__ __launch_bounds__(kThreads) void adds_kernel(const float* __restrict__ verts, int V, const double* __restrict__ pred, int pred_stride,
@@ -170,9 +159,9 @@ __global__ __launch_bounds__(kThreads) void adds_kernel(const float* __restrict_
         }
         __syncthreads();                                    // the tile is used up before the next one is staged
     }
-    sx[tid] = j < V ? sqrt(m) : 0.0;
-    const double sum = block_sum(sx, tid);
-    if (tid == 0) partials[(long long)f * nblk + blk] = sum;
+    double term[1] = {j < V ? sqrt(m) : 0.0};
+    red64::block_sums<kThreads>(term, 1, sx);
+    if (tid == 0) partials[(long long)f * nblk + blk] = term[0];
 }
 
 __global__ __launch_bounds__(kThreads) void finish_kernel(const double* __restrict__ partials, const int* __restrict__ flags, int frames, int nblk,

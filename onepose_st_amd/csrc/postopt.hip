@@ -13,6 +13,7 @@
 #include "tile.h"
 #include "onepose_hip.h"
 #include "postopt_fold.h"
+#include "reduce_f64.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -48,11 +49,6 @@ struct StepArgs {
     int P, max_steps;
 };
 
-__device__ __forceinline__ double wave_sum(double x) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);   // commutative pairs: every lane ends with the same sum
-    return x;
-}
-
 __global__ __launch_bounds__(kStepThreads) void postopt_step_kernel(StepArgs a, int it) {
 #pragma clang fp contract(off)
     __shared__ double red[kStepThreads];
@@ -80,8 +76,8 @@ __global__ __launch_bounds__(kStepThreads) void postopt_step_kernel(StepArgs a, 
                 a.resid[2 * r + 1] = ry;
             }
         }
-        g = wave_sum(g);
-        l = wave_sum(l);
+        g = red64::wave_sum(g);
+        l = red64::wave_sum(l);
         lsum += l;
         if (lane == 0) {
             // torch.optim.Adam, single tensor: exp_avg.lerp_(g, 1 - b1), exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2),

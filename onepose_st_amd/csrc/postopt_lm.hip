@@ -10,6 +10,7 @@
 // the per-track costs in index order into the two totals.
 #include "capi_error.h"
 #include "postopt_fold.h"
+#include "reduce_f64.h"
 #include "onepose_postopt_lm.h"
 #include <stdint.h>
 
@@ -18,6 +19,8 @@ namespace {
 using capi::bad_arg;
 using capi::fail;
 using capi::g_error;
+using red64::uniform;
+using red64::wave_sum;
 
 constexpr int kThreads = 256;                // 4 waves, one track per wave at a time
 constexpr int kMaxBlocks = 2048;             // wave w of the grid owns tracks w, w + 4 * grid, ... (the step kernel's rule)
@@ -35,18 +38,6 @@ struct LmArgs {
     long long L;
     int P, max_iters;
 };
-
-__device__ __forceinline__ double wave_sum(double x) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);   // commutative pairs: every lane ends with the same sum
-    return x;
-}
-
-// the value every lane holds, as a scalar: makes the loop's branches provably wave-uniform
-__device__ __forceinline__ double uniform(double x) {
-    const long long b = __double_as_longlong(x);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 struct Sums {
     double c, g, H;

@@ -4,6 +4,7 @@
 // Reference: utils/position_encoding.py:37-42 + OnePosePlusModel.py:135-140 (a1),
 // utils/normalize.py:17-28 (a2), utils/position_encoding.py:54-79 (a3).
 #include "tile.h"
+#include "crop_pixel.h"
 
 namespace {
 
@@ -232,25 +233,14 @@ __global__ __launch_bounds__(256) void transpose_c128_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------
 // query crop: bbox [x0, y0, x1, y1) of a full-resolution grayscale frame -> S x S float image in [0, 1]
 // (row f-2; local_feature_2D_detector.py:164-190 crop_img_by_bbox = two cv2.warpAffine calls: an integer-shift crop to the
-// box, then an isotropic resize by S / box_width about the crop centre with zero border).  One bilinear pass here.
+// box, then an isotropic resize by S / box_width about the crop centre with zero border).  One bilinear pass: crop_pixel.h, shared
+// with the device-box form of track_crop.hip.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void crop_resize_kernel(const unsigned char* __restrict__ img, int H, int W, int x0, int y0, int wb, int hb,
                                                           int S, float* __restrict__ out) {
     const int X = blockIdx.x * 32 + (threadIdx.x & 31), Y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (X >= S || Y >= S) return;
-    const float inv = (float)wb / (float)S;                    // 1 / scale of the second warp
-    const float u = ((float)X - 0.5f * (float)S) * inv + 0.5f * (float)wb;
-    const float v = ((float)Y - 0.5f * (float)S) * inv + 0.5f * (float)hb;
-    const float fu = floorf(u), fv = floorf(v);
-    const int i0 = (int)fu, j0 = (int)fv;
-    const float a = u - fu, b = v - fv;
-    auto px = [&](int i, int j) -> float {                     // the box crop with zeros outside it and outside the frame
-        if (i < 0 || i >= wb || j < 0 || j >= hb) return 0.f;
-        const int x = x0 + i, y = y0 + j;
-        return (x >= 0 && x < W && y >= 0 && y < H) ? (float)img[(size_t)y * W + x] : 0.f;
-    };
-    const float val = (1.f - b) * ((1.f - a) * px(i0, j0) + a * px(i0 + 1, j0)) + b * ((1.f - a) * px(i0, j0 + 1) + a * px(i0 + 1, j0 + 1));
-    out[(size_t)Y * S + X] = fminf(fmaxf(rintf(val), 0.f), 255.f) / 255.0f;      // cv2 writes uint8; astype(float32) / 255 is a true division
+    out[(size_t)Y * S + X] = crop_pixel(img, H, W, x0, y0, wb, hb, S, X, Y);
 }
 
 }  // namespace

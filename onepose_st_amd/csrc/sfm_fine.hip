@@ -8,14 +8,14 @@
 //   sample_rows  ophip_sample_features per row: the four feature tables of a bucket of rows in one launch, one wave per row and table,
 //                16-byte loads of the map rows, f32 rows out
 //
-// Every step is written in the order of operations and rounding of csrc/loftr_sfm.hip (which restates the reference's), in the
-// keypoints' own dtype, with contraction into FMA switched off (the pragma below and -ffp-contract=off): the results are compared
-// bit for bit with the per-pair kernels.  Both kernels are memory- and launch-bound.
+// The ids and the samples come from the functions of sfm_sample.h, which the per-pair kernels call too, so the two agree bit for bit
+// by construction.  Both kernels are memory- and launch-bound.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "onepose_sfm_fine.h"
 #include "capi_error.h"
+#include "sfm_sample.h"
 
 using capi::bad_arg;
 using capi::fail;
@@ -23,10 +23,7 @@ using capi::g_error;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float rint_t(float v) { return rintf(v); }          // torch.round / nearbyint: half to even
-__device__ __forceinline__ double rint_t(double v) { return rint(v); }
+using sfmsample::f32x4;
 
 // ---- cell ids of the rows' keypoints -------------------------------------------------------------------------------------------------
 struct IdsArgs {
@@ -52,16 +49,11 @@ __device__ __forceinline__ void row_id(const IdsArgs& p, int side, long long r) 
     long long id = -1, L = 0;
     if (img >= 0 && img < p.I) {
         const int H = p.hw[2 * img], W = p.hw[2 * img + 1];
-        const T xmax = (T)(W - 2), ymax = (T)(H - 2);
-        x = x < T(0) ? T(0) : (x > xmax ? xmax : x);                // torch.clip (NaN stays NaN)
-        y = y < T(0) ? T(0) : (y > ymax ? ymax : y);
-        // scale * scale[b_ids][:, [1, 0]]: x by the w factor, y by the h factor (f32), then the division in the promoted dtype
+        x = sfmsample::clip(x, (T)(W - 2));
+        y = sfmsample::clip(y, (T)(H - 2));
         const float* s = p.scale + 2 * img;
-        const float sx = p.cscale * s[1], sy = p.cscale * s[0];
-        const T rx = rint_t(x / (T)sx), ry = rint_t(y / (T)sy);
         const int wc = W / 8;
-        const T v = ry * (T)wc + rx;
-        if (v >= T(0) && v < T(9.0e18)) id = (long long)v;          // .long() truncates; NaN and negatives are flagged
+        id = sfmsample::cell_id<T>(x, y, p.cscale * s[1], p.cscale * s[0], wc);
         L = (long long)(H / 8) * wc;
     }
     out[2 * r] = x;
@@ -108,23 +100,6 @@ struct SampleArgs {
     int n, I;
 };
 
-// coord_normalization (scale 1): ((k - 0.5 + 0.5) / (extent - 1)) * 2 - 1 in the keypoints' dtype, then .float()
-template <typename T>
-__device__ __forceinline__ float normalise(T k, float extent) {
-#pragma clang fp contract(off)
-    const T den = (T)(extent - 1.0f);
-    T g = k - T(0.5);
-    g = g + T(0.5);
-    g = g / den;
-    g = g * T(2);
-    g = g - T(1);
-    return (float)g;
-}
-
-__device__ __forceinline__ f32x4 row4(const float* map, int w, int C, int y, int x, int c4) {
-    return *reinterpret_cast<const f32x4*>(map + ((size_t)y * w + x) * C + 4 * c4);
-}
-
 __global__ __launch_bounds__(256) void sample_rows_kernel(SampleArgs a) {
 #pragma clang fp contract(off)
     const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);      // one wave per (table, row)
@@ -147,38 +122,10 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(SampleArgs a) {
     }
     const int h = nearest ? s.H / 8 : s.H / 2, w = nearest ? s.W / 8 : s.W / 2;
     const float* map = nearest ? s.coarse + (size_t)b * s.coarse_bs : s.fine + (size_t)b * s.fine_bs;
-    float gx, gy;
-    {
-        const float* sc = a.scale + 2 * img;
-        const float eh = sc[0] * (float)s.H, ew = sc[1] * (float)s.W;       // imghw = scale * hw_i
-        if (s.kpt_double) {
-            const double* kp = static_cast<const double*>(s.kpts);
-            gx = normalise<double>(kp[2 * r], ew);
-            gy = normalise<double>(kp[2 * r + 1], eh);
-        } else {
-            const float* kp = static_cast<const float*>(s.kpts);
-            gx = normalise<float>(kp[2 * r], ew);
-            gy = normalise<float>(kp[2 * r + 1], eh);
-        }
-    }
-    // grid_sampler_unnormalize, align_corners: ((g + 1) / 2) * (size - 1)
-    const float ix = ((gx + 1.f) / 2.f) * (float)(w - 1), iy = ((gy + 1.f) / 2.f) * (float)(h - 1);
-    if (nearest) {
-        const float rx = rintf(ix), ry = rintf(iy);
-        if (rx >= 0.f && rx <= (float)(w - 1) && ry >= 0.f && ry <= (float)(h - 1)) o = row4(map, w, C, (int)ry, (int)rx, lane);
-    } else if (ix > -1.f && ix < (float)w && iy > -1.f && iy < (float)h) {
-        // the four corners and weights of PyTorch's bilinear grid_sample, summed nw, ne, sw, se; corners outside the map add nothing
-        const float fx = floorf(ix), fy = floorf(iy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float x1f = fx + 1.f, y1f = fy + 1.f;
-        const float wnw = (x1f - ix) * (y1f - iy), wne = (ix - fx) * (y1f - iy);
-        const float wsw = (x1f - ix) * (iy - fy), wse = (ix - fx) * (iy - fy);
-        const bool xin0 = x0 >= 0, xin1 = x0 + 1 < w, yin0 = y0 >= 0, yin1 = y0 + 1 < h;
-        if (yin0 && xin0) { const f32x4 v = row4(map, w, C, y0, x0, lane); o = o + v * wnw; }
-        if (yin0 && xin1) { const f32x4 v = row4(map, w, C, y0, x0 + 1, lane); o = o + v * wne; }
-        if (yin1 && xin0) { const f32x4 v = row4(map, w, C, y0 + 1, x0, lane); o = o + v * wsw; }
-        if (yin1 && xin1) { const f32x4 v = row4(map, w, C, y0 + 1, x0 + 1, lane); o = o + v * wse; }
-    }
+    const float* sc = a.scale + 2 * img;
+    const float eh = sc[0] * (float)s.H, ew = sc[1] * (float)s.W;           // imghw = scale * hw_i
+    const char* kp = static_cast<const char*>(s.kpts) + (size_t)r * (s.kpt_double ? 16 : 8);
+    o = sfmsample::sample_row(map, h, w, C, kp, s.kpt_double, eh, ew, nearest, lane);
     *reinterpret_cast<f32x4*>(out) = o;
 }
 

@@ -18,11 +18,14 @@
 #include <stdint.h>
 #include "onepose_sfm_triangulate.h"
 #include "capi_error.h"
+#include "device_loop.h"
+#include "reduce_f64.h"
 
 using capi::bad_arg;
 using capi::blocks_of;
 using capi::fail;
 using capi::g_error;
+using red64::block_sums;
 
 namespace {
 
@@ -146,11 +149,9 @@ struct GlobalElems {
     __device__ __forceinline__ double* unit(int k) const { return w + 4 * k; }
 };
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long seed, unsigned long long n) {   // the n-th output, n = 0, 1, ...
-    unsigned long long z = seed + (n + 1ULL) * 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
+// the n-th output of splitmix64 from `seed`, n = 0, 1, ...
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long seed, unsigned long long n) {
+    return devloop::mix64(seed + (n + 1ULL) * 0x9E3779B97F4A7C15ULL);
 }
 
 // q = P (X, 1): u = q0 / q2, v = q1 / q2, depth q2 (the last row of K is (0, 0, 1))
@@ -180,22 +181,6 @@ __device__ __forceinline__ void solve_sym3(const double* a, const double* b, dou
     x[0] = ((c00 * b[0] + c01 * b[1]) + c02 * b[2]) / det;
     x[1] = ((c01 * b[0] + c11 * b[1]) + c12 * b[2]) / det;
     x[2] = ((c02 * b[0] + c12 * b[1]) + c22 * b[2]) / det;
-}
-
-// the sums of v[0 .. n) over the workgroup, to every thread: a fixed tree over the threads
-template <int NT>
-__device__ __forceinline__ void block_sums(double* v, int n, double* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    for (int k = 0; k < n; ++k) red[k * NT + tid] = v[k];
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int k = 0; k < n; ++k) red[k * NT + tid] = red[k * NT + tid] + red[k * NT + tid + s];
-        __syncthreads();
-    }
-    for (int k = 0; k < n; ++k) v[k] = red[k * NT];
-    __syncthreads();
 }
 
 template <int NT>

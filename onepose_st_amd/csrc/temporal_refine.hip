@@ -14,6 +14,8 @@
 // inject_source_    position of a row never depends on timing.  inject is one launch for the frame's own rows and one per source, each
 // kernel            starting at the count the launch before it left.  No atomics anywhere in this file.
 #include "capi_error.h"
+#include "device_loop.h"
+#include "reduce_f64.h"
 #include "onepose_temporal.h"
 #include <math.h>
 #include <stdint.h>
@@ -26,6 +28,9 @@ using capi::bad_arg;
 using capi::blocks_of;
 using capi::fail;
 using capi::g_error;
+using devloop::clamped_count;
+using red64::uniform;
+using red64::wave_sum;
 
 constexpr int kThreads = 256;
 constexpr int kTileW = 64, kTileH = 16;                             // outputs of one pyr_down workgroup
@@ -102,23 +107,6 @@ struct TrackArgs {
     double scale, eps2, min_eig, fb_threshold;
     int cap, H, W, levels, window, max_iters;
 };
-
-__device__ __forceinline__ int clamped_count(const int* count, int cap) {
-    const int n = count ? *count : cap;
-    return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);   // commutative pairs: every lane ends with the same sum
-    return x;
-}
-
-// the value every lane holds, as a scalar: makes the branches on it provably wave-uniform
-__device__ __forceinline__ double uniform(double x) {
-    const long long b = __double_as_longlong(x);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
