@@ -25,12 +25,10 @@ Nothing is synchronised or read back: every launch is sized by the capacity.
 """
 from __future__ import annotations
 
-import contextlib
-
 import numpy as np
 import torch
 
-from . import cabi, hip
+from . import cabi, devargs, hip
 from .pnp_device import check_ransac_options
 from .track_device import MAX_CROP, TrackState, check_crop_size, check_K
 
@@ -54,39 +52,25 @@ class _Inputs:
     def __init__(self, mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size, count):
         tensors = [("mkpts0", mkpts0), ("mkpts1", mkpts1), ("b_ids", b_ids)]
         tensors += [(k, v) for k, v in (("view_hw", view_hw), ("K", K), ("count", count)) if isinstance(v, torch.Tensor)]
-        for name, t in tensors:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{name}: expected a tensor")
-        if mkpts0.dim() != 2 or mkpts0.shape[1] != 2 or tuple(mkpts1.shape) != tuple(mkpts0.shape):
-            raise ValueError("mkpts0 and mkpts1: [cap, 2], the same length")
-        if mkpts0.dtype != torch.float32 or mkpts1.dtype != torch.float32:
-            raise ValueError("mkpts0 and mkpts1: float32")
-        n = mkpts0.shape[0]
-        if n > MAX_ROWS:
-            raise ValueError(f"at most {MAX_ROWS} rows")
+        hip.need_tensors(tensors)
+        mkpts0, mkpts1 = devargs.point_tables("mkpts0", mkpts0, 2, "mkpts1", mkpts1, 2, max_rows=MAX_ROWS)
+        n, dev = mkpts0.shape[0], mkpts0.device
         if b_ids.dtype != torch.int64 or tuple(b_ids.shape) != (n,):
             raise ValueError(f"b_ids: int64 [{n}]")
         if not isinstance(view_hw, torch.Tensor):
             view_hw = torch.as_tensor(np.asarray(view_hw, dtype=np.int32).reshape(-1, 2))
-            view_hw = view_hw.to(mkpts0.device)
+            view_hw = view_hw.to(dev)
         if view_hw.dtype != torch.int32 or view_hw.dim() != 2 or view_hw.shape[1] != 2 or not 1 <= view_hw.shape[0] <= MAX_VIEWS:
             raise ValueError(f"view_hw: int32 [V, 2] (H, W of every view), V in [1, {MAX_VIEWS}]")
         H, W = (int(v) for v in query_hw)
         if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
             raise ValueError(f"query_hw: (H, W) in [1, {MAX_SIDE}]")
         S = check_crop_size(crop_size)
-        K = check_K(K) if isinstance(K, torch.Tensor) else check_K(K).to(mkpts0.device)
-        if isinstance(count, torch.Tensor) and (count.dtype != torch.int32 or count.numel() != 1):
-            raise ValueError("count: one int32 on the device")
-        if not all(t.is_cuda for t in (mkpts0, mkpts1, b_ids, view_hw, K)) or (isinstance(count, torch.Tensor) and not count.is_cuda):
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
-        dev = mkpts0.device
-        if count is not None and not isinstance(count, torch.Tensor):
-            count = torch.full((1,), int(count), dtype=torch.int32, device=dev)
-        if n == 0:                                          # the library wants a table of at least one row; the count says it is unused
-            mkpts0 = mkpts1 = torch.zeros(1, 2, dtype=torch.float32, device=dev)
-            b_ids, count = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
-        self.mk0, self.mk1, self.b_ids, self.count = mkpts0.contiguous(), mkpts1.contiguous(), b_ids.contiguous(), count
+        K = check_K(K) if isinstance(K, torch.Tensor) else check_K(K).to(dev)
+        count = devargs.count_arg(count, dev)
+        hip.on_device(t for t in (mkpts0, mkpts1, b_ids, view_hw, K, count) if t is not None)
+        self.mk0, self.mk1, self.count, b_ids = devargs.at_least_one_row(mkpts0, mkpts1, count, b_ids)
+        self.b_ids = b_ids.contiguous()
         self.view_hw, self.K = view_hw.contiguous(), K
         self.cap, self.V, self.H, self.W, self.S, self.dev = self.mk0.shape[0], int(view_hw.shape[0]), H, W, S, dev
 
@@ -105,18 +89,11 @@ class DeviceDetection:
     def to_host(self):
         """``({view: {"inliers", "bbox"}}, winner)``: ``match_worker``'s dict (``inliers``: uint8 ``[n, 1]`` over the view's rows, or an
         empty array where the view votes the centre box) and the winning view.  The one read-back."""
-        V, cap = self.boxes.shape[0], self.inlier_mask.shape[0]
-        packed = torch.cat([self.boxes.reshape(-1).view(torch.uint8), self.status.view(torch.uint8), self.ranges.reshape(-1).view(torch.uint8),
-                            self.winner.view(torch.uint8), self.inlier_mask]).cpu().numpy()
-        o = 0
-        boxes = packed[o:o + 16 * V].view(np.int32).reshape(V, 4); o += 16 * V
-        status = packed[o:o + 4 * V].view(np.int32); o += 4 * V
-        ranges = packed[o:o + 8 * V].view(np.int32).reshape(V, 2); o += 8 * V
-        winner = int(packed[o:o + 4].view(np.int32)[0]); o += 4
-        mask = packed[o:o + cap]
-        self.status_host = status.copy()
+        fields = (self.boxes, self.status, self.ranges, self.winner, self.inlier_mask)
+        (boxes, status, ranges, winner, mask), _ = devargs.unpack(devargs.pack(fields).cpu().numpy(), devargs.packed_layout(fields))
+        self.status_host, winner = status.copy(), int(winner[0])
         votes = {}
-        for v in range(V):
+        for v in range(boxes.shape[0]):
             b, e = int(ranges[v, 0]), int(ranges[v, 1])
             inl = np.empty((0)) if int(status[v]) & STATUS_NO_MODEL else mask[b:e].reshape(-1, 1).copy()
             votes[v] = {"inliers": inl, "bbox": boxes[v].copy()}
@@ -134,7 +111,7 @@ def vote(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size: int = 512, coun
     V, cap, dev = a.V, a.cap, a.dev
     nbytes = load().opdet_workspace_bytes(cap, V, int(trials))
     P = hip.ptr
-    with torch.cuda.device(dev), (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+    with hip.enqueue_on(dev, stream):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         boxes = torch.empty(V, 4, dtype=torch.int32, device=dev)
         n_in, status = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev)

@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import hip
+from . import devargs, hip
 from .pnp import ransac_PnP
 
 MIN_INLIERS = 20          # inference.py:152
@@ -207,9 +207,8 @@ class SequenceRunner:
             n = int(mk2d.shape[0])
             mask = np.zeros(max(n, 1), np.uint8)
             mask[np.asarray(rec["inliers"], np.int64)] = 1
-            if n == 0:                                  # the library wants a table of at least one row; the count says it is unused
-                mk2d, mk3d = torch.zeros(1, 2, dtype=torch.float32, device=dev), torch.zeros(1, 3, dtype=torch.float32, device=dev)
-            entries.append({"pts_2d": mk2d, "pts_3d": mk3d, "count": torch.full((1,), n, dtype=torch.int32, device=dev), "mask": up(mask, np.uint8),
+            mk2d, mk3d, count, _ = devargs.at_least_one_row(mk2d, mk3d, devargs.count_arg(n, dev))
+            entries.append({"pts_2d": mk2d, "pts_3d": mk3d, "count": count, "mask": up(mask, np.uint8),
                             "K_crop": up(rec["K_crop"], np.float64), "trans": up(rec["trans"], np.float64), "pose": up(rec["pose"], np.float64)})
         self._kept = None
         kw = dict(scale=self.scale, pnp_reprojection_error=self.reproj)

@@ -7,6 +7,7 @@ the C ABI with raw device pointers.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -59,6 +60,7 @@ EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version                                      # what the FrameDesc / FrameLayout mirrors above are written for
 # COARSE_PLANES_READY is or-ed into ophip_coarse_match's nsplit
 SAMPLE_MAX_JOBS, COARSE_PLANES_READY = map(_BINDING.constant, ("SAMPLE_MAX_JOBS", "COARSE_PLANES_READY"))
+NO_CPU_FALLBACK = "the HIP path needs device tensors (no CPU fallback)"     # what every device-loop module says of a CPU tensor
 
 
 def ptr(t: torch.Tensor | None, dtype=torch.float32):
@@ -66,7 +68,7 @@ def ptr(t: torch.Tensor | None, dtype=torch.float32):
     if t is None:
         return None
     if not t.is_cuda:
-        raise HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        raise HipLibraryError(NO_CPU_FALLBACK)
     if dtype is not None and t.dtype != dtype:
         raise TypeError(f"expected {dtype}, got {t.dtype}")
     return ctypes.c_void_p(t.data_ptr())
@@ -91,14 +93,31 @@ def seed_arg(seed):
     return ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))
 
 
-def need_device(named) -> None:
-    """``named``: (name, value) pairs.  Every value is a tensor, and then every one of them lies on the device."""
+@contextlib.contextmanager
+def enqueue_on(dev, stream=None):
+    """Where a device-loop call allocates and enqueues: the device ``dev`` current and, given one, ``stream`` (a ``torch.cuda.Stream``)"""
+    with torch.cuda.device(dev), torch.cuda.stream(stream):         # torch.cuda.stream(None) changes nothing
+        yield
+
+
+def need_tensors(named) -> None:
+    """``named``: (name, value) pairs.  Every value is a tensor."""
     for name, t in named:
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name}: expected a tensor")
-    for name, t in named:
-        if not t.is_cuda:
-            raise HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+
+
+def on_device(tensors) -> None:
+    """Every one of ``tensors`` lies on the device."""
+    if not all(t.is_cuda for t in tensors):
+        raise HipLibraryError(NO_CPU_FALLBACK)
+
+
+def need_device(named) -> None:
+    """:func:`need_tensors`, and then every one of them lies on the device."""
+    named = list(named)
+    need_tensors(named)
+    on_device(t for _, t in named)
 
 
 def exclusive(counts: torch.Tensor) -> torch.Tensor:

@@ -31,13 +31,12 @@ Nothing is synchronised and the match count is never read on the host: every lau
 """
 from __future__ import annotations
 
-import contextlib
 import math
 
 import numpy as np
 import torch
 
-from . import cabi, hip
+from . import cabi, devargs, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
@@ -60,49 +59,26 @@ class _Inputs:
     """The checked device tensors of one call"""
 
     def __init__(self, K, pts_2d, pts_3d, count, b_ids, frames):
-        named = [("pts_2d", pts_2d), ("pts_3d", pts_3d)] + [(k, v) for k, v in (("K", K), ("count", count), ("b_ids", b_ids)) if isinstance(v, torch.Tensor)]
-        for name, t in named:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{name}: expected a tensor")
-        if not all(t.is_cuda for _, t in named):
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        hip.need_device([("pts_2d", pts_2d), ("pts_3d", pts_3d)] + [(k, v) for k, v in (("K", K), ("count", count), ("b_ids", b_ids))
+                                                                    if isinstance(v, torch.Tensor)])
         dev = pts_2d.device
-        if pts_2d.dim() != 2 or pts_2d.shape[1] != 2 or pts_3d.dim() != 2 or pts_3d.shape[1] != 3 or pts_2d.shape[0] != pts_3d.shape[0]:
-            raise ValueError("pts_2d [cap, 2] and pts_3d [cap, 3] must have the same length")
-        if pts_2d.dtype != torch.float32 or pts_3d.dtype != torch.float32:
-            raise ValueError("pts_2d and pts_3d: float32")
+        pts_2d, pts_3d = devargs.point_tables("pts_2d", pts_2d, 2, "pts_3d", pts_3d, 3)
         self.frames = int(frames)
         if not 1 <= self.frames <= MAX_FRAMES:
             raise ValueError(f"frames: an integer in [1, {MAX_FRAMES}]")
         n = pts_2d.shape[0]
         if n > MAX_ROWS:
             raise ValueError(f"at most {MAX_ROWS} rows")
-        if n == 0:                                          # the library wants a table of at least one row; the count says it is unused
-            pts_2d, pts_3d = torch.zeros(1, 2, dtype=torch.float32, device=dev), torch.zeros(1, 3, dtype=torch.float32, device=dev)
-            b_ids = None if b_ids is None else torch.zeros(1, dtype=torch.int64, device=dev)
-            count = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.cap = pts_2d.shape[0]
-        self.pts_2d, self.pts_3d = pts_2d.contiguous(), pts_3d.contiguous()
-        if count is None:
-            count = torch.full((1,), n, dtype=torch.int32, device=dev)
-        elif not isinstance(count, torch.Tensor):
-            count = torch.full((1,), int(count), dtype=torch.int32, device=dev)
-        if count.dtype != torch.int32 or count.numel() != 1:
-            raise ValueError("count: one int32 on the device")
-        self.count = count
+        self.pts_2d, self.pts_3d, count, b_ids = devargs.at_least_one_row(pts_2d, pts_3d, count, b_ids)
+        self.cap = self.pts_2d.shape[0]
+        self.count = devargs.count_arg(count, dev, default=n)
         if b_ids is None:
             if self.frames != 1:
                 raise ValueError("frames > 1 needs b_ids")
         elif b_ids.dtype != torch.int64 or tuple(b_ids.shape) != (self.cap,):
             raise ValueError(f"b_ids: int64 [{self.cap}]")
         self.b_ids = None if b_ids is None else b_ids.contiguous()
-        if not isinstance(K, torch.Tensor):
-            K = torch.as_tensor(np.asarray(K, dtype=np.float64), device=dev)
-        K = K.to(torch.float64).reshape(-1, 9).contiguous()
-        if K.shape[0] not in (1, self.frames):
-            raise ValueError(f"K: [3, 3] shared, or [{self.frames}, 3, 3]")
-        self.K, self.k_shared = K, int(K.shape[0] == 1)
-        self.dev = dev
+        (self.K, self.k_shared), self.dev = devargs.k_table(K, self.frames, dev), dev
 
 
 def check_ransac_options(reproj_name, reproj, confidence, trials, max_trials):
@@ -138,21 +114,23 @@ class DevicePoses:
     def pack(self, extra=()) -> torch.Tensor:
         """One uint8 device tensor for one read-back: pose, status, ranges, the inlier mask, then every 1-D uint8 device tensor of
         ``extra`` (what a caller wants read with the pose); :meth:`unpack` reads it on the host"""
-        return torch.cat([self.pose.reshape(-1).view(torch.uint8), self.status.view(torch.uint8), self.ranges.reshape(-1).view(torch.uint8),
-                          self.inlier_mask, *extra])
+        return devargs.pack((*self._packed(), *extra))
+
+    def _packed(self):
+        return self.pose, self.status, self.ranges, self.inlier_mask
+
+    @property
+    def packed_bytes(self) -> int:
+        """The length of :meth:`pack` without extras"""
+        return devargs.packed_bytes(self._packed())
 
     def unpack(self, packed, extra_sizes=()):
         """:meth:`to_host`'s result from the host bytes of :meth:`pack` (a uint8 numpy array); with ``extra_sizes`` a pair of that and the
         byte arrays of the extras"""
-        F, cap = self.pose.shape[0], self.inlier_mask.shape[0]
-        o = 0
-        pose = packed[o:o + 96 * F].view(np.float64).reshape(F, 3, 4); o += 96 * F
-        status = packed[o:o + 4 * F].view(np.int32); o += 4 * F
-        ranges = packed[o:o + 8 * F].view(np.int32).reshape(F, 2); o += 8 * F
-        mask = packed[o:o + cap]; o += cap
+        (pose, status, ranges, mask, *_), o = devargs.unpack(packed, devargs.packed_layout(self._packed()))
         self.status_host = status.copy()                    # the status of every frame, read with the rest
         out = []
-        for f in range(F):
+        for f in range(pose.shape[0]):
             b, e = int(ranges[f, 0]), int(ranges[f, 1])
             ok = not (int(status[f]) & STATUS_NO_POSE)
             p = pose[f].copy()
@@ -184,8 +162,7 @@ def ransac_pnp(K, pts_2d, pts_3d, *, count=None, b_ids=None, frames=1, scale=1, 
     nbytes = load().oppnpd_workspace_bytes(cap, F, int(trials))
     if nbytes == 0:
         raise ValueError("frames x trials: too many hypotheses for one call")
-    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-    with ctx:
+    with hip.enqueue_on(dev, stream):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         pose = torch.empty(F, 3, 4, dtype=torch.float64, device=dev)
         n_in = torch.zeros(F, dtype=torch.int32, device=dev)
@@ -229,11 +206,11 @@ class stages:
 
     @staticmethod
     def prep(K, pts_2d, pts_3d, count, b_ids, frames, scale=1.0, stream=None):
-        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        K, k_shared = devargs.k_table(K, int(frames), pts_2d.device)
         cap = pts_2d.shape[0]
         rows = torch.zeros(cap, ROW_DOUBLES, dtype=torch.float64, device=pts_2d.device)
         call("oppnpd_prep", hip.ptr(pts_2d), hip.ptr(pts_3d), hip.ptr(count, torch.int32), cap, hip.ptr(b_ids, torch.int64), int(frames),
-             hip.ptr(K, torch.float64), int(K.shape[0] == 1), float(scale), hip.ptr(rows, torch.float64), hip.stream_arg(stream))
+             hip.ptr(K, torch.float64), k_shared, float(scale), hip.ptr(rows, torch.float64), hip.stream_arg(stream))
         return rows
 
     @staticmethod
@@ -255,24 +232,24 @@ class stages:
 
     @staticmethod
     def score(rows, ranges, K, hyps, reproj, stream=None):
-        K = K.to(torch.float64).reshape(-1, 9).contiguous()
         F, H = hyps.shape[0], hyps.shape[1]
+        K, k_shared = devargs.k_table(K, F, rows.device)
         cnt = torch.empty(F, H, dtype=torch.int32, device=rows.device)
         cost = torch.empty(F, H, dtype=torch.float64, device=rows.device)
-        call("oppnpd_score", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1),
+        call("oppnpd_score", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), k_shared,
              hip.ptr(hyps, torch.float64), rows.shape[0], F, H, float(reproj), hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.stream_arg(stream))
         return cnt, cost
 
     @staticmethod
     def select(cnt, cost, rows, ranges, count, K, hyps, reproj, confidence, trials, stream=None):
-        K = K.to(torch.float64).reshape(-1, 9).contiguous()
         F, H, dev = hyps.shape[0], hyps.shape[1], rows.device
+        K, k_shared = devargs.k_table(K, F, rows.device)
         nblk = (H + SELECT_BLOCK - 1) // SELECT_BLOCK
         partial = torch.empty(16 * F * nblk, dtype=torch.uint8, device=dev)
         best, n_in, status = (torch.empty(F, dtype=torch.int32, device=dev) for _ in range(3))
         mask = torch.zeros(rows.shape[0], dtype=torch.uint8, device=dev)
         call("oppnpd_select", hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32),
-             hip.ptr(count, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1), hip.ptr(hyps, torch.float64), rows.shape[0], F, H,
+             hip.ptr(count, torch.int32), hip.ptr(K, torch.float64), k_shared, hip.ptr(hyps, torch.float64), rows.shape[0], F, H,
              float(reproj), float(confidence), int(trials), hip.ptr(partial, None), hip.ptr(best, torch.int32), hip.ptr(n_in, torch.int32),
              hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
         return best, n_in, status, mask
@@ -280,10 +257,10 @@ class stages:
     @staticmethod
     def refine(rows, ranges, K, hyps, best, n_inliers, status, mask, reproj, scale=1.0, stream=None):
         """Updates ``n_inliers``, ``status`` and ``mask`` in place; returns ``pose [F, 3, 4]``"""
-        K = K.to(torch.float64).reshape(-1, 9).contiguous()
         F, H = hyps.shape[0], hyps.shape[1]
+        K, k_shared = devargs.k_table(K, F, rows.device)
         pose = torch.empty(F, 3, 4, dtype=torch.float64, device=rows.device)
-        call("oppnpd_refine", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), int(K.shape[0] == 1),
+        call("oppnpd_refine", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), k_shared,
              hip.ptr(hyps, torch.float64), hip.ptr(best, torch.int32), rows.shape[0], F, H, float(reproj), float(scale), hip.ptr(pose, torch.float64),
              hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
         return pose

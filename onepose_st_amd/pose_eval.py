@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import cabi, hip
+from . import cabi, devargs, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
@@ -115,16 +115,14 @@ class DevicePoseErrors:
 
     def pack(self) -> torch.Tensor:
         """One uint8 device tensor for one read-back: the float64 outputs that exist in the order above, then the flags"""
-        return torch.cat([t.view(torch.uint8) for t in self._doubles()] + [self.flags.view(torch.uint8)])
+        return devargs.pack(self._doubles() + [self.flags])
 
     def unpack(self, packed) -> dict:
         """The host arrays of :meth:`pack`'s bytes (a uint8 numpy array): ``rot_cos``, ``t_err``, ``flags`` and, where they exist,
         ``add_dist`` and ``proj2d``"""
-        F = self.flags.shape[0]
-        names = [n for n in ("rot_cos", "t_err", "add_dist", "proj2d") if getattr(self, n) is not None]
-        out = {n: packed[8 * F * k:8 * F * (k + 1)].view(np.float64).copy() for k, n in enumerate(names)}
-        out["flags"] = packed[8 * F * len(names):8 * F * len(names) + 4 * F].view(np.int32).copy()
-        return out
+        names = [n for n in ("rot_cos", "t_err", "add_dist", "proj2d", "flags") if getattr(self, n) is not None]
+        arrays, _ = devargs.unpack(packed, devargs.packed_layout(getattr(self, n) for n in names))
+        return {n: a.copy() for n, a in zip(names, arrays)}
 
     def to_host(self, diameter=None, percentage=0.1) -> dict:
         """The one read-back, in the reference's keys: ``R_errs`` (degrees: ``rad2deg(arccos(rot_cos))``) and ``t_errs`` (cm), both
@@ -143,17 +141,6 @@ class DevicePoseErrors:
         if "proj2d" in host:
             out["proj2D_metric"] = host["proj2d"]
         return out
-
-
-def _pose_table(name, p, dev=None):
-    """-> (contiguous float64 device tensor, stride in doubles) of a ``[F, 3, 4]`` or ``[F, 4, 4]`` table"""
-    if not isinstance(p, torch.Tensor):
-        if dev is None:
-            raise TypeError(f"{name}: expected a tensor")
-        p = torch.as_tensor(np.ascontiguousarray(p, dtype=np.float64), device=dev)
-    if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)):
-        raise ValueError(f"{name}: [F, 3, 4] or [F, 4, 4]")
-    return p.to(torch.float64).contiguous(), 4 * int(p.shape[1])
 
 
 def pose_errors(poses, pose_gt, *, status=None, unit="m", model_points=None, K=None, symmetric=False, stream=None,
@@ -177,9 +164,8 @@ def pose_errors(poses, pose_gt, *, status=None, unit="m", model_points=None, K=N
                                   if isinstance(v, torch.Tensor) or k == "status" and v is not None]
     hip.need_device(named)
     dev = poses.device
-    pred, pred_stride = _pose_table("poses", poses)
-    gt, gt_stride = _pose_table("pose_gt", pose_gt, dev)
-    F = int(pred.shape[0])
+    pred, gt = (devargs.mat64(n, p, [(None, 3, 4), (None, 4, 4)], dev, "[F, 3, 4] or [F, 4, 4]") for n, p in (("poses", poses), ("pose_gt", pose_gt)))
+    F, pred_stride, gt_stride = int(pred.shape[0]), 4 * int(pred.shape[1]), 4 * int(gt.shape[1])        # strides in doubles
     if gt.shape[0] != F or not 1 <= F <= MAX_FRAMES:
         raise ValueError(f"poses and pose_gt: the same number of frames, in [1, {MAX_FRAMES}]")
     if status is not None:
@@ -194,16 +180,11 @@ def pose_errors(poses, pose_gt, *, status=None, unit="m", model_points=None, K=N
             raise ValueError(f"model_points: float32 [V, 3], 1 <= V <= {MAX_VERTICES}")
         verts = verts.contiguous()
     if K is not None:
-        if not isinstance(K, torch.Tensor):
-            K = torch.as_tensor(np.asarray(K, dtype=np.float64), device=dev)
-        if tuple(K.shape) not in ((3, 3), (F, 3, 3)):
-            raise ValueError(f"K: [3, 3] shared, or [{F}, 3, 3]")
-        k_shared = int(K.dim() == 2)
-        K = K.to(torch.float64).reshape(-1, 9).contiguous()
+        K, k_shared = devargs.k_table(K, F, dev, exact=True)
     if pair_budget is not None and (int(pair_budget) != pair_budget or not 1 <= pair_budget <= MAX_PAIRS_PER_LAUNCH):
         raise ValueError(f"pair_budget: an integer in [1, {MAX_PAIRS_PER_LAUNCH}]")
     P, S = hip.ptr, hip.stream_arg(stream)
-    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev):
+    with hip.enqueue_on(dev, stream):
         rot_cos, t_err = (torch.empty(F, dtype=torch.float64, device=dev) for _ in range(2))
         flags = torch.empty(F, dtype=torch.int32, device=dev)
         call("opevl_errors", P(pred, torch.float64), pred_stride, P(gt, torch.float64), gt_stride, P(status, torch.int32),

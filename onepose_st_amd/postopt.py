@@ -79,18 +79,14 @@ def convert_pose2angleAxis(pose) -> np.ndarray:
 
 # ---- device calls ----------------------------------------------------------------------------------------------------------------------
 def _dev64(t: torch.Tensor, name: str, shape_tail: tuple) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a tensor")
-    if not t.is_cuda:
-        raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+    hip.need_device([(name, t)])
     if tuple(t.shape[1:]) != shape_tail:
         raise ValueError(f"{name}: expected shape [N, {', '.join(map(str, shape_tail))}], got {tuple(t.shape)}")
     return t.to(torch.float64).contiguous()
 
 
 def _dev_index(t: torch.Tensor, name: str, n: int, hi: int) -> torch.Tensor:
-    if not t.is_cuda:
-        raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+    hip.on_device([t])
     t = t.reshape(-1).to(torch.int64).contiguous()
     if t.numel() != n:
         raise ValueError(f"{name}: expected {n} entries, got {t.numel()}")
@@ -111,8 +107,9 @@ def adam_step_table(lr: float, max_steps: int, betas=ADAM_BETAS) -> list:
 
 def _flat_problem(depth, n_query, intrinsic0, intrinsic1, mkpts0_c, mkpts1_f, left_pose_idx, right_pose_idx, angle_axis_to_world):
     """The validation and flat layout both solvers share: -> (d [P] (a copy), offs [P + 1], K0, K1, mk0, mk1, li, ri, aa, P, L, F)."""
-    if not isinstance(n_query, torch.Tensor) or not n_query.is_cuda or not depth.is_cuda:
-        raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+    if not isinstance(n_query, torch.Tensor):               # host numbers are refused like a CPU tensor
+        raise hip.HipLibraryError(hip.NO_CPU_FALLBACK)
+    hip.on_device([n_query, depth])
     d = _dev64(depth.reshape(-1, 1), "depth", (1,)).reshape(-1).clone()
     P = d.numel()
     K0 = _dev64(intrinsic0, "intrinsic0", (3, 3))
@@ -297,8 +294,7 @@ class Optimizer:
                           "Please check whether installation is correct!")
             self.solver_type = "FirstOrder"
         depth = aggregated["depth"]
-        if not depth.is_cuda:
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        hip.on_device([depth])
         dev = depth.device
         ids = list(frame_poses.keys())
         poses = [v["initial_pose"] if isinstance(v, dict) else v for v in frame_poses.values()]

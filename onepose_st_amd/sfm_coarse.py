@@ -48,9 +48,7 @@ MAX_IMAGES = 1 << 22                    # OPHIP_SFM_POINTS2D_MAX_IMAGES
 def check_inputs(mkpts0: torch.Tensor, mkpts1: torch.Tensor, mconf: torch.Tensor, pair_offsets: torch.Tensor, pair_images: torch.Tensor,
                  n_images: int):
     """``merge_pair_matches``' input checks, on tensors of any device (the errors of the module docstring) -> (T, P, I)"""
-    for name, t in (("mkpts0", mkpts0), ("mkpts1", mkpts1), ("mconf", mconf), ("pair_offsets", pair_offsets), ("pair_images", pair_images)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor")
+    hip.need_tensors((("mkpts0", mkpts0), ("mkpts1", mkpts1), ("mconf", mconf), ("pair_offsets", pair_offsets), ("pair_images", pair_images)))
     I = int(n_images)
     T = mconf.shape[0] if mconf.dim() == 1 else -1
     for name, t, shape in (("mkpts0", mkpts0, (T, 2)), ("mkpts1", mkpts1, (T, 2)), ("mconf", mconf, (T,))):
@@ -170,8 +168,7 @@ def match_pairs(matcher, images, pairs, max_batch: int = 16) -> dict:
         if not (0 <= a < len(images) and 0 <= b < len(images)):
             raise IndexError(f"pair ({a}, {b}): image index outside [0, {len(images)})")
     for img, s in images:
-        if not img.is_cuda or not s.is_cuda:
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        hip.on_device((img, s))
         if img.dim() != 4 or img.shape[:2] != (1, 1) or s.dtype != torch.float32 or tuple(s.shape) != (1, 2):
             raise ValueError("images: (tensor [1, 1, H, W], scale float32 [1, 2]) per image")
     dev = images[pairs[0][0]][0].device

@@ -77,8 +77,7 @@ def _image_list(images) -> list:
         images = list(images)
     out = []
     for n, img in enumerate(images):
-        if not isinstance(img, torch.Tensor):
-            raise TypeError(f"images[{n}]: expected a tensor")
+        hip.need_tensors([(f"images[{n}]", img)])
         if img.dim() not in (2, 3, 4) or any(s != 1 for s in img.shape[:-2]):
             raise ValueError(f"images[{n}]: one grey image [H, W], [1, H, W] or [1, 1, H, W], got {list(img.shape)}")
         H, W = img.shape[-2:]
@@ -99,8 +98,7 @@ def build_feature_bank(matcher, images, scales=None, max_batch: int = 16, max_by
     if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
         raise ValueError("max_batch: an int >= 1")
     if scales is not None:
-        if not isinstance(scales, torch.Tensor):
-            raise TypeError("scales: expected a tensor")
+        hip.need_tensors([("scales", scales)])
         if scales.dtype != torch.float32 or tuple(scales.shape) != (I, 2):
             raise ValueError(f"scales: expected float32 [{I}, 2], got {scales.dtype} {list(scales.shape)}")
     sizes = [tuple(int(s) for s in img.shape[-2:]) for img in imgs]
@@ -168,9 +166,7 @@ def check_pairs(pairs: dict, n_images: int, ranges: bool = True) -> int:
     missing = [k for k in PAIR_KEYS if k not in pairs]
     if missing:
         raise ValueError(f"pairs lacks {missing}")
-    for k in PAIR_KEYS:
-        if not isinstance(pairs[k], torch.Tensor):
-            raise TypeError(f"pairs[{k!r}]: expected a tensor")
+    hip.need_tensors((f"pairs[{k!r}]", pairs[k]) for k in PAIR_KEYS)
     M = pairs["mkpts0_c"].shape[0] if pairs["mkpts0_c"].dim() == 2 else -1
     for k in ("mkpts0_c", "mkpts1_c"):
         t = pairs[k]

@@ -61,16 +61,6 @@ MAX_ITEMS, PAIR_TILE, PAIR_MAX_CHUNKS = map(_BINDING.constant, ("MAX_ITEMS", "PA
 DIM_COARSE, DIM_FINE = 256, 128
 
 
-def _tensors(named, need_device: bool):
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor")
-    if need_device:
-        for name, t in named:
-            if not t.is_cuda:
-                raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
-
-
 def _check_offsets(name: str, off: torch.Tensor, total: int, min_len: int = 0):
     if off.dtype != torch.int64 or off.dim() != 1 or off.numel() < 2:
         raise ValueError(f"{name}: expected int64 [n + 1], n >= 1")
@@ -95,9 +85,9 @@ def check_track_inputs(assigned_image, assigned_kpt, row_offsets, ref_image, ref
         raise NotImplementedError(f"aggregation_method {aggregation_method!r}: the reference implements 'avg' only")
     if keypoints_update_method != "colmap_updated_keypoints":
         raise NotImplementedError(f"keypoints_update_method {keypoints_update_method!r}: only 'colmap_updated_keypoints' (coordinates untouched)")
-    _tensors((("assigned_image", assigned_image), ("assigned_kpt", assigned_kpt), ("row_offsets", row_offsets), ("ref_image", ref_image),
-              ("ref_kpt", ref_kpt), ("feature_c0", feature_c0), ("feature_c1", feature_c1), ("feature0", feature0), ("feature1", feature1),
-              ("kpt_offsets", kpt_offsets)), False)
+    hip.need_tensors((("assigned_image", assigned_image), ("assigned_kpt", assigned_kpt), ("row_offsets", row_offsets), ("ref_image", ref_image),
+                      ("ref_kpt", ref_kpt), ("feature_c0", feature_c0), ("feature_c1", feature_c1), ("feature0", feature0), ("feature1", feature1),
+                      ("kpt_offsets", kpt_offsets)))
     R = ref_image.shape[0] if ref_image.dim() == 1 else -1
     P = assigned_image.shape[0] if assigned_image.dim() == 1 else -1
     for name, t, shape in (("assigned_image", assigned_image, (P,)), ("assigned_kpt", assigned_kpt, (P,)), ("ref_image", ref_image, (R,)),
@@ -140,7 +130,7 @@ def aggregate_track_features(assigned_image, assigned_kpt, row_offsets, ref_imag
     names = ("assigned_image", "assigned_kpt", "row_offsets", "ref_image", "ref_kpt", "feature_c0", "feature_c1", "feature0", "feature1",
              "kpt_offsets")
     if aggregation_method == "avg" and keypoints_update_method == "colmap_updated_keypoints":
-        _tensors(tuple(zip(names, args)), True)
+        hip.need_device(tuple(zip(names, args)))
     P, R, I, U = check_track_inputs(*args, keypoints_update_method=keypoints_update_method, aggregation_method=aggregation_method)
     dev = feature_c0.device
     Pt, i64 = hip.ptr, torch.int64
@@ -160,7 +150,7 @@ def aggregate_track_features(assigned_image, assigned_kpt, row_offsets, ref_imag
 def check_point_inputs(point_ids, xyz, track_len, bbox_corners, max_num_kp3d, dist_threshold):
     """Stage B's input checks, on tensors of any device -> Q"""
     named = [("point_ids", point_ids), ("xyz", xyz), ("track_len", track_len)] + ([] if bbox_corners is None else [("bbox_corners", bbox_corners)])
-    _tensors(named, False)
+    hip.need_tensors(named)
     Q = point_ids.shape[0] if point_ids.dim() == 1 else -1
     if point_ids.dtype != torch.int64 or Q < 1:
         raise ValueError("point_ids: expected int64 [Q], Q >= 1")
@@ -201,7 +191,7 @@ def select_points(point_ids, xyz, track_len, bbox_corners=None, max_num_kp3d: in
     """Stage B of the module docstring -> ``{"keypoints3d" [N, 3] float64, "group_offsets" [N + 1], "group_members" [sum] int64 (old ids),
     "track_length" int, "counts" {"input", "after_bbox", "after_track_length", "after_merge", "close_entries"}}``"""
     named = [("point_ids", point_ids), ("xyz", xyz), ("track_len", track_len)] + ([] if bbox_corners is None else [("bbox_corners", bbox_corners)])
-    _tensors(named, True)
+    hip.need_device(named)
     Q = check_point_inputs(point_ids, xyz, track_len, bbox_corners, max_num_kp3d, dist_threshold)
     dev = xyz.device
     Pt, S, i64, u8 = hip.ptr, hip.stream_handle(), torch.int64, torch.uint8
@@ -259,7 +249,7 @@ def select_points(point_ids, xyz, track_len, bbox_corners=None, max_num_kp3d: in
 def observation_runs(point3D_ids, group_offsets, group_members) -> tuple:
     """Stage C's integer half: which 2D keypoints each new point averages, in the summation order.
     -> (obs [sum] int64 slots, runs [N + 1] int64): point n owns ``obs[runs[n] : runs[n + 1]]``"""
-    _tensors((("point3D_ids", point3D_ids), ("group_offsets", group_offsets), ("group_members", group_members)), True)
+    hip.need_device((("point3D_ids", point3D_ids), ("group_offsets", group_offsets), ("group_members", group_members)))
     if point3D_ids.dtype != torch.int64 or point3D_ids.dim() != 1 or point3D_ids.numel() < 1:
         raise ValueError("point3D_ids: expected int64 [U], U >= 1")
     if group_members.dtype != torch.int64 or group_members.dim() != 1:
@@ -288,7 +278,7 @@ def observation_runs(point3D_ids, group_offsets, group_members) -> tuple:
 
 def point_means(table, obs, runs) -> torch.Tensor:
     """Stage C's float half: ``table [U, dim]`` float32 -> ``[N, dim]`` float64 means over ``observation_runs``' rows, in their order"""
-    _tensors((("table", table),), True)
+    hip.need_device((("table", table),))
     if table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 1:
         raise ValueError(f"table: expected float32 [U, dim], got {table.dtype} {list(table.shape)}")
     N, (U, dim) = runs.numel() - 1, table.shape
@@ -300,7 +290,7 @@ def point_means(table, obs, runs) -> torch.Tensor:
 
 def average_point_features(point3D_ids, table, group_offsets, group_members) -> tuple:
     """Stage C of the module docstring -> ``(descriptors3d [N, dim] float64, scores3d [N, 1] float64 ones)``"""
-    _tensors((("point3D_ids", point3D_ids), ("table", table), ("group_offsets", group_offsets), ("group_members", group_members)), True)
+    hip.need_device((("point3D_ids", point3D_ids), ("table", table), ("group_offsets", group_offsets), ("group_members", group_members)))
     if table.dim() != 2 or point3D_ids.dim() != 1 or table.shape[0] != point3D_ids.shape[0]:
         raise ValueError("table: expected float32 [U, dim] with one row per entry of point3D_ids")
     obs, runs = observation_runs(point3D_ids, group_offsets, group_members)

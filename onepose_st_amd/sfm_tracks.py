@@ -88,9 +88,7 @@ def check_model(model: dict, feature_track_assignment_strategy: str = "greedy") 
     if missing:
         raise ValueError(f"model lacks {missing}")
     m = {k: model[k] for k in MODEL_KEYS}
-    for k, v in m.items():
-        if not isinstance(v, torch.Tensor):
-            raise TypeError(f"{k}: expected a tensor")
+    hip.need_tensors(m.items())
     i64, f64 = torch.int64, torch.float64
     I = m["image_ids"].shape[0] if m["image_ids"].dim() == 1 else -1
     Q = m["point_ids"].shape[0] if m["point_ids"].dim() == 1 else -1

@@ -90,9 +90,7 @@ def check_inputs(merged: dict, cameras: dict) -> dict:
         raise ValueError(f"merged / cameras lack {missing}")
     m = {k: merged[k] for k in MERGED_KEYS}
     m.update({k: cameras[k] for k in CAMERA_KEYS})
-    for k, v in m.items():
-        if not isinstance(v, torch.Tensor):
-            raise TypeError(f"{k}: expected a tensor")
+    hip.need_tensors(m.items())
     i64, f64 = torch.int64, torch.float64
     I = m["image_ids"].shape[0] if m["image_ids"].dim() == 1 else -1
     U = m["keypoints"].shape[0] if m["keypoints"].dim() == 2 else -1
@@ -172,8 +170,8 @@ def triangulate(merged: dict, cameras: dict, **options) -> dict:
     """The module docstring's ``triangulate``"""
     o = check_options(options)
     named = [(k, merged.get(k)) for k in MERGED_KEYS] + [(k, cameras.get(k)) for k in CAMERA_KEYS]
-    if all(isinstance(t, torch.Tensor) for _, t in named) and not all(t.is_cuda for _, t in named):
-        raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+    if all(isinstance(t, torch.Tensor) for _, t in named):      # anything else is check_inputs' to report
+        hip.on_device(t for _, t in named)
     d = check_inputs(merged, cameras)
     I, U = d["I"], d["U"]
     dev = merged["keypoints"].device

@@ -19,7 +19,7 @@ import math
 import numpy as np
 import torch
 
-from . import cabi, hip
+from . import cabi, devargs, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
@@ -63,30 +63,6 @@ class Queries:
     def __init__(self, pts, pts_3d, count, keep=()):
         self.pts, self.pts_3d, self.count = pts, pts_3d, count
         self._keep = keep
-
-
-def _count_arg(count, dev):
-    if count is None or isinstance(count, torch.Tensor):
-        if count is not None and (count.dtype != torch.int32 or count.numel() != 1):
-            raise ValueError("count: one int32 on the device")
-        return count
-    return torch.full((1,), int(count), dtype=torch.int32, device=dev)
-
-
-def _table(name2, t2, name3, t3):
-    if t2.dim() != 2 or t2.shape[1] != 2 or t3.dim() != 2 or t3.shape[1] != 3 or t2.shape[0] != t3.shape[0] or t2.shape[0] < 1:
-        raise ValueError(f"{name2} [cap, 2] and {name3} [cap, 3] must have the same length, at least 1")
-    if t2.dtype != torch.float32 or t3.dtype != torch.float32:
-        raise ValueError(f"{name2} and {name3}: float32")
-    return t2.contiguous(), t3.contiguous()
-
-
-def _mat(name, m, shape, dev):
-    if not isinstance(m, torch.Tensor):
-        m = torch.as_tensor(np.asarray(m, dtype=np.float64), device=dev)
-    if tuple(m.shape) != shape:
-        raise ValueError(f"{name}: {list(shape)}")
-    return m.to(torch.float64).contiguous()
 
 
 def build_pyramid(frame_u8: torch.Tensor, levels: int = DEFAULTS["levels"], stream=None) -> Pyramid:
@@ -139,8 +115,8 @@ def track(src: Pyramid, dst: Pyramid, pts, *, count=None, guess=None, pts_3d=Non
     if pts_3d is not None:
         if pts_3d.dtype != torch.float32 or tuple(pts_3d.shape) != (cap, 3):
             raise ValueError(f"pts_3d: float32 [{cap}, 3]")
-        pts_3d, pose, K = pts_3d.contiguous(), _mat("pose", pose, (3, 4), dev), _mat("K", K, (3, 3), dev)
-    count = _count_arg(count, dev)
+        pts_3d, pose, K = pts_3d.contiguous(), devargs.mat64("pose", pose, [(3, 4)], dev), devargs.mat64("K", K, [(3, 3)], dev)
+    count = devargs.count_arg(count, dev)
     if out is None:
         out = Tracks(torch.empty(cap, 2, dtype=torch.float64, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
                      torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.float64, device=dev))
@@ -162,15 +138,13 @@ def collect(pts_2d, pts_3d, trans, *, count=None, mask=None, stream=None) -> Que
     ``trans`` (``optmp_collect``)."""
     hip.need_device([("pts_2d", pts_2d), ("pts_3d", pts_3d)] + [(k, v) for k, v in (("trans", trans), ("count", count), ("mask", mask))
                                                              if isinstance(v, torch.Tensor) or k == "mask" and v is not None])
-    pts_2d, pts_3d = _table("pts_2d", pts_2d, "pts_3d", pts_3d)
+    pts_2d, pts_3d = devargs.point_tables("pts_2d", pts_2d, 2, "pts_3d", pts_3d, 3, max_rows=MAX_ROWS, min_rows=1)
     cap, dev = int(pts_2d.shape[0]), pts_2d.device
-    if cap > MAX_ROWS:
-        raise ValueError(f"at most {MAX_ROWS} rows")
     if mask is not None:
         if mask.dtype != torch.uint8 or tuple(mask.shape) != (cap,):
             raise ValueError(f"mask: uint8 [{cap}]")
         mask = mask.contiguous()
-    trans, count = _mat("trans", trans, (3, 3), dev), _count_arg(count, dev)
+    trans, count = devargs.mat64("trans", trans, [(3, 3)], dev), devargs.count_arg(count, dev)
     out = Queries(torch.empty(cap, 2, dtype=torch.float64, device=dev), torch.empty(cap, 3, dtype=torch.float32, device=dev),
                   torch.empty(1, dtype=torch.int32, device=dev), keep=(pts_2d, pts_3d, mask, trans, count))
     P = hip.ptr
@@ -190,7 +164,7 @@ def inject(own_2d, own_3d, own_count, sources, trans, *, stream=None):
             raise TypeError("sources: (Queries, Tracks) pairs")
         named += [("source pts_3d", q.pts_3d), ("source pts", tr.pts), ("source flags", tr.flags)]
     hip.need_device(named)
-    own_2d, own_3d = _table("own_2d", own_2d, "own_3d", own_3d)
+    own_2d, own_3d = devargs.point_tables("own_2d", own_2d, 2, "own_3d", own_3d, 3, min_rows=1)
     cap_own, dev = int(own_2d.shape[0]), own_2d.device
     if len(sources) > MAX_SOURCES:
         raise ValueError(f"at most {MAX_SOURCES} sources")
@@ -207,7 +181,7 @@ def inject(own_2d, own_3d, own_count, sources, trans, *, stream=None):
     cap_total = cap_own + sum(caps)
     if cap_total > MAX_ROWS:
         raise ValueError(f"at most {MAX_ROWS} rows")
-    trans, own_count = _mat("trans", trans, (3, 3), dev), _count_arg(own_count, dev)
+    trans, own_count = devargs.mat64("trans", trans, [(3, 3)], dev), devargs.count_arg(own_count, dev)
     out_2d = torch.empty(cap_total, 2, dtype=torch.float32, device=dev)
     out_3d = torch.empty(cap_total, 3, dtype=torch.float32, device=dev)
     out_count = torch.empty(1, dtype=torch.int32, device=dev)
@@ -244,8 +218,9 @@ class RefinedSequence:
             if f is None:
                 out.append(None)
                 continue
-            n = f["poses"].pose.shape[0] * 108 + f["poses"].inlier_mask.shape[0] + 4
-            ((pose, _, inliers),), (raw,) = f["poses"].unpack(packed[o:o + n], (4,))
+            n_count = devargs.packed_bytes((f["count"],))
+            n = f["poses"].packed_bytes + n_count
+            ((pose, _, inliers),), (raw,) = f["poses"].unpack(packed[o:o + n], (n_count,))
             o += n
             out.append({"pose": pose, "inliers": inliers, "status": int(f["poses"].status_host[0]), "count": int(raw.view(np.int32)[0])})
         return out

@@ -69,8 +69,7 @@ def check_K(K) -> torch.Tensor:
 def _device_K(K, device):
     """:func:`check_K` on the device: a device tensor as it is, host numbers uploaded"""
     if isinstance(K, torch.Tensor):
-        if not K.is_cuda:
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+        hip.on_device([K])
         return check_K(K)
     K = check_K(K)
     if device is None or torch.device(device).type != "cuda":
@@ -96,7 +95,7 @@ def set_box(bbox, K, crop_size: int = 512, device=None) -> TrackState:
     Kd = _device_K(K, device)
     st = TrackState(Kd.device)
     P = hip.ptr
-    with torch.cuda.device(Kd.device):
+    with hip.enqueue_on(Kd.device):
         call("optrk_box_set", x0, y0, x1, y1, P(Kd, torch.float64), S, P(st.box, torch.int32), P(st.flag, torch.int32), P(st.K_crop, torch.float64),
              P(st.trans, torch.float64), hip.stream_handle())
     return st
@@ -107,11 +106,8 @@ def next_box(poses, prev_state: TrackState, K, bbox3d, *, frame: int = 0, min_in
     state that frame was cropped with; ``K`` full-frame intrinsics and ``bbox3d [8, 3]`` float64 device tensors.  Enqueued on the current
     stream -- the one the solve was enqueued on, so that the stream orders the two and the allocator may reuse the inputs afterwards;
     nothing is read back."""
-    for name, t in (("poses.pose", poses.pose), ("poses.n_inliers", poses.n_inliers), ("poses.status", poses.status), ("bbox3d", bbox3d)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor")
-        if not t.is_cuda:
-            raise hip.HipLibraryError("the HIP path needs device tensors (no CPU fallback)")
+    for named in (("poses.pose", poses.pose), ("poses.n_inliers", poses.n_inliers), ("poses.status", poses.status), ("bbox3d", bbox3d)):
+        hip.need_device([named])                    # one at a time: the first input that is wrong in either way is the one reported
     if not isinstance(prev_state, TrackState):
         raise TypeError("prev_state: a TrackState")
     F = poses.pose.shape[0]
@@ -128,7 +124,7 @@ def next_box(poses, prev_state: TrackState, K, bbox3d, *, frame: int = 0, min_in
     n_in, status = poses.n_inliers[frame:frame + 1], poses.status[frame:frame + 1]
     st = TrackState(Kd.device)                           # no reference to the inputs: a chain of states must not keep every solve's workspace
     P = hip.ptr
-    with torch.cuda.device(Kd.device):
+    with hip.enqueue_on(Kd.device):
         call("optrk_box_from_pose", P(Kd, torch.float64), P(pose, torch.float64), P(n_in, torch.int32), P(status, torch.int32), P(bbox3d, torch.float64),
              P(prev_state.box, torch.int32), P(prev_state.flag, torch.int32), int(min_inliers), S, P(st.box, torch.int32), P(st.flag, torch.int32),
              P(st.K_crop, torch.float64), P(st.trans, torch.float64), hip.stream_handle())
@@ -143,7 +139,7 @@ def crop(frame_u8: torch.Tensor, state: TrackState, crop_size: int = 512) -> tor
     S = check_crop_size(crop_size)
     frame_u8 = frame_u8.contiguous()
     out = torch.empty(1, 1, S, S, dtype=torch.float32, device=frame_u8.device)
-    with torch.cuda.device(frame_u8.device):
+    with hip.enqueue_on(frame_u8.device):
         call("optrk_crop", hip.ptr(frame_u8, torch.uint8), frame_u8.shape[0], frame_u8.shape[1], hip.ptr(state.box, torch.int32), S, hip.ptr(out),
              hip.stream_handle())
     return out
