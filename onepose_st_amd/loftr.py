@@ -16,7 +16,8 @@ definition (``oracle/loftr_oracle.py`` restates it on the CPU; parity unpinned).
 * batch: ``image0 [V, 1, H, W]`` against ``image1 [1 or V, 1, H, W]`` in ONE call -- the detector's ~15 reference views against one query
   frame (the query's backbone features are computed once); ``b_ids`` names the pair of every match;
 * dual-softmax + mutual-nearest between the two grids: ``ophip_coarse_match_2d`` (temperature exactly 0.1, all-sides border);
-* fine stage, window 9 on both images, batched over all matches: ``csrc/loftr_fine.hip``.
+* fine stage, window 9 on both images, batched over all matches: ``csrc/loftr_fine.hip``.  ``fine_window_size`` is odd, from 3 to 11
+  (``ValueError`` at construction otherwise).
 
 ``coarse.attention`` / ``fine.attention`` = ``"full"`` (each on its own; the reference config's other option) swap the attention form
 (``FullAttention``, same ``state_dict``): a coarse layer is then ``ophip_encoder_layer_full_x3_stream`` (one query stream per launch,
@@ -104,8 +105,8 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         if config["fine_concat_coarse_feat"]:
             raise NotImplementedError("fine_concat_coarse_feat")
         W = int(config["fine_window_size"])
-        if W % 2 == 0 or W * W > 128:
-            raise ValueError("fine_window_size must be odd and at most 11")
+        if W < 3 or W % 2 == 0 or W * W > 128:             # FineMatching's grid step is 2 / (W - 1); W * W heat-map slots <= 128
+            raise ValueError("fine_window_size must be odd, from 3 to 11")
         for n in list(cc["layer_names"]) + list(cf["layer_names"]):
             if n not in ("self", "cross"):
                 raise KeyError(n)
