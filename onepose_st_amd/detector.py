@@ -6,9 +6,12 @@ a box -- the view's four corners through the RANSAC affinity of its matches, or 
 when it has fewer than 6 matches -- and the view with the most inliers wins; the box is cropped to 512 x 512 with the intrinsics
 updated (``crop_img_by_bbox``: :func:`onepose_st_amd.frameloop.crop_geometry` / ``ophip_crop_resize_gray``).
 
-What differs from the reference by design: the views are matched as ONE batch (one matcher call, one read-back, the per-view RANSACs in
-parallel on the host) instead of one call and one synchronisation per view.  What differs by necessity: the reference views are handed over as arrays (its constructor reads a COLMAP model and
-decodes images with ``cv2`` / ``natsort``, neither of which exists here); ``cv2.estimateAffine2D`` is the build's own RANSAC
+What differs from the reference by design: reference views of one common size (any size: the reference's are 512 x 512 crops against a
+full frame) are matched as a batch -- consecutive chunks of views, one matcher call and one read-back per chunk, as many views per chunk
+as ``LoFTR_for_OnePose_Plus.coarse_batch_bytes`` fits into ``batch_budget_bytes`` (:func:`plan_chunks`), with
+``conf_matrix="lazy"`` for a dual-softmax matcher since nothing here reads the matrix; the per-view RANSACs run in parallel on the host
+-- instead of one call and one synchronisation per view.  Views of mixed sizes keep the view-by-view loop.  What differs by necessity:
+the reference views are handed over as arrays (its constructor reads a COLMAP model and decodes images with ``cv2`` / ``natsort``, neither of which exists here); ``cv2.estimateAffine2D`` is the build's own RANSAC
 (``oppnp_estimate_affine2d``, parity unpinned).  The control flow, thresholds, integer truncations and the tie rule (first view
 among equals) are the reference's.  ``detect`` plugs into :class:`onepose_st_amd.frameloop.SequenceRunner` as its ``detector``.
 """
@@ -30,15 +33,32 @@ def sample_reference_views(n_images: int, n_ref_view: int = 15) -> list:
     return list(range(1, n_images, gap))
 
 
+def plan_chunks(n_views: int, estimate, budget) -> list:
+    """The batched call's chunks: ``[(first, last + 1), ...]``, consecutive, covering ``range(n_views)`` once, each of the largest
+    ``Vc >= 1`` with ``estimate(Vc) <= budget`` (the last one may be shorter).  ``estimate(Vc) -> bytes`` is non-decreasing in ``Vc``;
+    ``budget=None``: no limit, one chunk.  A budget below ``estimate(1)`` still gives one view per chunk."""
+    vc = n_views if budget is None else 1
+    while vc < n_views and estimate(vc + 1) <= budget:
+        vc += 1
+    return [(a, min(a + vc, n_views)) for a in range(0, n_views, max(vc, 1))]
+
+
 class LocalFeatureObjectDetector:
-    def __init__(self, matcher, db_imgs, device=None, min_matches: int = 6, ransac_reproj_threshold: float = 6.0, vote: str = "host"):
+    def __init__(self, matcher, db_imgs, device=None, min_matches: int = 6, ransac_reproj_threshold: float = 6.0, vote: str = "host",
+                 batch_budget_bytes=4 << 30):
         """``matcher``: a ``LoFTR_for_OnePose_Plus`` on the device; ``db_imgs``: the reference views, grayscale ``[H, W]`` uint8 arrays
         (or float tensors in [0, 1]) -- already sampled (:func:`sample_reference_views`).  ``vote="device"`` adds
         :meth:`match_worker_device` and :meth:`detect_state`: the per-view RANSACs, the vote and the box's track state on the device
-        (``detect_device``), nothing read back; the host path stays as it is."""
+        (``detect_device``), nothing read back; the host path stays as it is.  ``batch_budget_bytes``: what the coarse stage of one batched
+        matcher call may allocate by the matcher's own estimate (``coarse_batch_bytes``; the fine stage's buffers are not part of it);
+        the views are split into chunks under it.  4 GiB is a design constant, not a measurement; ``None``: no
+        limit."""
         if vote not in ("host", "device"):
             raise ValueError(f"vote={vote!r}: 'host' or 'device'")
         self.vote = vote
+        if batch_budget_bytes is not None and int(batch_budget_bytes) < 0:
+            raise ValueError("batch_budget_bytes: a number of bytes >= 0, or None for no limit")
+        self.batch_budget_bytes = None if batch_budget_bytes is None else int(batch_budget_bytes)
         if vote == "device":                          # only then: ``hasattr(detector, "detect_state")`` is how SequenceRunner asks
             self.match_worker_device, self.detect_state, self._view_hw_dev = self._match_worker_device, self._detect_state, None
         self.matcher = matcher
@@ -55,6 +75,35 @@ class LocalFeatureObjectDetector:
             self.db_corners_homo.append(np.array([[0, 0, 1], [W, 0, 1], [0, H, 1], [W, H, 1]], dtype=np.float64).T)      # 3 x 4
 
     # ------------------------------------------------------------------------------------------
+    def common_view_size(self):
+        """``(H, W)`` when all reference views have one size (any size, not necessarily the query's), else ``None``"""
+        sizes = {tuple(v.shape[-2:]) for v in self.db_imgs}
+        return next(iter(sizes)) if len(sizes) == 1 else None
+
+    def plans_batch(self, batched: bool = True) -> bool:
+        """whether :meth:`match_worker` / :meth:`match_worker_device` take the batched call: more than one view, all of one size"""
+        return bool(batched) and len(self.db_imgs) > 1 and self.common_view_size() is not None
+
+    def _batched_matches(self, query):
+        """the batched form: one matcher call per chunk of views; yields each call's ``(mkpts0_f, mkpts1_f, b_ids)`` with ``b_ids``
+        counted from view 0.  A generator that hands out the match lists only: a call's data dict -- its ``conf_matrix``, or the rows a
+        lazy one keeps -- is dropped before the next chunk's call, or the chunks would add up to what the budget was to avoid"""
+        # nothing here reads conf_matrix: a dual-softmax LoFTR matcher is asked not to store it (sinkhorn needs the matrix; a stand-in
+        # without a config or without the estimate is called as it always was, all views at once)
+        cfg = getattr(self.matcher, "config", None)
+        lazy = cfg is not None and cfg["match_coarse"]["match_type"] == "dual_softmax"
+        kw = {"conf_matrix": "lazy", "budget_bytes": self.batch_budget_bytes} if lazy else {}
+        hv, wv = self.common_view_size()
+        hw0_c, hw1_c = (hv // 8, wv // 8), (query.shape[-2] // 8, query.shape[-1] // 8)
+        estimate = getattr(self.matcher, "coarse_batch_bytes", None)
+        chunks = plan_chunks(len(self.db_imgs), lambda n: estimate(n, hw0_c, hw1_c, lazy), self.batch_budget_bytes if estimate is not None else None)
+        for a, b in chunks:
+            pair = {"image0": torch.cat(self.db_imgs[a:b], 0), "image1": query}
+            self.matcher(pair, **kw)
+            out = (pair["mkpts0_f"], pair["mkpts1_f"], pair["b_ids"] + a)
+            del pair
+            yield out
+
     def _vote(self, idx: int, mkpts0: np.ndarray, mkpts1: np.ndarray, hw) -> dict:
         """One view's vote (:104-144): the view's corners through the RANSAC affinity of its matches; a fixed 1000 x 1000 box around the
         image centre when the view has fewer than ``min_matches`` matches (or RANSAC finds no model)."""
@@ -72,13 +121,13 @@ class LocalFeatureObjectDetector:
     @torch.no_grad()
     def match_worker(self, query: torch.Tensor, batched: bool = True) -> dict:
         """``{view index: {"inliers", "bbox"}}`` for every reference view (:89-144).  The reference loops over the views -- one LoFTR call
-        and one device -> host copy each; here ALL views go through the matcher as one batch (``image0 [V, 1, H, W]`` against the one
-        query: its backbone features once, every kernel launched once over V pairs) and the matches come back in ONE copy; the
-        per-view RANSACs then run side by side on host threads (``oppnp_estimate_affine2d`` releases the GIL).  ``batched=False`` keeps
-        the view-by-view form (views of different sizes take it as well); both give the same boxes."""
+        and one device -> host copy each; here views of one common size (the query may have another) go through the matcher as a batch
+        (``image0 [V, 1, H, W]`` against the one query: every kernel launched once over V pairs), in chunks under
+        ``batch_budget_bytes`` -- one call and one copy of the matches per chunk, one of each when all views fit; the per-view RANSACs
+        then run side by side on host threads (``oppnp_estimate_affine2d`` releases the GIL).  ``batched=False`` keeps the view-by-view
+        form (views of mixed sizes take it as well); both give the same boxes."""
         hw = tuple(query.shape[-2:])
-        same = all(tuple(v.shape[-2:]) == hw for v in self.db_imgs)
-        if not (batched and same and len(self.db_imgs) > 1):
+        if not self.plans_batch(batched):
             out = {}
             for idx, view in enumerate(self.db_imgs):
                 pair = {"image0": view, "image1": query}
@@ -86,9 +135,9 @@ class LocalFeatureObjectDetector:
                 both = torch.cat([pair["mkpts0_f"], pair["mkpts1_f"]], 1).cpu().numpy()
                 out[idx] = self._vote(idx, both[:, :2], both[:, 2:], hw)
             return out
-        pair = {"image0": torch.cat(self.db_imgs, 0), "image1": query}
-        self.matcher(pair)
-        packed = torch.cat([pair["b_ids"].to(torch.float32)[:, None], pair["mkpts0_f"], pair["mkpts1_f"]], 1).cpu().numpy()      # the one read-back
+        # one read-back per chunk; b_ids counts from the chunk's first view
+        packed = np.concatenate([torch.cat([b_ids.to(torch.float32)[:, None], mk0, mk1], 1).cpu().numpy()
+                                 for mk0, mk1, b_ids in self._batched_matches(query)], 0)
         view_of = packed[:, 0].astype(np.int64)
         # matches arrive in ascending (view, cell) order: a view's matches are one slice
         bounds = np.searchsorted(view_of, np.arange(len(self.db_imgs) + 1))
@@ -101,24 +150,21 @@ class LocalFeatureObjectDetector:
     # ---- vote="device" -------------------------------------------------------------------------------
     @torch.no_grad()
     def _match_worker_device(self, query: torch.Tensor, K=None, crop_size: int = 512):
-        """:meth:`match_worker` with the vote on the device -> a ``detect_device.DeviceDetection``.  The matcher call is the batched
-        one; views of other sizes than the query take one call each, concatenated with their view index as ``b_ids``; then ONE vote
-        call.  ``K`` (default: the identity) and ``crop_size`` go into the winning box's track state.  Nothing is read back after
+        """:meth:`match_worker` with the vote on the device -> a ``detect_device.DeviceDetection``.  The matcher calls are the batched
+        ones (one per chunk of views, ``b_ids`` counted from the chunk's first view); views of mixed sizes take one call each with
+        their view index as ``b_ids``; the device tensors are concatenated, then ONE vote call.  ``K`` (default: the identity) and ``crop_size`` go into the winning box's track state.  Nothing is read back after
         the matcher's own count."""
         from . import detect_device
         hw = tuple(query.shape[-2:])
-        same = all(tuple(v.shape[-2:]) == hw for v in self.db_imgs)
-        if same and len(self.db_imgs) > 1:
-            pair = {"image0": torch.cat(self.db_imgs, 0), "image1": query}
-            self.matcher(pair)
-            mk0, mk1, b_ids = pair["mkpts0_f"], pair["mkpts1_f"], pair["b_ids"]
+        if self.plans_batch():
+            parts = list(self._batched_matches(query))
         else:
             parts = []
             for idx, view in enumerate(self.db_imgs):
                 pair = {"image0": view, "image1": query}
                 self.matcher(pair)
                 parts.append((pair["mkpts0_f"], pair["mkpts1_f"], torch.full((pair["mkpts0_f"].shape[0],), idx, dtype=torch.int64, device=self.device)))
-            mk0, mk1, b_ids = (torch.cat([p[k] for p in parts], 0) for k in range(3))
+        mk0, mk1, b_ids = parts[0] if len(parts) == 1 else (torch.cat([p[k] for p in parts], 0) for k in range(3))
         if self._view_hw_dev is None:
             self._view_hw_dev = torch.tensor([list(v.shape[-2:]) for v in self.db_imgs], dtype=torch.int32).to(self.device)
         if K is None:

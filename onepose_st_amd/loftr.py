@@ -48,6 +48,14 @@ scales, extraction and the fine-only branch (which ignores them, as the referenc
 "full"`` masks raise: the published ``FullAttention`` fills a padded query row with -inf, its softmax is NaN, and the NaN reaches every
 row one layer later.
 
+``config["hip_conf_matrix"]`` = ``"lazy"`` (this build's key; ``"eager"`` when absent), or ``forward(data, conf_matrix="lazy")`` for one
+call: the ``[V, L0, L1]`` matrix is not stored -- ``ophip_coarse_match_2d[_masked]`` with ``conf == NULL``; every
+match list equals the eager form's bit for bit -- and ``data["conf_matrix"]`` is a :class:`LazyConfMatrix` that computes it on first
+use.  An exact row tie that the lazy selection cannot resolve (``count[1]``, read with the match count in one copy) runs the coarse
+matching again eagerly on the same final rows; ``lazy_reruns`` counts those calls, ``forward(..., budget_bytes=n)`` splits the re-run into
+sub-batches of pairs within ``n`` bytes (:meth:`LoFTR_for_OnePose_Plus.coarse_batch_bytes`).  Sinkhorn matching needs the matrix:
+``"lazy"`` with it is a ``ValueError``, as is any other value.
+
 Malformed masks (a lone mask, another dtype, image-resolution masks, a wrong batch or grid), malformed scale / keypoint tensors, a tensor
 without its partner, V > 1 with provided matches or extraction, and coarse extraction with a ``feature_hook`` raise
 ``NotImplementedError`` before anything runs.  No CPU fallback.
@@ -63,17 +71,47 @@ import torch.nn as nn
 from . import hip, host_math, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
+from .lazy_conf import LazyConfMatrixBase
 from .params import EncoderParams, load_matcher_checkpoint
 from .rows import rows_encoder_layer
 
-default_cfg = {
+# this build's own config keys and their defaults.  "hip_conf_matrix": "eager" stores conf_matrix, "lazy" does not (see the module text)
+BUILD_KEYS = {"hip_conf_matrix": "eager"}
+
+
+class _ReferenceConfig(dict):
+    """``default_cfg``: its items are the reference's config and nothing else -- it still compares equal to the reference's dict -- and
+    a lookup of one of this build's own keys (``BUILD_KEYS``) answers with that key's default.  A config that sets such a key holds it
+    as an ordinary item; one without it (any plain dict written for the reference) means the default."""
+
+    def __missing__(self, key):
+        return BUILD_KEYS[key]
+
+
+default_cfg = _ReferenceConfig({
     "backbone_type": "ResNetFPN", "resolution": (8, 2), "fine_window_size": 9, "fine_concat_coarse_feat": False,
     "resnetfpn": {"initial_dim": 128, "block_dims": [128, 196, 256]},
     "coarse": {"d_model": 256, "d_ffn": 256, "nhead": 8, "layer_names": ["self", "cross"] * 4, "attention": "linear", "temp_bug_fix": False},
     "match_coarse": {"thr": 0.2, "border_rm": 2, "match_type": "dual_softmax", "dsmax_temperature": 0.1, "skh_iters": 3,
                      "skh_init_bin_score": 1.0, "skh_prefilter": True, "train_coarse_percent": 0.4, "train_pad_num_gt_min": 200},
     "fine": {"d_model": 128, "d_ffn": 128, "nhead": 8, "layer_names": ["self", "cross"] * 1, "attention": "linear"},
-}
+})
+
+
+class LazyConfMatrix(LazyConfMatrixBase):
+    """``data["conf_matrix"]`` of a lazy call: keeps the coarse transformer's final rows ``x0 [V, L0, 256]``, ``x1 [V, L1, 256]`` (and the
+    flattened padding masks) and nothing V x L0 x L1.  First use runs ``match(x0, x1, masks)`` -- the eager
+    ``ophip_coarse_match_2d[_masked]`` call on those rows with scratch match lists -- and keeps its matrix: the eager forward's bits."""
+
+    def __init__(self, match, x0, x1, masks, stream):
+        super().__init__((x0.shape[0], x0.shape[1], x1.shape[1]), x0.device)
+        self._match, self._x0, self._x1, self._masks, self._stream = match, x0, x1, masks, stream
+
+    def _compute(self) -> torch.Tensor:
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)          # the forward's stream has produced the rows
+        conf = self._match(self._x0, self._x1, self._masks)
+        self._match = self._x0 = self._x1 = self._masks = None
+        return conf
 
 
 class LoFTR_for_OnePose_Plus(nn.Module):
@@ -94,6 +132,10 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         if mc["match_type"] not in ("dual_softmax", "sinkhorn"):
             raise NotImplementedError("match_coarse.match_type: dual_softmax or sinkhorn")
         self.sinkhorn = mc["match_type"] == "sinkhorn"
+        # "lazy": conf_matrix is not stored (ophip_coarse_match_2d[_masked] with conf == NULL; the match lists are the eager form's bit
+        # for bit) and data["conf_matrix"] is a LazyConfMatrix.  forward(data, conf_matrix=...) overrides it for one call
+        self.conf_matrix_mode = self._conf_form(config.get("hip_conf_matrix", BUILD_KEYS["hip_conf_matrix"]), "hip_conf_matrix")
+        self.lazy_reruns = 0                           # lazy calls that met an exact row tie and ran the coarse matching again eagerly
         if self.sinkhorn:
             iters = mc["skh_iters"]
             if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
@@ -126,6 +168,38 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         self.feature_hook = None
 
     # ------------------------------------------------------------------------------------------
+    def _conf_form(self, value, what) -> str:
+        """``"eager"`` / ``"lazy"`` -> the value; anything else, or ``"lazy"`` with sinkhorn matching, raises ``ValueError``"""
+        if value not in ("eager", "lazy"):
+            raise ValueError(f"{what} {value!r}: expected 'eager' or 'lazy'")
+        if value == "lazy" and self.sinkhorn:
+            raise ValueError(f"{what} = 'lazy' with match_type 'sinkhorn': ophip_coarse_match_2d_sinkhorn requires conf")
+        return value
+
+    def coarse_batch_bytes(self, V: int, hw0_c, hw1_c, lazy: bool) -> int:
+        """Upper estimate, in bytes, of what the coarse stage of ONE call allocates for ``V`` pairs of coarse grids ``hw0_c`` x ``hw1_c``
+        (cells): what :class:`onepose_st_amd.detector.LocalFeatureObjectDetector` holds against its ``batch_budget_bytes``.  The sum of
+
+        * ``4 * V * (L0 + L1) * 256 * 4``: the rows -- input, output and one layer in flight for both streams, the shared query expanded;
+        * the coarse transformer's workspace: ``ophip_encoder_x3w8_workspace_bytes(V, L0, L1)``, with ``coarse.attention = "full"``
+          ``ophip_encoder_full_stream_workspace_bytes(V, max(L0, L1), max(L0, L1))``;
+        * the coarse matching's workspace: ``4 * ophip_coarse_workspace_floats(V, L0, L1)`` (sinkhorn: its own query);
+        * the match lists of capacity ``V * L0``: 57 bytes a slot as the entry point writes them, 24 more for their compacted and scaled
+          copies, and 64 bytes a cell of image 0 plus 8 KiB for the point table, the count and the allocator's rounding of small blocks;
+        * ``4 * V * L0 * L1`` for ``conf_matrix`` when not ``lazy``.
+
+        Host arithmetic and three size queries: no device is touched.  Not counted: the backbone, and the fine stage's buffers
+        (``K * W * W * 128`` floats, a few at a time), which depend on the number of matches; the eager re-run of a lazy call that met an
+        exact tie (it is held under the budget by its own sub-batches)."""
+        lib = hip.load()
+        V, L0, L1 = int(V), int(hw0_c[0]) * int(hw0_c[1]), int(hw1_c[0]) * int(hw1_c[1])
+        rows = 4 * V * (L0 + L1) * 256 * 4
+        Lm = max(L0, L1)
+        enc = lib.ophip_encoder_full_stream_workspace_bytes(V, Lm, Lm) if self.coarse_full else lib.ophip_encoder_x3w8_workspace_bytes(V, L0, L1)
+        cws = 4 * (lib.ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else lib.ophip_coarse_workspace_floats)(V, L0, L1)
+        lists = (57 + 24) * V * L0 + 64 * L0 + 8192
+        return int(rows + enc + cws + lists + (0 if lazy else 4 * V * L0 * L1))
+
     def _blocks(self, device):
         params = list(self.parameters()) + list(self.buffers())
         key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
@@ -249,6 +323,10 @@ class LoFTR_for_OnePose_Plus(nn.Module):
     def forward(self, data, **kwargs):
         if self.training:
             raise NotImplementedError("inference only")
+        # conf_matrix = "lazy" / "eager": this call's form (default: the config's); budget_bytes: what the eager re-run of a lazy call
+        # that met an exact tie may allocate per sub-batch (None: all pairs at once)
+        lazy = self._conf_form(kwargs.get("conf_matrix", self.conf_matrix_mode), "conf_matrix") == "lazy"
+        budget = kwargs.get("budget_bytes")
         fine_only, has_s, ext_c, ext_f = self._check_inputs(data, kwargs)
         img0, img1 = data["image0"], data["image1"]
         V = img0.size(0)
@@ -268,7 +346,8 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             data.update({"m_bids": b_ids, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "mconf": torch.ones_like(b_ids)})
         else:
             masks = (data["mask0"], data["mask1"]) if "mask0" in data else None
-            x0, x1, conf, b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0c, mk1c = self._coarse(Wb, fc0, fc1, hw0_c, hw1_c, scale, s0, s1, masks)
+            x0, x1, conf, b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0c, mk1c = self._coarse(Wb, fc0, fc1, hw0_c, hw1_c, scale, s0, s1, masks,
+                                                                                                 lazy, budget)
             data.update({"conf_matrix": conf, "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids, "m_bids": m_bids, "gt_mask": gt_mask,
                          "mconf": mconf, "mkpts0_c": mk0c, "mkpts1_c": mk1c})
         if self.enable_fine_matching:
@@ -333,10 +412,12 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             raise IndexError(f"{nbad} provided coarse keypoint(s) round to a cell outside the coarse grid")
         return b_ids, i_ids, j_ids
 
-    def _coarse(self, Wb, fc0, fc1, hw0_c, hw1_c, scale, s0, s1, masks):
+    def _coarse(self, Wb, fc0, fc1, hw0_c, hw1_c, scale, s0, s1, masks, lazy=False, budget=None):
         """coarse transformer and coarse matching between the two grids; ``masks``: None or ``(mask0, mask1)`` as the caller gave them
-        -> final rows ``x0, x1``, ``conf_matrix`` and the K matches ``b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mkpts0_c, mkpts1_c``"""
-        call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        -> final rows ``x0, x1``, ``conf_matrix`` and the K matches ``b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mkpts0_c, mkpts1_c``.
+        ``lazy``: no ``[V, L0, L1]`` tensor is allocated, ``conf_matrix`` is a :class:`LazyConfMatrix`; an exact row tie that the
+        selection cannot resolve without the stored row (``count[1]``) runs the matching again eagerly on the same rows, in sub-batches of
+        pairs whose :meth:`coarse_batch_bytes` fits ``budget`` (None: all at once)"""
         V, dev = fc0.shape[0], fc0.device
         L0, L1 = hw0_c[0] * hw0_c[1], hw1_c[0] * hw1_c[1]
         # ---- coarse transformer.  linear: self = one two-stream launch, cross = two one-stream launches (sequential semantics);
@@ -350,11 +431,44 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             x0, x1 = self._coarse_linear(Wb["coarse"], fc0, fc1, fc1.shape[0] == 1 and V > 1, V, L0, L1, masks)
 
         # ---- coarse matching between the two grids -------------------------------------------------------------------------
+        def match(y0, y1, mk, want_conf=True):
+            return self._match(Wb["bin_score"], y0, y1, mk, hw0_c, hw1_c, scale, want_conf)
+        raw = match(x0, x1, masks, not lazy)
+        # the detector reads the matches on the host right after: one sync here (the count and the lazy form's tie flag in one copy)
+        K, tie = raw["count"][:2].tolist()
+        if lazy and tie:
+            self.lazy_reruns += 1
+            n = V
+            if budget is not None:                         # the largest sub-batch within the budget, one pair at the least
+                while n > 1 and self.coarse_batch_bytes(n, hw0_c, hw1_c, False) > budget:
+                    n -= 1
+            parts = []
+            for p in range(0, V, n):                       # ascending (b, i) inside a sub-batch: pair order is the full call's order
+                sub = match(x0[p:p + n], x1[p:p + n], None if masks is None else (masks[0][p:p + n], masks[1][p:p + n]))
+                parts.append(self._lists(sub, int(sub["count"][0].item()), p))
+            lists = tuple(torch.cat([q[k] for q in parts], 0) for k in range(8))
+        else:
+            lists = self._lists(raw, K, 0)
+        conf = raw["conf"]
+        if lazy:
+            conf = LazyConfMatrix(lambda y0, y1, mk: match(y0, y1, mk)["conf"], x0, x1, masks, torch.cuda.current_stream(dev))
+        b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0c, mk1c = lists
+        if s0 is not None:                                 # get_coarse_match: cell * (scale * scale0[b_ids]); scale = 8 is a power of two
+            mk0c = mk0c * s0[b_ids]
+            mk1c = mk1c * (s1[b_ids] if s1.shape[0] > 1 else s1)
+        return x0, x1, conf, b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0c, mk1c
+
+    def _match(self, bin_score, x0, x1, masks, hw0_c, hw1_c, scale, want_conf):
+        """one coarse-matching call on the final rows ``x0 [V, L0, 256]``, ``x1 [V, L1, 256]`` (``masks``: None or the flattened pair) ->
+        the entry point's output buffers of capacity ``V * L0`` and ``count`` (int32 ``[4]`` on the device: the number of matches and,
+        without ``want_conf``, the tie flag); ``conf`` is ``None`` without ``want_conf`` (dual softmax only: the lazy form)"""
+        call, P, S = hip.call, hip.ptr, hip.stream_handle()
+        V, L0, L1, dev = x0.shape[0], x0.shape[1], x1.shape[1], x0.device
         mc = self.config["match_coarse"]
         ii = torch.arange(L0, device=dev)
         pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
         cap = V * L0
-        conf = torch.empty(V, L0, L1, device=dev)
+        conf = torch.empty(V, L0, L1, device=dev) if want_conf else None
         ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
         cws = torch.empty(ws_floats(V, L0, L1), device=dev)
         ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
@@ -366,19 +480,22 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
         sfx = "" if masks is None else "_masked"
         if self.sinkhorn:
-            call("ophip_coarse_match_2d_sinkhorn" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], Wb["bin_score"],
+            call("ophip_coarse_match_2d_sinkhorn" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], bin_score,
                  int(mc["skh_iters"]), 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws),
                  *outs, *mk, S)
         else:
             call("ophip_coarse_match_2d" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]),
                  float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, *mk, S)
-        K = int(count[0].item())                           # the detector reads the matches on the host right after: one sync here
-        b_ids = ids[0][:K]
-        mk0c, mk1c = mk0[:K, :2].contiguous(), mk1c[:K].contiguous()
-        if s0 is not None:                                 # get_coarse_match: cell * (scale * scale0[b_ids]); scale = 8 is a power of two
-            mk0c = mk0c * s0[b_ids]
-            mk1c = mk1c * (s1[b_ids] if s1.shape[0] > 1 else s1)
-        return x0, x1, conf, b_ids, ids[1][:K], ids[2][:K], ids[3][:K], gt_mask[:K], mconf[:K], mk0c, mk1c
+        return {"conf": conf, "ids": ids, "mconf": mconf, "mk0": mk0, "mk1c": mk1c, "gt_mask": gt_mask, "count": count}
+
+    @staticmethod
+    def _lists(raw, K, first_pair):
+        """the K matches of one :meth:`_match` call, ``b_ids`` counted from ``first_pair`` -> ``b_ids, i_ids, j_ids, m_bids, gt_mask,
+        mconf, mkpts0_c, mkpts1_c`` (the keypoints before the image scales)"""
+        ids = raw["ids"]
+        b_ids, m_bids = (ids[0][:K], ids[3][:K]) if first_pair == 0 else (ids[0][:K] + first_pair, ids[3][:K] + first_pair)
+        return (b_ids, ids[1][:K], ids[2][:K], m_bids, raw["gt_mask"][:K], raw["mconf"][:K], raw["mk0"][:K, :2].contiguous(),
+                raw["mk1c"][:K].contiguous())
 
     def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug,
               b_ids1=None, scale_ids=None):

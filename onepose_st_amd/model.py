@@ -34,6 +34,7 @@ from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .config import encoder_layer_names, validate_config
 from .hip import bstride
+from .lazy_conf import LazyConfMatrixBase
 from .params import EncoderParams, load_matcher_checkpoint
 from .rows import rows_encoder_layer
 
@@ -818,72 +819,38 @@ class OnePosePlus_model(nn.Module):
         return pend
 
 
-class LazyConfMatrix:
+class LazyConfMatrix(LazyConfMatrixBase):
     """``data["conf_matrix"]`` of the lazy form (``config["hip_conf_matrix"] = "lazy"``): the N x M dual-softmax matrix is not stored
     by the frame; this object keeps the encoder's final rows and computes it on first use -- same kernels, same bits as the eager
     form (``ophip_coarse_match_conf`` with a conf buffer).  ``shape`` / ``dtype`` / ``device`` answer without materialising; indexing,
-    attribute access (``.max``, ``.cpu`` ...) and ``torch.*`` functions materialise first (``__torch_function__``).
-    Reference: ``utils/coarse_matching.py:115``; its readers at inference time: none (``inference.py:179-180``)."""
+    attribute access (``.max``, ``.cpu`` ...) and ``torch.*`` functions materialise first (``lazy_conf.LazyConfMatrixBase``, shared with
+    the LoFTR matcher).  Reference: ``utils/coarse_matching.py:115``; its readers at inference time: none (``inference.py:179-180``)."""
 
     def __init__(self, feat3d, feat2d, temperature, nsplit, stream, query_mask=None):
+        super().__init__((feat3d.shape[0], feat3d.shape[1], feat2d.shape[1]), feat3d.device)
         self._f3, self._f2, self._temp, self._nsplit, self._stream, self._qmask = feat3d, feat2d, temperature, nsplit, stream, query_mask
-        self._t = None
-        self.shape = torch.Size((feat3d.shape[0], feat3d.shape[1], feat2d.shape[1]))
-        self.dtype, self.device = torch.float32, feat3d.device
 
-    def materialize(self) -> torch.Tensor:
-        if self._t is None:
-            B, N, M = self.shape
-            dev = self.device
-            cur = torch.cuda.current_stream(dev)
-            cur.wait_stream(self._stream)             # the frame's encoder has produced the rows
-            conf = torch.empty(B, N, M, device=dev, dtype=torch.float32)
-            ws = torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev, dtype=torch.float32)
-            cap = B * N
-            ids = torch.empty(3 * cap, dtype=torch.int64, device=dev)
-            fl = torch.empty(6 * cap + 3, dtype=torch.float32, device=dev)
-            cnt = torch.zeros(4, dtype=torch.int32, device=dev)
-            P = hip.ptr
-            args = (P(self._f3), P(self._f2), P(fl[:3]), 0, B, N, M, M, self._temp, 0.5, 0, 1.0,
-                    P(conf), P(ws), P(ids[:cap], torch.int64), P(ids[cap:2 * cap], torch.int64), P(ids[2 * cap:], torch.int64),
-                    P(fl[3:3 + cap]), P(fl[3 + cap:3 + 4 * cap]), P(fl[3 + 4 * cap:3 + 6 * cap]), None, None, P(cnt, torch.int32), self._nsplit)
-            if self._qmask is None:
-                hip.call("ophip_coarse_match_conf", *args, hip.stream_handle())
-            else:
-                hip.call("ophip_coarse_match_masked", *args, 1, P(self._qmask, torch.uint8), None, hip.stream_handle())
-            self._t = conf
-            self._f3 = self._f2 = None
-        return self._t
-
-    def size(self, dim=None):
-        return self.shape if dim is None else self.shape[dim]
-
-    def dim(self):
-        return 3
-
-    def __len__(self):
-        return self.shape[0]
-
-    def __getitem__(self, idx):
-        return self.materialize()[idx]
-
-    def __getattr__(self, name):                      # anything a tensor has and this object does not: materialise, then delegate
-        if name.startswith("_"):
-            raise AttributeError(name)
-        return getattr(self.materialize(), name)
-
-    def __repr__(self):
-        return f"LazyConfMatrix(shape={tuple(self.shape)}, materialised={self._t is not None})"
-
-    @classmethod
-    def __torch_function__(cls, func, types, args=(), kwargs=None):
-        def conv(a):
-            if isinstance(a, LazyConfMatrix):
-                return a.materialize()
-            if isinstance(a, (list, tuple)):
-                return type(a)(conv(x) for x in a)
-            return a
-        return func(*conv(tuple(args)), **{k: conv(v) for k, v in (kwargs or {}).items()})
+    def _compute(self) -> torch.Tensor:
+        B, N, M = self.shape
+        dev = self.device
+        cur = torch.cuda.current_stream(dev)
+        cur.wait_stream(self._stream)             # the frame's encoder has produced the rows
+        conf = torch.empty(B, N, M, device=dev, dtype=torch.float32)
+        ws = torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev, dtype=torch.float32)
+        cap = B * N
+        ids = torch.empty(3 * cap, dtype=torch.int64, device=dev)
+        fl = torch.empty(6 * cap + 3, dtype=torch.float32, device=dev)
+        cnt = torch.zeros(4, dtype=torch.int32, device=dev)
+        P = hip.ptr
+        args = (P(self._f3), P(self._f2), P(fl[:3]), 0, B, N, M, M, self._temp, 0.5, 0, 1.0,
+                P(conf), P(ws), P(ids[:cap], torch.int64), P(ids[cap:2 * cap], torch.int64), P(ids[2 * cap:], torch.int64),
+                P(fl[3:3 + cap]), P(fl[3 + cap:3 + 4 * cap]), P(fl[3 + 4 * cap:3 + 6 * cap]), None, None, P(cnt, torch.int32), self._nsplit)
+        if self._qmask is None:
+            hip.call("ophip_coarse_match_conf", *args, hip.stream_handle())
+        else:
+            hip.call("ophip_coarse_match_masked", *args, 1, P(self._qmask, torch.uint8), None, hip.stream_handle())
+        self._f3 = self._f2 = None
+        return conf
 
 
 def _result_views(blob, cap):

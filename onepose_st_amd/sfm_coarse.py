@@ -176,6 +176,8 @@ def match_pairs(matcher, images, pairs, max_batch: int = 16) -> dict:
     groups = OrderedDict()                                     # (size0, size1) -> pair indices, in first-appearance order
     for p, (a, b) in enumerate(pairs):
         groups.setdefault((tuple(images[a][0].shape[2:]), tuple(images[b][0].shape[2:])), []).append(p)
+    # only the match lists leave this function: a dual-softmax matcher need not store conf_matrix (sinkhorn's entry point requires it)
+    kw = {"conf_matrix": "lazy"} if not getattr(matcher, "sinkhorn", False) else {}
     calls = []
     pair_counts = torch.zeros(P, dtype=torch.int64, device=dev)
     T = 0
@@ -187,7 +189,7 @@ def match_pairs(matcher, images, pairs, max_batch: int = 16) -> dict:
                     "image1": torch.cat([images[pairs[p][1]][0] for p in ps], 0),
                     "scale0": torch.cat([images[pairs[p][0]][1] for p in ps], 0).contiguous(),
                     "scale1": torch.cat([images[pairs[p][1]][1] for p in ps], 0).contiguous()}
-            matcher(data)
+            matcher(data, **kw)
             b_ids = data["b_ids"]
             K = b_ids.shape[0]                                 # the matcher read its count on the host
             counts = torch.zeros(V, dtype=torch.int64, device=dev).index_add_(0, b_ids, torch.ones_like(b_ids))
