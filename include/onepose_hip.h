@@ -8,7 +8,12 @@
  *   - every pointer is a DEVICE pointer (HBM) unless it says "host"; plain pointers and sizes only
  *   - float = IEEE f32, ids = int64 (torch.long), all tensors dense row-major in the stated shape
  *   - `stream` is a hipStream_t (NULL = default stream); calls only enqueue work, never synchronise,
- *     never allocate: callers pass workspaces sized by the *_workspace_floats() helpers
+ *     never allocate: callers pass workspaces sized by the *_workspace_floats() / *_workspace_bytes() helpers
+ *   - workspace contract: an entry point writes nothing outside the buffers it is given at their declared sizes, and reads no
+ *     workspace byte that it (or the call its comment names as the producer of carried state) has not written: a workspace may
+ *     hold anything on entry, NaN included.  Every workspace has a stated alignment (16 bytes unless its comment says 256); the
+ *     helpers' sizes already pay for the sub-regions that the code rounds up to 64 or 256 bytes from ANY base of that alignment,
+ *     so a caller may sub-allocate.  A misaligned workspace is refused with -1 before anything is launched.
  *   - return 0 on success; -1 invalid argument; otherwise the hipError_t.  ophip_last_error() (host
  *     string, thread local) describes the last failure.
  *   - packed weight blocks are produced by onepose_st_amd/packing.py (layout documented there and in
@@ -78,7 +83,8 @@ int ophip_kpt_encode(const float* keypoints3d, long long kpts_bstride, const flo
 /* a4-a6 -- one LoFTREncoderLayer applied to both streams of the coarse encoder (d_model 256, 8 heads)
  * (loftr_module/transformer.py:65-94 and :146-159, loftr_module/linear_attention.py:29-61).
  * x3d [B][L3d][256], x2d [B][L2d][256] -> y3d, y2d (must not alias the inputs: both streams of a layer read
- * the pre-update tensors).  is_cross: 0 = "self", 1 = "cross".  workspace: ophip_encoder_workspace_floats(). */
+ * the pre-update tensors).  is_cross: 0 = "self", 1 = "cross".  workspace: ophip_encoder_workspace_floats() floats, 16-byte
+ * aligned (the K^T V slabs and their sum are read and written as float4). */
 size_t ophip_encoder_workspace_floats(int B, int L3d, int L2d);
 int ophip_encoder_layer(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
                         const float* wpack, int is_cross, float* workspace, void* stream);
@@ -100,7 +106,8 @@ int ophip_encoder_layer_bf16(const float* x3d, const float* x2d, float* y3d, flo
  * workgroups of eight waves (one workgroup per CU, two waves per SIMD; csrc/encoder_x3w8.hip), the layer's weights pre-ordered
  * into one linear stream per wave (packing.pack_coarse_layer_x3w8, ophip_encoder_x3w8_wpack_bytes() bytes, 16-byte aligned),
  * epilogues overlapped with the next GEMM inside a wave.  Arguments and layer chaining (wpack_next / kv_from_prev / slot) as
- * ophip_encoder_layer_bf16; workspace: ophip_encoder_x3w8_workspace_bytes() bytes.
+ * ophip_encoder_layer_bf16; workspace: ophip_encoder_x3w8_workspace_bytes() bytes, 16-byte aligned (two slab sets read and written
+ * as float4, then the summed K^T V | Ksum blocks, which the code rounds up to the next 256-byte boundary: the helper's + 256 pays for it).
  * Replaces transformer.py:65-94 + linear_attention.py:29-61. */
 size_t ophip_encoder_x3w8_workspace_bytes(int B, int L3d, int L2d);
 size_t ophip_encoder_x3w8_wpack_bytes(void);
@@ -156,7 +163,13 @@ int ophip_encoder_kv_first_x3w8(const float* x3d, const float* x2d, int B, int L
  * (row, column tile) the best candidate above the threshold and the column maxima -- what the selection consumes.  Indices and
  * mconf are bit-identical to the eager form.  `count` must then point at TWO ints: count[1] is set to 1 when a row's maximum is
  * tied exactly between columns and the first of them fails the mutual test (resolving that needs the stored row): the caller
- * re-runs the frame with a conf buffer.  count[1] = 0 otherwise. */
+ * re-runs the frame with a conf buffer.  count[1] = 0 otherwise.
+ *
+ * workspace: ophip_coarse_workspace_floats(B, N, M) floats, 16-byte aligned, in every entry point of this stage (ophip_coarse_match*,
+ * ophip_coarse_frag_planes); the fragment planes inside it start at the next 64-byte boundary, which the helper's size pays for.
+ * The match lists (b_ids, i_ids, j_ids, mconf, mkpts3d, mkpts_c, m_bids, gt_mask) have B * N entries each; entries from *count on are
+ * not written.  A consumer that takes the lists with a capacity (max_matches of ophip_fine_refine*) is given buffers of max_matches
+ * entries: it may READ entries at and past *count and ignores them, so those must be readable memory, not meaningful values. */
 size_t ophip_coarse_workspace_floats(int B, int N, int M);
 /* bf16 modes: the similarity kernel reads its operands as (hi, lo) bf16 MFMA fragments that a first kernel derives from
  * feat3d / feat2d.  A producer that writes them itself (ophip_encoder_layer_x3w8_frag) gets their place inside the workspace
@@ -188,7 +201,8 @@ int ophip_coarse_match_select(const float* feat3d, const float* feat2d, const fl
  * feat_f: fine feature map addressed by strides in floats (NCHW or channels-last), hf x wf.
  * desc3d_f [B][128][N] (strides ds_b, ds_c).  Matches come from ophip_coarse_match (device count, no host sync);
  * the grid covers max_matches, surplus workgroups exit.  *count is clamped to max_matches in every variant (f32, bf16, _scaled): a count
- * above the capacity refines rows 0 .. max_matches - 1 and writes no output row >= max_matches.  expec_f [.][3] = (x, y, std), mkpts_f [.][2].
+ * above the capacity refines rows 0 .. max_matches - 1 and writes no output row >= max_matches.  The id lists (b_ids, i_ids, j_ids) and
+ * mkpts_c hold max_matches entries: entries at and past *count are read and ignored.  expec_f [.][3] = (x, y, std), mkpts_f [.][2].
  * dbg_win [.][25][128] / dbg_f3 [.][128] (both or neither; NULL in production) receive the fine-encoder outputs. */
 int ophip_fine_refine(const float* feat_f, long long fs_b, long long fs_c, long long fs_y, long long fs_x, int hf, int wf,
                       const float* desc3d_f, long long ds_b, long long ds_c,
@@ -248,7 +262,8 @@ int ophip_fine_refine_bf16_scaled(const float* feat_f, long long fs_b, long long
  * rows a1-a11 on three streams (input kernels | encoder + coarse matching | selection + fine stage) and the read-back of the
  * result block, issued from C (csrc/frame.hip) instead of ~27 separate calls from the host language.
  * ophip_frame_desc: sizes, scalars and packed-weight pointers of the model (fixed per model and input shape).
- * ophip_frame_layout(): byte offsets of every intermediate and output inside ONE device block of `total` bytes
+ * ophip_frame_layout(): byte offsets of every intermediate and output inside ONE device block of `total` bytes, 256-byte aligned
+ *   (every offset is a multiple of 256, and the stages' own alignments are met through that; a misaligned block is refused)
  *   (transpose_fine: the fine map arrives NCHW and needs the channels-last copy; external_x3d: 1 = the keypoint encoding is
  *   supplied by the caller -- a cached object block -- and stays read-only; 2 = so are the first encoder layer's 3D rows, see
  *   ophip_object_cache below).
@@ -320,7 +335,8 @@ int ophip_frame_order_after_fine(void* compute_stream);
  * (ophip_frame_enqueue_object) runs layer 0 on the 2D stream alone and layer 1 with the cached rows / block; it is BIT-IDENTICAL to a
  * frame without the cache (a workgroup's arithmetic does not depend on the others of its launch; the K^T V sum adds a stream's slabs in
  * the same fixed order).  Needs n_coarse >= 2 and a first layer of kind "self" for y3d0 / kv1 (else pass them NULL: depth 1).
- * workspace of ophip_encoder_object_x3w8: ophip_encoder_x3w8_workspace_bytes(Bo, N, 1) bytes of scratch.  masked_frames: 1 = build the
+ * workspace of ophip_encoder_object_x3w8: ophip_encoder_x3w8_workspace_bytes(Bo, N, 1) bytes of scratch, 16-byte aligned like kv1 (its
+ * fragments are read as 16-byte vectors; a batch stride kv1_bs keeps that alignment).  masked_frames: 1 = build the
  * entry for frames that carry a query_mask (they run both streams through the masked instantiation of the layer kernel, whose rounding
  * need not equal the plain one's: an entry built the same way keeps the bit-identity); a caller with both kinds of frames keeps two entries.
  * ready: a hipEvent_t recorded behind the kernels that wrote the buffers, or NULL when they are complete; ophip_frame_enqueue_object makes
@@ -412,7 +428,7 @@ int ophip_coarse_match_2d_masked(const float* feat0, const float* feat1, const f
  *   prefilter != 0: a row whose argmax over j (dustbin included) is the dustbin column, and a column whose argmax over i is the dustbin
  *     row, are zeroed.  argmax takes the first maximum and the dustbin is last: it wins only when its exp'd f32 value is STRICTLY greater.
  *   Then the selection of ophip_coarse_match_2d (threshold, all-sides border, mutual nearest, first-j ties, ordered compaction), same
- *   outputs.  workspace: ophip_coarse_sinkhorn_workspace_floats(B, L0, L1) floats.  Deterministic.  On return the workspace holds
+ *   outputs.  workspace: ophip_coarse_sinkhorn_workspace_floats(B, L0, L1) floats, 16-byte aligned.  Deterministic.  On return the workspace holds
  *   the dual potentials from float ophip_coarse_workspace_floats(B, L0, L1) on, rounded up to a 64-byte boundary: u [B][U] then
  *   v [B][V], U = L0 + 1 and V = L1 + 1 rounded up to multiples of 4, the dustbin's last (conf = exp(((S + u_i) + v_j) - norm)). */
 size_t ophip_coarse_sinkhorn_workspace_floats(int B, int L0, int L1);
@@ -480,7 +496,8 @@ int ophip_sample_features(const ophip_sample_job* jobs, int n_jobs, void* stream
  * msg = softmax(Q K^T / sqrt(32)) V per head (8 heads of 32), then the same merge / LayerNorm / MLP / LayerNorm / residual tail as the
  * linear layer.  Same stream wiring and in-place rule as ophip_encoder_layer; wpack is the f32 layer block of ophip_encoder_layer.
  * The attention runs on split-bf16 MFMA (hi*hi + hi*lo + lo*hi, f32 accumulate) with an online softmax; the projections and the tail on
- * the exact-f32 MFMA tiles.  workspace: ophip_encoder_full_workspace_bytes() bytes.  No mask variant: the reference's masked full
+ * the exact-f32 MFMA tiles.  workspace: ophip_encoder_full_workspace_bytes() bytes, 16-byte aligned (four planes of whole 1 KiB rows,
+ * read and written as float4).  No mask variant: the reference's masked full
  * attention raises (linear_attention.py:85 reads q_mask[:, :, None, None] of a None q_mask in the 3D stream's cross layer).
  * ophip_full_attention_h8d32: the attention step alone, q [B][L][256], k, v [B][S][256] -> msg [B][L][256]. */
 size_t ophip_encoder_full_workspace_bytes(int B, int L3d, int L2d);
@@ -493,7 +510,7 @@ int ophip_full_attention_h8d32(const float* q, const float* k, const float* v, i
  * layer of x [B][L][256] (batch stride x_bstride floats) against src [B][S][256] (src_bstride) -- Q from x, K and V from src, the kernels
  * and arithmetic of ophip_encoder_layer_full_x3.  A batch stride of 0 makes that input one image shared by every batch element (one query
  * frame against B views); its projections are computed once.  src == x with equal strides and S == L is the self layer.  y must not alias
- * x or src.  wpack: the f32 layer block.  workspace: ophip_encoder_full_stream_workspace_bytes(B, L, S) bytes. */
+ * x or src.  wpack: the f32 layer block.  workspace: ophip_encoder_full_stream_workspace_bytes(B, L, S) bytes, 16-byte aligned. */
 size_t ophip_encoder_full_stream_workspace_bytes(int B, int L, int S);
 int ophip_encoder_layer_full_x3_stream(const float* x, long long x_bstride, const float* src, long long src_bstride, float* y, int B, int L,
                                        int S, const float* wpack, void* workspace, void* stream);

@@ -1342,6 +1342,7 @@ int coarse_impl(int parts, int border_mode, int wi, double temp_eps,
                 const unsigned char* fill0 = nullptr, const unsigned char* fill1 = nullptr) {
     if (!feat3d || !feat2d || !keypoints3d || !workspace || !b_ids || !i_ids || !j_ids || !mconf || !mkpts3d || !mkpts_c || !count)
         return ophip_bad_arg(__func__, "null pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return ophip_bad_arg(__func__, "workspace must be 16-byte aligned");
     const bool lazy = conf == nullptr;               // conf_matrix not requested: nothing N x M is stored (bf16 modes)
     if (B < 1 || N < 1 || M < 1 || wc < 1 || M % wc != 0) return ophip_bad_arg(__func__, "bad sizes (need M == hc * wc)");
     if (border_mode == 1 && (wi < 1 || N % wi != 0)) return ophip_bad_arg(__func__, "bad sizes (need N == h0c * w0c)");
@@ -1509,6 +1510,7 @@ int ophip_coarse_select_2d(const float* conf, int nspan, const float* points0, l
 
 extern "C" int ophip_coarse_frag_planes(float* workspace, int B, int N, int M, void** planes3d, void** planes2d) {
     if (!workspace || !planes3d || !planes2d || B < 1 || N < 1 || M < 1) return ophip_bad_arg(__func__, "bad argument");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return ophip_bad_arg(__func__, "workspace must be 16-byte aligned");
     char *a, *b;
     frag_plane_ptrs(workspace, B, N, M, &a, &b);
     *planes3d = a; *planes2d = b;

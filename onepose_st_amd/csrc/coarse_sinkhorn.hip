@@ -387,6 +387,7 @@ int sinkhorn_impl(const float* feat0, const float* feat1, const float* points0, 
                   const unsigned char* mask0, const unsigned char* mask1) {
     if (!feat0 || !feat1 || !points0 || !conf || !workspace || !b_ids || !i_ids || !j_ids || !mconf || !mkpts0 || !mkpts1_c || !count)
         return ophip_bad_arg(__func__, "null pointer (conf is required)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return ophip_bad_arg(__func__, "workspace must be 16-byte aligned");
     if (B < 1 || L0 < 1 || L1 < 1 || w0c < 1 || w1c < 1 || L0 % w0c != 0 || L1 % w1c != 0)
         return ophip_bad_arg(__func__, "bad sizes (need L0 == h0c * w0c, L1 == h1c * w1c)");
     if (iters < 0) return ophip_bad_arg(__func__, "iters must be >= 0");

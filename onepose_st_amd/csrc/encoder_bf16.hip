@@ -456,6 +456,7 @@ int layer_bf16(const float* x3d, const float* x2d, float* y3d, float* y2d, int B
                const void* wpack, const void* wpack_next, int nsplit, int is_cross, int kv_from_prev, int slot,
                void* workspace, const unsigned char* mask2d, void* stream_) {
     if (!x3d || !x2d || !y3d || !y2d || !wpack || !workspace) return ophip_bad_arg(__func__, "null pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return ophip_bad_arg(__func__, "workspace must be 256-byte aligned");
     if (B < 1 || L3d < 1 || L2d < 1) return ophip_bad_arg(__func__, "B, L3d, L2d must be >= 1");
     if (nsplit != 1) return ophip_bad_arg(__func__, "nsplit must be 1: this is the plain-bf16 mode's layer (split-bf16: ophip_encoder_layer_x3w8)");
     if (slot != 0 && slot != 1) return ophip_bad_arg(__func__, "slot must be 0 or 1");

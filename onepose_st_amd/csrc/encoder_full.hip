@@ -303,6 +303,7 @@ extern "C" size_t ophip_encoder_full_workspace_bytes(int B, int L3d, int L2d) {
 extern "C" int ophip_encoder_layer_full_x3(const float* x3d, const float* x2d, float* y3d, float* y2d, int B, int L3d, int L2d,
                                            const float* wpack, int is_cross, void* workspace, void* stream_) {
     if (!x3d || !x2d || !y3d || !y2d || !wpack || !workspace) return ophip_bad_arg(__func__, "null pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return ophip_bad_arg(__func__, "workspace must be 16-byte aligned");
     if (B < 1 || L3d < 1 || L2d < 1) return ophip_bad_arg(__func__, "B, L3d, L2d must be >= 1");
     if (x3d == y3d || x2d == y2d) return ophip_bad_arg(__func__, "in-place layer is not supported (cross layers read the pre-update streams)");
     hipStream_t stream = (hipStream_t)stream_;
@@ -384,6 +385,7 @@ extern "C" size_t ophip_encoder_full_stream_workspace_bytes(int B, int L, int S)
 extern "C" int ophip_encoder_layer_full_x3_stream(const float* x, long long x_bstride, const float* src, long long src_bstride, float* y,
                                                   int B, int L, int S, const float* wpack, void* workspace, void* stream_) {
     if (!x || !src || !y || !wpack || !workspace) return ophip_bad_arg(__func__, "null pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return ophip_bad_arg(__func__, "workspace must be 16-byte aligned");
     if (B < 1 || L < 1 || S < 1) return ophip_bad_arg(__func__, "B, L, S must be >= 1");
     if (y == x || y == src) return ophip_bad_arg(__func__, "in-place layer is not supported (y must not alias x or src)");
     if ((x_bstride != 0 && x_bstride < (long long)L * C) || (src_bstride != 0 && src_bstride < (long long)S * C) || x_bstride % 4 != 0 ||

@@ -498,6 +498,7 @@ int layer_x3w8(const float* x3d, const float* x2d, float* y3d, float* y2d, int B
     const bool r3 = run & 1, r2 = run & 2;
     if ((!sum_only && ((r3 && !x3d) || (r2 && !x2d))) || !wpack || !workspace || (!only_kv && !sum_only && ((r3 && !y3d) || (r2 && !y2d))))
         return ophip_bad_arg(__func__, "null pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return ophip_bad_arg(__func__, "workspace must be 16-byte aligned");
     if (is_cross && run != 3 && kv_mode == 0 && !sum_only && (!x3d || !x2d)) return ophip_bad_arg(__func__, "null pointer (a cross layer reads both streams)");
     if (B < 1 || L3d < 1 || L2d < 1) return ophip_bad_arg(__func__, "B, L3d, L2d must be >= 1");
     if (slot != 0 && slot != 1) return ophip_bad_arg(__func__, "slot must be 0 or 1");

@@ -194,6 +194,7 @@ int frame_enqueue_impl(const ophip_frame_desc* d, const ophip_frame_layout_t* L,
     if (!d || !L || !blob_ || !feat_c || !feat_f || !kpts || !desc_c || !desc_f || !host_dst || !s_fine_ || !s_copy_ || !slot_out)
         return ophip_bad_arg(__func__, "null pointer");
     if (host_bytes < 16 || host_bytes > L->result_bytes) return ophip_bad_arg(__func__, "host_bytes");
+    if (reinterpret_cast<uintptr_t>(blob_) & 255) return ophip_bad_arg(__func__, "block must be 256-byte aligned");
     const bool deep = obj && obj->y3d0;                      // the first layer's 3D rows and layer 1's 3D-source block come from the cache
     const float* x3d_external = (obj && !deep) ? obj->x3d : nullptr;
     const long long x3d_ext_bs = obj ? obj->x3d_bs : -1;

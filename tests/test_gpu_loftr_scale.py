@@ -433,18 +433,24 @@ def test_sinkhorn_stage_at_size(dev, name, iters, masked):
     for prefilter in (0, 1):
         tag = f"{name} iters={iters} prefilter={prefilter} masked={masked}"
         out = _skh(dev, d0, d1, hw0[1], hw1[1], iters, prefilter, masks)
-        conf64, assign = lmo.sinkhorn_conf(f0d, f1d, 1.0, iters, prefilter, m0d, m1d)
-        ref = lmo.get_coarse_match(conf64, hw0, hw1, (8 * hw0[0], 8 * hw0[1]), THR, BD, m0d, m1d)
-        ref = {k: (v.cpu() if torch.is_tensor(v) and k != "conf_matrix" else v) for k, v in ref.items()}
-        near_r, near_c = tgls._near(assign, conf64, THR)
-        keep = ~(near_r[:, :, None] | near_c[:, None, :])
-        _close_dev(out["conf"], conf64, 1e-3 if iters == 0 else 0.0, 1e-4, f"{tag}: conf_matrix", keep=keep)
-        nr, nc = near_r.cpu(), near_c.cpu()
-        K, _ = _against_ref(out, ref, tag, lambda b, i, j: bool(nr[b, i] or nc[b, j]), rtol=1e-3 if iters == 0 else 1e-4, conf=False)
+        K = _check_sinkhorn(out, f0d, f1d, hw0, hw1, iters, prefilter, m0d, m1d, tag)
         assert K >= 50 * B, "the planted matches must survive: the comparison would be vacuous"
-        del conf64, assign, keep
     if masked:
         assert torch.equal(masks[0].cpu(), m0.flatten(1)) and torch.equal(masks[1].cpu(), m1.flatten(1))
+
+
+def _check_sinkhorn(out, f0d, f1d, hw0, hw1, iters, prefilter, m0d, m1d, tag, bin_score=1.0):
+    """one Sinkhorn stage result (``_skh``'s dict) against the float64 oracle on the device (features float64, masks or None);
+    -> the reference's match count"""
+    conf64, assign = lmo.sinkhorn_conf(f0d, f1d, bin_score, iters, prefilter, m0d, m1d)
+    ref = lmo.get_coarse_match(conf64, hw0, hw1, (8 * hw0[0], 8 * hw0[1]), THR, BD, m0d, m1d)
+    ref = {k: (v.cpu() if torch.is_tensor(v) and k != "conf_matrix" else v) for k, v in ref.items()}
+    near_r, near_c = tgls._near(assign, conf64, THR)
+    keep = ~(near_r[:, :, None] | near_c[:, None, :])
+    _close_dev(out["conf"], conf64, 1e-3 if iters == 0 else 0.0, 1e-4, f"{tag}: conf_matrix", keep=keep)
+    nr, nc = near_r.cpu(), near_c.cpu()
+    K, _ = _against_ref(out, ref, tag, lambda b, i, j: bool(nr[b, i] or nc[b, j]), rtol=1e-3 if iters == 0 else 1e-4, conf=False)
+    return K
 
 
 # ------------------------------------------------------------------------------------------------

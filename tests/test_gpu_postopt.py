@@ -48,7 +48,11 @@ def rel(a, b):
 
 def test_prep_and_first_evaluation_match_the_oracle(dev, seeds):
     data = seeds[0]
-    out = refine(data, dev, max_steps=1, return_residuals=True)
+    check_first_evaluation(refine(data, dev, max_steps=1, return_residuals=True), data)
+
+
+def check_first_evaluation(out, data):
+    """``out``: a one-step run with residuals; the prep kernel's fold and the first evaluation against the oracle"""
     p0, p1, idx = po.expand_inputs(data)
     want = po.depth_residual(data["depth"][idx], p0, p1, data["intrinsic0"], data["intrinsic1"], data["mkpts0_c"], data["mkpts1_f"])
     err = (out["residuals"].cpu() - want).abs().max().item()
