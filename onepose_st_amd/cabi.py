@@ -154,6 +154,7 @@ class Binding:
         self.exported_symbols = tuple(self.signatures)
         self.handle = None
         self._params = {name: proto.params for name, proto in self.header.prototypes.items()}
+        self._names = {name: tuple(n for _, n in params) for name, params in self._params.items()}
         self._last_error = f"{prefix}_last_error"
 
     @classmethod
@@ -205,6 +206,21 @@ class Binding:
         params = self._params[name]
         if len(args) != len(params):
             raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(n for _, n in params)}), {len(args)} given")
+
+    def order(self, name: str, **named) -> tuple:
+        """The values of ``named`` in the order of the header's parameter names: two neighbouring ``float*`` cannot change places on the
+        way to C.  ``TypeError`` names every missing and every unknown parameter.  Needs no loaded library."""
+        names = self._names[name]
+        if len(named) == len(names):
+            try:
+                return tuple([named[n] for n in names])
+            except KeyError:
+                pass
+        missing, unknown = [n for n in names if n not in named], [n for n in named if n not in names]
+        raise TypeError(f"{name}: missing {', '.join(missing) or 'nothing'}; unknown {', '.join(unknown) or 'nothing'}")
+
+    def call_named(self, name: str, **named) -> None:
+        self.call(name, *self.order(name, **named))
 
     def call(self, name: str, *args) -> None:
         """Call an entry point that returns a status and raise on failure: -1 (a rejected argument) -> ``ValueError``, any other

@@ -55,12 +55,17 @@ _MIRRORS = {"ophip_sample_job": SampleJob, "ophip_frame_desc": FrameDesc, "ophip
 _BINDING = cabi.Binding.of(__name__, _MIRRORS)
 for _name, _fields in _BINDING.header.structs.items():
     cabi.check_mirror(_MIRRORS[_name], _name, _fields)
-library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
-EXPORTED_SYMBOLS = _BINDING.exported_symbols
+library_path, load, check_arity, call, order = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call, _BINDING.order
+EXPORTED_SYMBOLS, PROTOTYPES = _BINDING.exported_symbols, _BINDING.header.prototypes
 ABI_VERSION = _BINDING.abi_version                                      # what the FrameDesc / FrameLayout mirrors above are written for
 # COARSE_PLANES_READY is or-ed into ophip_coarse_match's nsplit
 SAMPLE_MAX_JOBS, COARSE_PLANES_READY = map(_BINDING.constant, ("SAMPLE_MAX_JOBS", "COARSE_PLANES_READY"))
 NO_CPU_FALLBACK = "the HIP path needs device tensors (no CPU fallback)"     # what every device-loop module says of a CPU tensor
+
+
+def call_named(name: str, **named) -> None:
+    """``call`` with every argument bound by its name in the header (``cabi.Binding.order``)"""
+    call(name, *order(name, **named))          # this module's ``call``: whoever replaces it (a test's spy) sees these calls too
 
 
 def ptr(t: torch.Tensor | None, dtype=torch.float32):

@@ -72,6 +72,7 @@ from . import hip, host_math, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .lazy_conf import LazyConfMatrixBase
+from .matchcall import MatchLists, coarse_match_2d
 from .params import EncoderParams, load_matcher_checkpoint
 from .rows import rows_encoder_layer
 
@@ -435,7 +436,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             return self._match(Wb["bin_score"], y0, y1, mk, hw0_c, hw1_c, scale, want_conf)
         raw = match(x0, x1, masks, not lazy)
         # the detector reads the matches on the host right after: one sync here (the count and the lazy form's tie flag in one copy)
-        K, tie = raw["count"][:2].tolist()
+        K, tie = raw.count[:2].tolist()
         if lazy and tie:
             self.lazy_reruns += 1
             n = V
@@ -445,13 +446,13 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             parts = []
             for p in range(0, V, n):                       # ascending (b, i) inside a sub-batch: pair order is the full call's order
                 sub = match(x0[p:p + n], x1[p:p + n], None if masks is None else (masks[0][p:p + n], masks[1][p:p + n]))
-                parts.append(self._lists(sub, int(sub["count"][0].item()), p))
+                parts.append(self._lists(sub, int(sub.count[0].item()), p))
             lists = tuple(torch.cat([q[k] for q in parts], 0) for k in range(8))
         else:
             lists = self._lists(raw, K, 0)
-        conf = raw["conf"]
+        conf = raw.conf
         if lazy:
-            conf = LazyConfMatrix(lambda y0, y1, mk: match(y0, y1, mk)["conf"], x0, x1, masks, torch.cuda.current_stream(dev))
+            conf = LazyConfMatrix(lambda y0, y1, mk: match(y0, y1, mk).conf, x0, x1, masks, torch.cuda.current_stream(dev))
         b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0c, mk1c = lists
         if s0 is not None:                                 # get_coarse_match: cell * (scale * scale0[b_ids]); scale = 8 is a power of two
             mk0c = mk0c * s0[b_ids]
@@ -462,40 +463,25 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         """one coarse-matching call on the final rows ``x0 [V, L0, 256]``, ``x1 [V, L1, 256]`` (``masks``: None or the flattened pair) ->
         the entry point's output buffers of capacity ``V * L0`` and ``count`` (int32 ``[4]`` on the device: the number of matches and,
         without ``want_conf``, the tie flag); ``conf`` is ``None`` without ``want_conf`` (dual softmax only: the lazy form)"""
-        call, P, S = hip.call, hip.ptr, hip.stream_handle()
-        V, L0, L1, dev = x0.shape[0], x0.shape[1], x1.shape[1], x0.device
+        V, L0, dev = x0.shape[0], x0.shape[1], x0.device
         mc = self.config["match_coarse"]
         ii = torch.arange(L0, device=dev)
         pts0 = torch.stack([(ii % hw0_c[1]).float() * scale, (ii // hw0_c[1]).float() * scale, torch.zeros(L0, device=dev)], 1)[None].contiguous()
-        cap = V * L0
-        conf = torch.empty(V, L0, L1, device=dev) if want_conf else None
-        ws_floats = hip.load().ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else hip.load().ophip_coarse_workspace_floats
-        cws = torch.empty(ws_floats(V, L0, L1), device=dev)
-        ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
-        mconf, mk0, mk1c = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-        gt_mask = torch.empty(cap, dtype=torch.bool, device=dev)
-        count = torch.zeros(4, dtype=torch.int32, device=dev)
-        outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1c), P(ids[3], torch.int64),
-                P(gt_mask, torch.bool), P(count, torch.int32))
-        mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
-        sfx = "" if masks is None else "_masked"
-        if self.sinkhorn:
-            call("ophip_coarse_match_2d_sinkhorn" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], bin_score,
-                 int(mc["skh_iters"]), 1 if mc["skh_prefilter"] else 0, float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws),
-                 *outs, *mk, S)
-        else:
-            call("ophip_coarse_match_2d" + sfx, P(x0), P(x1), P(pts0), 0, V, L0, L1, hw0_c[1], hw1_c[1], float(mc["dsmax_temperature"]),
-                 float(mc["thr"]), int(mc["border_rm"]), float(scale), P(conf), P(cws), *outs, 3, *mk, S)
-        return {"conf": conf, "ids": ids, "mconf": mconf, "mk0": mk0, "mk1c": mk1c, "gt_mask": gt_mask, "count": count}
+        lists = MatchLists.empty(V * L0, dev, conf_shape=(V, L0, x1.shape[1]) if want_conf else None)
+        form = (dict(sinkhorn=(bin_score, int(mc["skh_iters"]), 1 if mc["skh_prefilter"] else 0)) if self.sinkhorn
+                else dict(temperature=mc["dsmax_temperature"]))
+        coarse_match_2d(x0, x1, pts0, w0c=hw0_c[1], w1c=hw1_c[1], thr=mc["thr"], border_rm=mc["border_rm"], scale=scale, lists=lists,
+                        conf=lists.conf, masks=masks, **form)
+        return lists
 
     @staticmethod
     def _lists(raw, K, first_pair):
         """the K matches of one :meth:`_match` call, ``b_ids`` counted from ``first_pair`` -> ``b_ids, i_ids, j_ids, m_bids, gt_mask,
         mconf, mkpts0_c, mkpts1_c`` (the keypoints before the image scales)"""
-        ids = raw["ids"]
-        b_ids, m_bids = (ids[0][:K], ids[3][:K]) if first_pair == 0 else (ids[0][:K] + first_pair, ids[3][:K] + first_pair)
-        return (b_ids, ids[1][:K], ids[2][:K], m_bids, raw["gt_mask"][:K], raw["mconf"][:K], raw["mk0"][:K, :2].contiguous(),
-                raw["mk1c"][:K].contiguous())
+        b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0, mk1c = raw.trim(K)
+        if first_pair:
+            b_ids, m_bids = b_ids + first_pair, m_bids + first_pair
+        return b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0[:, :2].contiguous(), mk1c.contiguous()
 
     def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug,
               b_ids1=None, scale_ids=None):

@@ -35,6 +35,7 @@ from .backbone_hip import HipBackbone, pack_backbone
 from .config import encoder_layer_names, validate_config
 from .hip import bstride
 from .lazy_conf import LazyConfMatrixBase
+from .matchcall import MatchLists, coarse_match, fine_refine
 from .params import EncoderParams, load_matcher_checkpoint
 from .rows import rows_encoder_layer
 
@@ -544,9 +545,7 @@ class OnePosePlus_model(nn.Module):
         """Rows a7 + a8 on the compute stream; sets ``data["conf_matrix"]``.  Returns the stage's buffers (read-only from here on; ``held``: what
         must stay referenced until ``finish()``) and ``select``: with the fine stage on its side stream the single-workgroup select kernel goes there with it (it only feeds that stage
         and the read-back: the next frame's input kernels then run beside it, not behind it) -- ``select(stream)`` launches it; else None."""
-        lib_call, P = hip.call, hip.ptr
         B, N, M, dev, kpts_d, qmask, qscale = fi.B, fi.N, fi.M, fi.dev, fi.kpts_d, fi.qmask, fi.qscale
-        S = ctypes.c_void_p(main.cuda_stream)
         f32, i64 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int64)
         cm = self.config["coarse_matching"]
         cap = B * N
@@ -561,25 +560,16 @@ class OnePosePlus_model(nn.Module):
         mkc = torch.empty(cap, 2, **f32) if fine_on else mk2d
         scale = data["q_hw_i"][0] / fi.hc
         temperature = float(cm["dual_softmax"]["temperature"])
-        cm_args = (P(x3d), P(x2d), P(kpts_d), bstride(kpts_d), B, N, M, fi.wc,
-                   temperature, float(cm["thr"]), int(cm["border_rm"]), float(scale),
-                   P(conf), P(cws), P(b_ids, torch.int64), P(i_ids, torch.int64), P(j_ids, torch.int64),
-                   P(mconf), P(mk3d), P(mkc), P(m_bids, torch.int64), P(gt_mask, torch.bool), P(count, torch.int32),
-                   _NSPLIT[self.precision])
+        lists = MatchLists(b_ids, i_ids, j_ids, mconf, mk3d, mkc, m_bids, gt_mask, count)
         split_select = fine_on and self.overlap_fine
-        padded = qmask is not None or qscale is not None
-        pad_args = (P(qmask, torch.uint8), P(qscale))
-        select = None
+
+        def match(parts, stream):
+            coarse_match(x3d, x2d, kpts_d, wc=fi.wc, temperature=temperature, thr=cm["thr"], border_rm=cm["border_rm"], scale=scale,
+                         nsplit=_NSPLIT[self.precision], lists=lists, conf=conf, workspace=cws, parts=parts, query_mask=qmask,
+                         query_scale=qscale, stream=stream)
         with self.profiler.record_function("LoFTR/coarse-matching/get_coarse_match"):
-            if padded:
-                lib_call("ophip_coarse_match_masked", *cm_args, 1 if split_select else 3, *pad_args, S)
-                if split_select:
-                    select = lambda stream: lib_call("ophip_coarse_match_masked", *cm_args, 2, *pad_args, stream)
-            elif split_select:
-                lib_call("ophip_coarse_match_conf", *cm_args, S)
-                select = lambda stream: lib_call("ophip_coarse_match_select", *cm_args, stream)
-            else:
-                lib_call("ophip_coarse_match", *cm_args, S)
+            match(1 if split_select else 3, main)
+        select = (lambda stream: match(2, stream)) if split_select else None
         data["conf_matrix"] = conf if not lazy else LazyConfMatrix(x3d, x2d, temperature, _NSPLIT[self.precision], main, qmask)
         return dict(blob=blob, b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, mconf=mconf, mk3d=mk3d, mk2d=mk2d, mkc=mkc, count=count, m_bids=m_bids,
                     gt_mask=gt_mask, held=(x3d, x2d, cws, conf)), select
@@ -588,7 +578,6 @@ class OnePosePlus_model(nn.Module):
         """Rows a9-a11 on the coarse stage's buffers ``cb`` (behind the kept-back selection ``select``) and the frame's :class:`PendingFrame`.  With ``hip_overlap_fine`` they run on
         the compute stream's fine stream, behind an event of the coarse stage, and leave the event the next frame's encoder waits for.  The grid
         is sized by the capacity B * N (one match per 3D point at most; surplus workgroups exit on the device-side count): no sync yet."""
-        lib_call, P = hip.call, hip.ptr
         B, N, M, hf, dev, desc, qscale, W = fi.B, fi.N, fi.M, fi.hf, fi.dev, fi.desc_fine_d, fi.qscale, fi.W
         cfg = self.config
         fine_on = bool(cfg["fine_matching"]["enable"])
@@ -604,9 +593,8 @@ class OnePosePlus_model(nn.Module):
         keep = [desc, W, fi.qmask, qscale, ff, *cb["held"]]          # inputs of the side-stream kernels stay referenced until finish()
         expec = dbg_w = dbg_3 = None
         with fine_ctx:
-            S = hip.stream_handle()
             if select is not None:
-                select(S)
+                select(None)                              # on the stream of this context
             if fine_on:
                 cf = cfg["loftr_fine"]
                 expec = torch.empty(cap, 3, **f32)
@@ -622,12 +610,11 @@ class OnePosePlus_model(nn.Module):
                 else:
                     bf = self.precision != "f32"          # the bf16 pipe's kernel takes its operand split (3: split-bf16, 1: plain) as well
                     fine_scale = (cf["window_size"] // 2) * (data["q_hw_i"][0] / hf)
-                    lib_call("ophip_fine_refine" + ("_bf16" if bf else "") + ("_scaled" if qscale is not None else ""), P(ff), *ff_strides, hf, fi.wf,
-                             P(desc), bstride(desc), desc.stride(1),
-                             P(cb["b_ids"], torch.int64), P(cb["i_ids"], torch.int64), P(cb["j_ids"], torch.int64), P(cb["count"], torch.int32), cap,
-                             P(cb["mkc"]), P(W["fine_bf16"], None) if bf else P(W["fine"]), len(names_f), ctypes.c_uint(cross_bits), 1 if cf["enable"] else 0,
-                             *((_NSPLIT[self.precision],) if bf else ()),
-                             fi.wc, stride, float(fine_scale), P(expec), P(cb["mk2d"]), P(dbg_w), P(dbg_3), *((P(qscale),) if qscale is not None else ()), S)
+                    fine_refine(ff, ff_strides, hf, fi.wf, desc, b_ids=cb["b_ids"], i_ids=cb["i_ids"], j_ids=cb["j_ids"], count=cb["count"],
+                                mkpts_c=cb["mkc"], max_matches=cap, wpack=W["fine_bf16"] if bf else W["fine"], nlayers=len(names_f),
+                                cross_bits=cross_bits, encoder_enable=1 if cf["enable"] else 0, nsplit=_NSPLIT[self.precision] if bf else None,
+                                wc=fi.wc, stride=stride, fine_scale=fine_scale, expec_f=expec, mkpts_f=cb["mk2d"], dbg_win=dbg_w, dbg_f3=dbg_3,
+                                query_scale=qscale)
             if fine_entry is not None:
                 fine_done = torch.cuda.Event()
                 fine_done.record()
@@ -841,14 +828,9 @@ class LazyConfMatrix(LazyConfMatrixBase):
         ids = torch.empty(3 * cap, dtype=torch.int64, device=dev)
         fl = torch.empty(6 * cap + 3, dtype=torch.float32, device=dev)
         cnt = torch.zeros(4, dtype=torch.int32, device=dev)
-        P = hip.ptr
-        args = (P(self._f3), P(self._f2), P(fl[:3]), 0, B, N, M, M, self._temp, 0.5, 0, 1.0,
-                P(conf), P(ws), P(ids[:cap], torch.int64), P(ids[cap:2 * cap], torch.int64), P(ids[2 * cap:], torch.int64),
-                P(fl[3:3 + cap]), P(fl[3 + cap:3 + 4 * cap]), P(fl[3 + 4 * cap:3 + 6 * cap]), None, None, P(cnt, torch.int32), self._nsplit)
-        if self._qmask is None:
-            hip.call("ophip_coarse_match_conf", *args, hip.stream_handle())
-        else:
-            hip.call("ophip_coarse_match_masked", *args, 1, P(self._qmask, torch.uint8), None, hip.stream_handle())
+        lists = MatchLists(ids[:cap], ids[cap:2 * cap], ids[2 * cap:], fl[3:3 + cap], fl[3 + cap:3 + 4 * cap], fl[3 + 4 * cap:3 + 6 * cap], None, None, cnt)
+        coarse_match(self._f3, self._f2, fl[:3], kpts_bstride=0, wc=M, temperature=self._temp, thr=0.5, border_rm=0, scale=1.0,
+                     nsplit=self._nsplit, lists=lists, conf=conf, workspace=ws, parts=1, query_mask=self._qmask)
         self._f3 = self._f2 = None
         return conf
 

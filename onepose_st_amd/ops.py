@@ -28,6 +28,7 @@ import itertools
 import torch
 
 from . import hip
+from .matchcall import MatchLists, coarse_match, fine_refine
 
 _lib = torch.library.Library("onepose_hip", "DEF")
 
@@ -98,16 +99,12 @@ def _coarse_match(feat3d, feat2d, keypoints3d, wc, temperature, thr, border_rm, 
     M = feat2d.shape[1]
     dev = feat3d.device
     cap = B * N
-    conf = torch.empty(B, N, M, device=dev)
-    ws = torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev)
     ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3)]
-    mconf, mk3, mkc = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    hip.call("ophip_coarse_match", hip.ptr(_f32(feat3d, "feat3d")), hip.ptr(_f32(feat2d, "feat2d")), hip.ptr(_f32(keypoints3d, "keypoints3d")),
-             hip.bstride(keypoints3d), B, N, M, int(wc), float(temperature), float(thr), int(border_rm), float(scale), hip.ptr(conf), hip.ptr(ws),
-             *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), None, None, hip.ptr(count, torch.int32),
-             int(nsplit), hip.stream_handle())
-    return conf, ids[0], ids[1], ids[2], mconf, mk3, mkc, count
+    lists = MatchLists(*ids, torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev), None, None,
+                       torch.zeros(1, dtype=torch.int32, device=dev), conf=torch.empty(B, N, M, device=dev))
+    coarse_match(_f32(feat3d, "feat3d"), _f32(feat2d, "feat2d"), _f32(keypoints3d, "keypoints3d"), wc=wc, temperature=temperature, thr=thr,
+                 border_rm=border_rm, scale=scale, nsplit=nsplit, lists=lists, conf=lists.conf)
+    return lists.conf, lists.b_ids, lists.i_ids, lists.j_ids, lists.mconf, lists.mk3d, lists.mkc, lists.count
 
 
 def _fine_refine_bf16(feat_f_cl, desc3d_f, b_ids, i_ids, j_ids, count, mkpts_c, wpack, nlayers, cross_bits, encoder_enable, nsplit,
@@ -120,11 +117,9 @@ def _fine_refine_bf16(feat_f_cl, desc3d_f, b_ids, i_ids, j_ids, count, mkpts_c, 
     cap = b_ids.numel()
     dev = feat_f_cl.device
     expec, mkf = torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-    hip.call("ophip_fine_refine_bf16", hip.ptr(feat_f_cl), feat_f_cl.stride(0), feat_f_cl.stride(1), feat_f_cl.stride(2), feat_f_cl.stride(3), hf, wf,
-             hip.ptr(_f32(desc3d_f, "desc3d_f")), hip.bstride(desc3d_f), desc3d_f.stride(1),
-             hip.ptr(b_ids, torch.int64), hip.ptr(i_ids, torch.int64), hip.ptr(j_ids, torch.int64), hip.ptr(count, torch.int32), cap,
-             hip.ptr(_f32(mkpts_c, "mkpts_c")), hip.ptr(wpack, None), int(nlayers), ctypes.c_uint(int(cross_bits)), int(bool(encoder_enable)), int(nsplit),
-             int(wc), int(stride), float(fine_scale), hip.ptr(expec), hip.ptr(mkf), None, None, hip.stream_handle())
+    fine_refine(feat_f_cl, feat_f_cl.stride(), hf, wf, _f32(desc3d_f, "desc3d_f"), b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, count=count,
+                mkpts_c=_f32(mkpts_c, "mkpts_c"), max_matches=cap, wpack=wpack, nlayers=nlayers, cross_bits=cross_bits,
+                encoder_enable=bool(encoder_enable), nsplit=nsplit, wc=wc, stride=stride, fine_scale=fine_scale, expec_f=expec, mkpts_f=mkf)
     return expec, mkf
 
 

@@ -270,6 +270,39 @@ def test_every_binding_checks_the_number_of_arguments(module, monkeypatch):
 
 
 @pytest.mark.parametrize("module", BINDINGS)
+def test_order_puts_named_arguments_into_header_order(module, monkeypatch):
+    """``Binding.order`` for every prototype: shuffled keywords of sentinel values come back in header order without a loaded library;
+    a missing and an unknown name raise ``TypeError`` naming them; ``call_named`` hands ``call`` that tuple"""
+    import random
+    binding, rng = BINDINGS[module], random.Random(5)
+    monkeypatch.setattr(binding, "load", lambda: pytest.fail("order() must not load the library"))
+    assert binding.header.prototypes
+    for proto in binding.header.prototypes.values():
+        names = [n for _, n in proto.params]
+        assert len(set(names)) == len(names), f"{proto.name}: a parameter name twice"
+        sentinels = {n: object() for n in names}
+        shuffled = rng.sample(names, len(names))
+        got = binding.order(proto.name, **{n: sentinels[n] for n in shuffled})
+        assert len(got) == len(names) and all(g is sentinels[n] for g, n in zip(got, names)), proto.name
+        if names:
+            with pytest.raises(TypeError) as e:
+                binding.order(proto.name, **{n: sentinels[n] for n in shuffled if n != names[-1]})
+            assert proto.name in str(e.value) and f"missing {names[-1]}" in str(e.value)
+        with pytest.raises(TypeError) as e:
+            binding.order(proto.name, **sentinels, no_such_parameter=1)
+        assert proto.name in str(e.value) and "unknown no_such_parameter" in str(e.value)
+        if proto.ret == "int" and names:
+            lib = _StandIn()
+            monkeypatch.setattr(binding, "handle", lib)
+            binding.call_named(proto.name, **{n: sentinels[n] for n in shuffled})
+            assert lib.entered == [(proto.name, got)]
+    if module == "hip":
+        assert hip.order == binding.order
+        with pytest.raises(TypeError, match="missing stream; unknown streem"):
+            hip.call_named("ophip_pe_add_transpose", feat_nchw=None, pe_nlc=None, out_nlc=None, B=1, C=2, M=3, streem=None)
+
+
+@pytest.mark.parametrize("module", BINDINGS)
 def test_call_maps_the_status_to_an_exception(module, monkeypatch):
     binding, mod = BINDINGS[module], importlib.import_module(f"onepose_st_amd.{module}")
     proto = _status_entry(binding)

@@ -24,12 +24,11 @@ The device's shares lie at or above the CPU stand-in's (0.70 / 0.81 / 0.89): ``_
 rounding boundaries than accumulation order does, and the reference misses no rounding point.  The caps stay at the issue's 0.40 / 0.55.
 Planted heat maps land within 9.0e-6 of their grid point in every mode and layout.
 """
-import ctypes
 
 import pytest
 import torch
 
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, matchcall, packing
 from tests import bf16_faithful as bf
 
 pytestmark = pytest.mark.gpu
@@ -165,19 +164,11 @@ def run(dev, mode, c, w, nl, bits, enc, count, cap, rows=None, layout="nchw", qs
     cnt = torch.tensor([count], dtype=torch.int32, device=dev)
     nan = lambda *s: torch.full(s, float("nan"), device=dev)
     expec, mkf, dw, d3 = nan(rows, 3), nan(rows, 2), nan(rows, 25, 128), nan(rows, 128)
-    head = (hip.ptr(ff), ff.stride(0), ff.stride(1), ff.stride(2), ff.stride(3), c["hf"], c["wf"], hip.ptr(dd), dd.stride(0), dd.stride(1),
-            hip.ptr(bd, torch.int64), hip.ptr(idd, torch.int64), hip.ptr(jd, torch.int64), hip.ptr(cnt, torch.int32), cap, hip.ptr(mkd))
-    tail = [c["wc"], c["stride"], FINE_SCALE, hip.ptr(expec), hip.ptr(mkf), hip.ptr(dw if dbg else None), hip.ptr(d3 if dbg else None)]
-    qd = None
-    if qscale is not None:
-        qd = qscale.to(dev)
-        tail.append(hip.ptr(qd))
-    tail.append(hip.stream_handle())
-    sfx = "_scaled" if qscale is not None else ""
-    if mode == "f32":
-        hip.call("ophip_fine_refine" + sfx, *head, hip.ptr(w), nl, ctypes.c_uint(bits), enc, *tail)
-    else:
-        hip.call("ophip_fine_refine_bf16" + sfx, *head, hip.ptr(w, None), nl, ctypes.c_uint(bits), enc, 3 if mode == "bf16x3" else 1, *tail)
+    qd = None if qscale is None else qscale.to(dev)
+    matchcall.fine_refine(ff, ff.stride(), c["hf"], c["wf"], dd, b_ids=bd, i_ids=idd, j_ids=jd, count=cnt, mkpts_c=mkd, max_matches=cap, wpack=w,
+                          nlayers=nl, cross_bits=bits, encoder_enable=enc, nsplit={"f32": None, "bf16x3": 3, "bf16": 1}[mode], wc=c["wc"],
+                          stride=c["stride"], fine_scale=FINE_SCALE, expec_f=expec, mkpts_f=mkf, dbg_win=dw if dbg else None,
+                          dbg_f3=d3 if dbg else None, query_scale=qd)
     torch.cuda.synchronize()
     return {"expec_f": expec.cpu(), "mkpts_f": mkf.cpu(), "windows": dw.cpu(), "f3": d3.cpu()}
 

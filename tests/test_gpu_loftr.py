@@ -9,7 +9,7 @@ import torch
 
 from oracle import loftr_oracle as lo
 from oracle import onepose_oracle as orc
-from onepose_st_amd import detector, hip, loftr, packing
+from onepose_st_amd import detector, hip, loftr, matchcall, packing
 from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
 from tests.loftr_helpers import device_hook, oracle_hook, planted_pair
 
@@ -127,9 +127,8 @@ def test_coarse_match_2d_against_the_published_rules(dev):
     mconf, mk0, mk1 = torch.empty(L0, device=dev), torch.empty(L0, 3, device=dev), torch.empty(L0, 2, device=dev)
     cnt = torch.zeros(4, dtype=torch.int32, device=dev)
     for conf_buf in (conf, None):                                               # eager and lazy form
-        hip.call("ophip_coarse_match_2d", hip.ptr(d0), hip.ptr(d1), hip.ptr(pts0), 0, 1, L0, L1, w0, w1, 0.1, 0.2, 2, 8.0, hip.ptr(conf_buf), hip.ptr(ws),
-                 *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk0), hip.ptr(mk1), None, None, hip.ptr(cnt, torch.int32), 3,
-                 hip.stream_handle())
+        matchcall.coarse_match_2d(d0, d1, pts0, w0c=w0, w1c=w1, temperature=0.1, thr=0.2, border_rm=2, scale=8.0,
+                                  lists=matchcall.MatchLists(*ids, mconf, mk0, mk1, None, None, cnt), conf=conf_buf, workspace=ws)
         K = int(cnt[0])
         assert K == 3 and ids[1][:K].tolist() == ref["i_ids"].tolist() and ids[2][:K].tolist() == ref["j_ids"].tolist()
         close(mconf[:K], ref["mconf"], 1e-3, 1e-5)

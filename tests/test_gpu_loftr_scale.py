@@ -19,7 +19,7 @@ import copy
 import pytest
 import torch
 
-from onepose_st_amd import hip, loftr, packing
+from onepose_st_amd import hip, loftr, matchcall, packing
 from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
 from tests import loftr_masked_oracle as lmo
 from tests import test_gpu_loftr_masked as tglm
@@ -186,17 +186,11 @@ def _collect(conf, ids, mconf, mk0, mk1, cnt):
 
 def _dual(dev, d0, d1, w0, w1, masks=None, nsplit=3, lazy=False):
     B, L0, L1 = d0.shape[0], d0.shape[1], d1.shape[1]
-    P = hip.ptr
     conf = None if lazy else torch.full((B, L0, L1), float("nan"), device=dev)
     ws = torch.full((hip.load().ophip_coarse_workspace_floats(B, L0, L1),), float("nan"), device=dev)
     ids, mconf, mk0, mk1, gt, cnt = _outputs(B, L0, dev)
-    pts0 = _pts(L0, w0, dev)
-    args = (P(d0), P(d1), P(pts0), 0, B, L0, L1, w0, w1, TEMP, THR, BD, 8.0, P(conf), P(ws), *[P(t, torch.int64) for t in ids[:3]],
-            P(mconf), P(mk0), P(mk1), P(ids[3], torch.int64), P(gt, torch.bool), P(cnt, torch.int32), nsplit)
-    if masks is None:
-        hip.call("ophip_coarse_match_2d", *args, hip.stream_handle())
-    else:
-        hip.call("ophip_coarse_match_2d_masked", *args, P(masks[0], torch.bool), P(masks[1], torch.bool), hip.stream_handle())
+    matchcall.coarse_match_2d(d0, d1, _pts(L0, w0, dev), w0c=w0, w1c=w1, temperature=TEMP, thr=THR, border_rm=BD, scale=8.0, nsplit=nsplit,
+                              masks=masks, lists=matchcall.MatchLists(*ids[:3], mconf, mk0, mk1, ids[3], gt, cnt), conf=conf, workspace=ws)
     out = _collect(conf, ids, mconf, mk0, mk1, cnt)
     if conf is not None:
         assert bool(torch.isfinite(conf).all()), "conf_matrix has entries no kernel wrote"
@@ -205,17 +199,11 @@ def _dual(dev, d0, d1, w0, w1, masks=None, nsplit=3, lazy=False):
 
 def _skh(dev, d0, d1, w0, w1, iters, prefilter, masks=None, bin_score=1.0):
     B, L0, L1 = d0.shape[0], d0.shape[1], d1.shape[1]
-    P = hip.ptr
     conf = torch.full((B, L0, L1), float("nan"), device=dev)
     ws = torch.full((hip.load().ophip_coarse_sinkhorn_workspace_floats(B, L0, L1),), float("nan"), device=dev)
     ids, mconf, mk0, mk1, gt, cnt = _outputs(B, L0, dev)
-    pts0 = _pts(L0, w0, dev)
-    args = (P(d0), P(d1), P(pts0), 0, B, L0, L1, w0, w1, float(bin_score), iters, prefilter, THR, BD, 8.0, P(conf), P(ws),
-            *[P(t, torch.int64) for t in ids[:3]], P(mconf), P(mk0), P(mk1), P(ids[3], torch.int64), P(gt, torch.bool), P(cnt, torch.int32))
-    if masks is None:
-        hip.call("ophip_coarse_match_2d_sinkhorn", *args, hip.stream_handle())
-    else:
-        hip.call("ophip_coarse_match_2d_sinkhorn_masked", *args, P(masks[0], torch.bool), P(masks[1], torch.bool), hip.stream_handle())
+    matchcall.coarse_match_2d(d0, d1, _pts(L0, w0, dev), w0c=w0, w1c=w1, sinkhorn=(bin_score, iters, prefilter), thr=THR, border_rm=BD, scale=8.0,
+                              masks=masks, lists=matchcall.MatchLists(*ids[:3], mconf, mk0, mk1, ids[3], gt, cnt), conf=conf, workspace=ws)
     assert bool(torch.isfinite(conf).all()), "conf_matrix has entries no kernel wrote"
     return _collect(conf, ids, mconf, mk0, mk1, cnt)
 

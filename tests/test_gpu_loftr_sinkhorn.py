@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from onepose_st_amd import detector, hip, loftr
+from onepose_st_amd import detector, hip, loftr, matchcall
 from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
 from tests import loftr_sinkhorn_oracle as lso
 from tests import test_gpu_loftr as tgl
@@ -77,9 +77,8 @@ def _stage(dev, f0, f1, w0, w1, bin_score, iters, prefilter, thr=0.2, border=2, 
     mconf, mk0, mk1 = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
     gt = torch.empty(cap, dtype=torch.bool, device=dev)
     cnt = torch.zeros(4, dtype=torch.int32, device=dev)
-    hip.call("ophip_coarse_match_2d_sinkhorn", hip.ptr(d0), hip.ptr(d1), hip.ptr(pts0), 0, B, L0, L1, w0, w1, float(bin_score), iters, prefilter,
-             thr, border, 8.0, hip.ptr(conf), hip.ptr(ws), *[hip.ptr(t, torch.int64) for t in ids[:3]], hip.ptr(mconf), hip.ptr(mk0), hip.ptr(mk1),
-             hip.ptr(ids[3], torch.int64), hip.ptr(gt, torch.bool), hip.ptr(cnt, torch.int32), hip.stream_handle())
+    matchcall.coarse_match_2d(d0, d1, pts0, w0c=w0, w1c=w1, sinkhorn=(bin_score, iters, prefilter), thr=thr, border_rm=border, scale=8.0,
+                              lists=matchcall.MatchLists(*ids[:3], mconf, mk0, mk1, ids[3], gt, cnt), conf=conf, workspace=ws)
     K = int(cnt[0])
     return {"conf": conf, "ws": ws, "K": K, "b_ids": ids[0][:K].cpu(), "i_ids": ids[1][:K].cpu(), "j_ids": ids[2][:K].cpu(),
             "mconf": mconf[:K].cpu(), "m_bids": ids[3][:K].cpu(), "mkpts0": mk0[:K].cpu(), "mkpts1": mk1[:K].cpu()}

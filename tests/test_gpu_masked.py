@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, matchcall, packing
 from onepose_st_amd.synthetic import make_synthetic_inputs
 from tests.test_gpu_parity import TOL, _check_against, _model, _planted_features, close, dev, model, to_dev  # noqa: F401  (dev, model: fixtures)
 
@@ -93,7 +93,6 @@ def test_coarse_match_masked_scaled_vs_oracle(dev, B, N, hc, wc, nsplit, rtol):
     outs = []
     for lazy in ([False] if nsplit == 0 else [False, True]):
         cap = B * N
-        P = hip.ptr
         d3, d2, dk = f3.to(dev), f2.to(dev), kp.to(dev)
         dm, dq = mask.flatten(1).to(dev).view(torch.uint8).contiguous(), qs.to(dev)
         conf = None if lazy else torch.full((B, N, M), float("nan"), device=dev)
@@ -101,9 +100,9 @@ def test_coarse_match_masked_scaled_vs_oracle(dev, B, N, hc, wc, nsplit, rtol):
         ids = torch.zeros(4, cap, dtype=torch.int64, device=dev)
         mconf, mk3, mkc = torch.zeros(cap, device=dev), torch.zeros(cap, 3, device=dev), torch.zeros(cap, 2, device=dev)
         gtm, cnt = torch.zeros(cap, dtype=torch.bool, device=dev), torch.zeros(4, dtype=torch.int32, device=dev)
-        hip.call("ophip_coarse_match_masked", P(d3), P(d2), P(dk), N * 3, B, N, M, wc, 0.08, 0.1, 2, 8.0, P(conf), P(ws),
-                 P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk3), P(mkc), P(ids[3], torch.int64),
-                 P(gtm, torch.bool), P(cnt, torch.int32), nsplit, 3, P(dm, torch.uint8), P(dq), hip.stream_handle())
+        matchcall.coarse_match(d3, d2, dk, kpts_bstride=N * 3, wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=nsplit,
+                               lists=matchcall.MatchLists(*ids[:3], mconf, mk3, mkc, ids[3], gtm, cnt), conf=conf, workspace=ws,
+                               query_mask=dm, query_scale=dq)
         torch.cuda.synchronize()
         K = int(cnt[0])
         assert int(cnt[1]) == 0

@@ -1,5 +1,5 @@
 """The product's own allocations under guard (run with ``-m gpu`` on the MI355X): for the duration of a call, ``torch.empty`` /
-``torch.empty_like`` as ``onepose_st_amd.model`` and ``onepose_st_amd.loftr`` look them up hand out regions of a ``tests.guarded.Arena``
+``torch.empty_like`` as ``onepose_st_amd.model``, ``.loftr`` and ``.matchcall`` look them up hand out regions of a ``tests.guarded.Arena``
 -- every workspace, intermediate, output and frame block of the call at exactly the size the product asks for, 1 MiB of guard on each
 side, filled 0xFF (NaN / -1) or 0x00 instead of whatever the caching allocator last held there.
 
@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from onepose_st_amd import loftr as loftr_module
-from onepose_st_amd import hip, model as model_module
+from onepose_st_amd import hip, matchcall as matchcall_module, model as model_module
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_loftr_state_dict
 from tests import test_gpu_loftr_masked as tglm
@@ -22,7 +22,7 @@ from tests.test_gpu_workspace_contract import FILLS, FRAME_KEYS, same_bits
 
 pytestmark = pytest.mark.gpu
 
-MODULES = [model_module, loftr_module]
+MODULES = [model_module, loftr_module, matchcall_module]
 ARENA_BYTES = 320 << 20
 
 

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, host_math, packing
+from onepose_st_amd import hip, host_math, matchcall, packing
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.pnp import ransac_PnP
 from onepose_st_amd.synthetic import make_synthetic_inputs
@@ -238,7 +238,6 @@ def test_encoder_layer_writes_the_similarity_fragments(sd, dev, B, N, hc, wc):
     """ophip_encoder_layer_x3w8_frag: the layer's output rows, also as the similarity kernel's (hi, lo) operand fragments inside the
     coarse workspace (rows padded with zeros to 128).  Coarse matching fed that way (nsplit | OPHIP_COARSE_PLANES_READY) must give
     bit for bit what it gives when its own frag_planes kernel converts the same rows -- at sizes that are no multiple of 48 or 128."""
-    import ctypes
     M = hc * wc
     g = torch.Generator().manual_seed(9)
     x3, x2 = torch.randn(B, N, 256, generator=g).to(dev), torch.randn(B, M, 256, generator=g).to(dev)
@@ -253,9 +252,8 @@ def test_encoder_layer_writes_the_similarity_fragments(sd, dev, B, N, hc, wc):
         ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3)]
         mconf, mk3, mkc = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
         cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-        hip.call("ophip_coarse_match", hip.ptr(y3), hip.ptr(y2), hip.ptr(kp), kp.stride(0), B, N, M, wc, 0.08, 0.1, 2, 8.0, hip.ptr(conf), hip.ptr(cws),
-                 *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), None, None, hip.ptr(cnt, torch.int32),
-                 3 | flag, hip.stream_handle())
+        matchcall.coarse_match(y3, y2, kp, kpts_bstride=kp.stride(0), wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=3 | flag,
+                               lists=matchcall.MatchLists(*ids, mconf, mk3, mkc, None, None, cnt), conf=conf, workspace=cws)
         K = int(cnt.item())
         return conf, [t[:K].clone() for t in ids], mconf[:K].clone()
 
@@ -325,10 +323,8 @@ def _coarse_match(dev, f3, f2, kp, wc, thr=0.1, border=2, temp=0.08, scale=8.0, 
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     m_bids, gt_mask = torch.full((cap,), -1, dtype=torch.int64, device=dev), torch.full((cap,), 7, dtype=torch.uint8, device=dev)
     kd, f3d, f2d = kp.to(dev), f3.to(dev), f2.to(dev)      # keep the device copies alive across the call
-    hip.call("ophip_coarse_match", hip.ptr(f3d), hip.ptr(f2d), hip.ptr(kd), kd.stride(0), B, N, M, wc,
-             temp, thr, border, scale, hip.ptr(conf), hip.ptr(ws), *[hip.ptr(t, torch.int64) for t in ids],
-             hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), hip.ptr(m_bids, torch.int64), hip.ptr(gt_mask, torch.uint8),
-             hip.ptr(cnt, torch.int32), nsplit, hip.stream_handle())
+    matchcall.coarse_match(f3d, f2d, kd, kpts_bstride=kd.stride(0), wc=wc, temperature=temp, thr=thr, border_rm=border, scale=scale, nsplit=nsplit,
+                           lists=matchcall.MatchLists(*ids, mconf, mk3, mkc, m_bids, gt_mask, cnt), conf=conf, workspace=ws)
     K = int(cnt.item())
     assert bool(torch.isfinite(conf).all()), "conf_matrix has elements no kernel wrote"
     assert torch.equal(m_bids[:K], ids[0][:K]) and bool((m_bids[K:] == -1).all())      # second copy of b_ids, nothing past K
@@ -493,9 +489,9 @@ def test_fine_pair_kernel_is_bit_identical_to_the_one_match_kernel(sd, dev):
     NCHW and channels-last maps, both bf16 modes.  The one-match kernel stays reachable through OPHIP_FINE_PAIR=0 for this test."""
     import subprocess, sys, json, tempfile
     code = r'''
-import ctypes, os, sys, torch, hashlib, json
+import os, sys, torch, hashlib, json
 sys.path.insert(0, os.getcwd())
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, matchcall, packing
 from onepose_st_amd.config import default_config
 from onepose_st_amd.synthetic import make_synthetic_state_dict
 sd = make_synthetic_state_dict(0, default_config()); dev = torch.device("cuda:0"); hip.load()
@@ -517,9 +513,9 @@ for cl in (False, True):
     for ns in (3, 1):
         expec = torch.full((cap, 3), float("nan"), device=dev); mkf = torch.full((cap, 2), float("nan"), device=dev)
         dw, d3 = torch.zeros(cap, 25, 128, device=dev), torch.zeros(cap, 128, device=dev)
-        hip.call("ophip_fine_refine_bf16", hip.ptr(ff), ff.stride(0), ff.stride(1), ff.stride(2), ff.stride(3), hf, wf, hip.ptr(desc), desc.stride(0), desc.stride(1),
-                 hip.ptr(b_ids, torch.int64), hip.ptr(i_ids, torch.int64), hip.ptr(j_ids, torch.int64), hip.ptr(cnt, torch.int32), cap, hip.ptr(mkc),
-                 hip.ptr(w, None), 2, ctypes.c_uint(2), 1, ns, wc, 4, 4.0, hip.ptr(expec), hip.ptr(mkf), hip.ptr(dw), hip.ptr(d3), hip.stream_handle())
+        matchcall.fine_refine(ff, ff.stride(), hf, wf, desc, b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, count=cnt, mkpts_c=mkc, max_matches=cap, wpack=w,
+                              nlayers=2, cross_bits=2, encoder_enable=1, nsplit=ns, wc=wc, stride=4, fine_scale=4.0, expec_f=expec, mkpts_f=mkf,
+                              dbg_win=dw, dbg_f3=d3)
         torch.cuda.synchronize()
         assert torch.isfinite(expec[:K]).all() and torch.isnan(expec[K:]).all()
         h = hashlib.sha256()
@@ -575,18 +571,16 @@ def test_fine_refine_vs_oracle(sd, cfg, dev, channels_last, mode):
     mkf = torch.full((cap, 2), float("nan"), device=dev)
     dw, d3 = torch.empty(cap, 25, 128, device=dev), torch.empty(cap, 128, device=dev)
     dd = desc.to(dev)
-    head = (hip.ptr(ff), ff.stride(0), ff.stride(1), ff.stride(2), ff.stride(3), hf, wf, hip.ptr(dd), dd.stride(0), dd.stride(1),
-            hip.ptr(bd, torch.int64), hip.ptr(idd, torch.int64), hip.ptr(jd, torch.int64), hip.ptr(cnt, torch.int32), cap, hip.ptr(mkd))
-    tail = (wc, 4, 4.0, hip.ptr(expec), hip.ptr(mkf), hip.ptr(dw), hip.ptr(d3), hip.stream_handle())
     if mode == "f32":
         w = torch.cat([packing.pack_fine_layer(sd, f"loftr_fine.layers.{i}.") for i in range(2)]).to(dev)
-        hip.call("ophip_fine_refine", *head, hip.ptr(w), 2, ctypes.c_uint(2), 1, *tail)
         rt, at = RTOL, ATOL
     else:
         w = packing.pack_fine_layers_bf16(sd, "loftr_fine.layers.", 2).to(dev)
         assert w.numel() == hip.load().ophip_fine_bf16_wpack_bytes(2)
-        hip.call("ophip_fine_refine_bf16", *head, hip.ptr(w, None), 2, ctypes.c_uint(2), 1, 3 if mode == "bf16x3" else 1, *tail)
         rt, at = (5e-4, 2e-4) if mode == "bf16x3" else (1e-1, 1e-1)
+    matchcall.fine_refine(ff, ff.stride(), hf, wf, dd, b_ids=bd, i_ids=idd, j_ids=jd, count=cnt, mkpts_c=mkd, max_matches=cap, wpack=w, nlayers=2,
+                          cross_bits=2, encoder_enable=1, nsplit={"f32": None, "bf16x3": 3, "bf16": 1}[mode], wc=wc, stride=4, fine_scale=4.0,
+                          expec_f=expec, mkpts_f=mkf, dbg_win=dw, dbg_f3=d3)
     print(f"{mode}: fine encoder max abs err window {(dw[:K].cpu() - wino).abs().max().item():.3e}, "
           f"3D {(d3[:K].cpu() - f3o[:, 0]).abs().max().item():.3e}, mkpts_f {(mkf[:K].cpu() - ref['mkpts_query_f']).abs().max().item():.3e} px")
     close(dw[:K], wino, rtol=rt, atol=at, msg="fine encoder, window stream")
@@ -1275,9 +1269,8 @@ def test_lazy_conf_matrix_exact_tie_raises_the_rerun_flag(dev):
         ids = [torch.empty(N, dtype=torch.int64, device=dev) for _ in range(3)]
         mconf, mk3, mkc = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 2, device=dev)
         cnt = torch.full((4,), 7, dtype=torch.int32, device=dev)
-        hip.call("ophip_coarse_match", hip.ptr(d3), hip.ptr(d2), hip.ptr(dk), 0, 1, N, M, wc, 0.08, 0.1, 2, 8.0, None, hip.ptr(ws),
-                 *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), None, None, hip.ptr(cnt, torch.int32), 3,
-                 hip.stream_handle())
+        matchcall.coarse_match(d3, d2, dk, wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=3,
+                               lists=matchcall.MatchLists(*ids, mconf, mk3, mkc, None, None, cnt), conf=None, workspace=ws)
         K = int(cnt[0])
         return K, int(cnt[1]), ids[1][:K].cpu(), ids[2][:K].cpu(), mconf[:K].cpu()
     # no tie: flag 0, lists equal the eager form's
@@ -1293,12 +1286,8 @@ def test_lazy_conf_matrix_exact_tie_raises_the_rerun_flag(dev):
     K, flag, i_l, j_l, _ = lazy_call(f2t)
     assert flag == 1                                   # "run this frame again with a conf buffer"
     with pytest.raises(ValueError):                    # the exact-f32 mode has no lazy form
-        d3 = f3.to(dev)
-        hip.call("ophip_coarse_match", hip.ptr(d3), hip.ptr(f2.to(dev)), hip.ptr(kp.to(dev)), 0, 1, N, M, wc, 0.08, 0.1, 2, 8.0, None,
-                 hip.ptr(torch.empty(hip.load().ophip_coarse_workspace_floats(1, N, M), device=dev)),
-                 *[hip.ptr(torch.empty(N, dtype=torch.int64, device=dev), torch.int64) for _ in range(3)],
-                 hip.ptr(torch.empty(N, device=dev)), hip.ptr(torch.empty(N, 3, device=dev)), hip.ptr(torch.empty(N, 2, device=dev)), None, None,
-                 hip.ptr(torch.zeros(4, dtype=torch.int32, device=dev), torch.int32), 0, hip.stream_handle())
+        matchcall.coarse_match(f3.to(dev), f2.to(dev), kp.to(dev), wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=0,
+                               lists=matchcall.MatchLists.empty(N, dev), conf=None)
 
 
 def test_custom_ops_match_the_c_abi(sd, cfg, dev):
@@ -1339,9 +1328,8 @@ def test_custom_ops_match_the_c_abi(sd, cfg, dev):
     expec, mkf = torch.ops.onepose_hip.fine_refine_bf16(ff, dd, b_ids, i_ids, j_ids, count, mkc, wf_, 2, 2, True, 3, wc, 4, 4.0)
     e2, m2 = torch.full_like(expec, float("nan")), torch.full_like(mkf, float("nan"))
     cap = b_ids.numel()
-    hip.call("ophip_fine_refine_bf16", hip.ptr(ff), ff.stride(0), ff.stride(1), ff.stride(2), ff.stride(3), hf, wf, hip.ptr(dd), dd.stride(0), dd.stride(1),
-             hip.ptr(b_ids, torch.int64), hip.ptr(i_ids, torch.int64), hip.ptr(j_ids, torch.int64), hip.ptr(count, torch.int32), cap, hip.ptr(mkc),
-             hip.ptr(wf_, None), 2, ctypes.c_uint(2), 1, 3, wc, 4, 4.0, hip.ptr(e2), hip.ptr(m2), None, None, hip.stream_handle())
+    matchcall.fine_refine(ff, ff.stride(), hf, wf, dd, b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, count=count, mkpts_c=mkc, max_matches=cap, wpack=wf_,
+                          nlayers=2, cross_bits=2, encoder_enable=1, nsplit=3, wc=wc, stride=4, fine_scale=4.0, expec_f=e2, mkpts_f=m2)
     assert torch.equal(expec[:K], e2[:K]) and torch.equal(mkf[:K], m2[:K]) and torch.isfinite(mkf[:K]).all()
     with pytest.raises(ValueError):
         torch.ops.onepose_hip.encoder_layer_x3w8(x3, x2, y3, y2, w, None, False, False, 0, ws[:64])

@@ -24,7 +24,7 @@ import pytest
 import torch
 
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, model as model_module, packing, postopt
+from onepose_st_amd import hip, matchcall, model as model_module, packing, postopt
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_sfm_tracks
 from tests import bf16_faithful as bf
@@ -340,10 +340,10 @@ def coarse_buffers(arena, B, N, M, lazy):
             "count": arena.typed((4,), I32, name="count")}
 
 
-def coarse_tail(o):
-    """the output arguments of every coarse-matching entry, conf to count"""
-    return (P(o["conf"]), o["wsp"], P(o["b_ids"], I64), P(o["i_ids"], I64), P(o["j_ids"], I64), P(o["mconf"]), P(o["mk3"]), P(o["mkc"]),
-            P(o["m_bids"], I64), P(o["gt_mask"], U8), P(o["count"], I32))
+def coarse_outputs(o, wsp):
+    """the buffers of ``coarse_buffers`` and the workspace region as every coarse-matching call of ``matchcall`` takes them"""
+    lists = matchcall.MatchLists(*(o[k] for k in ("b_ids", "i_ids", "j_ids", "mconf", "mk3", "mkc", "m_bids", "gt_mask", "count")))
+    return dict(lists=lists, conf=o["conf"], workspace=wsp.view(F32))
 
 
 def coarse_lists(out):
@@ -365,6 +365,10 @@ def coarse_bar(case, hc, wc, nsplit):
     return lambda out: par.coarse_equals_oracle(*coarse_lists(out), ref_conf, ref, par.COARSE_RTOL[nsplit])
 
 
+def coarse_kw(wc):
+    return dict(wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0)
+
+
 COARSE_FORMS = [("f32", 0, None, None), ("x3", 3, None, None), ("bf16", 1, None, None), ("x3_lazy", 3, None, None), ("bf16_lazy", 1, None, None)] + \
                [(f"{'x3' if ns == 3 else 'bf16'}_tile{tile}_twopass{two}", ns, tile, two) for ns in (3, 1) for tile in ("2", "3") for two in ("0", "1")]
 
@@ -384,9 +388,7 @@ def test_coarse_match(dev, monkeypatch, B, N, hc, wc, form, nsplit, tile, two):
     def run(arena, ws):
         f3, f2, kp = (arena.put(case[k], name=k) for k in ("f3", "f2", "kp"))
         o = coarse_buffers(arena, B, N, M, lazy)
-        o["wsp"] = P(ws(4 * nfloats), None)
-        hip.call("ophip_coarse_match", P(f3), P(f2), P(kp), N * 3, B, N, M, wc, 0.08, 0.1, 2, 8.0, *coarse_tail(o), nsplit, hip.stream_handle())
-        del o["wsp"]
+        matchcall.coarse_match(f3, f2, kp, kpts_bstride=N * 3, nsplit=nsplit, **coarse_kw(wc), **coarse_outputs(o, ws(4 * nfloats)))
         return o
 
     def bar(out):
@@ -408,10 +410,9 @@ def test_coarse_match_in_two_halves(dev, B, N, hc, wc, nsplit):
     def run(arena, ws):
         f3, f2, kp = (arena.put(case[k], name=k) for k in ("f3", "f2", "kp"))
         o = coarse_buffers(arena, B, N, M, False)
-        o["wsp"] = P(ws(4 * nfloats), None)
-        for entry in ("ophip_coarse_match_conf", "ophip_coarse_match_select"):
-            hip.call(entry, P(f3), P(f2), P(kp), N * 3, B, N, M, wc, 0.08, 0.1, 2, 8.0, *coarse_tail(o), nsplit, hip.stream_handle())
-        del o["wsp"]
+        outputs = coarse_outputs(o, ws(4 * nfloats))
+        for parts in (1, 2):                                          # _conf, then _select
+            matchcall.coarse_match(f3, f2, kp, kpts_bstride=N * 3, nsplit=nsplit, parts=parts, **coarse_kw(wc), **outputs)
         return o
 
     contract(dev, 16, run, coarse_bar(case, hc, wc, nsplit))
@@ -433,10 +434,8 @@ def test_coarse_match_masked(dev, B, N, hc, wc, form, nsplit):
         f3, f2, kp = (arena.put(case[k], name=k) for k in ("f3", "f2", "kp"))
         dm, dq = arena.put(mask.flatten(1).view(U8), name="query_mask"), arena.put(qs, name="query_scale")
         o = coarse_buffers(arena, B, N, M, lazy)
-        o["wsp"] = P(ws(4 * nfloats), None)
-        hip.call("ophip_coarse_match_masked", P(f3), P(f2), P(kp), N * 3, B, N, M, wc, 0.08, 0.1, 2, 8.0, *coarse_tail(o), nsplit, 3, P(dm, U8), P(dq),
-                 hip.stream_handle())
-        del o["wsp"]
+        matchcall.coarse_match(f3, f2, kp, kpts_bstride=N * 3, nsplit=nsplit, query_mask=dm, query_scale=dq, **coarse_kw(wc),
+                               **coarse_outputs(o, ws(4 * nfloats)))
         return o
 
     def bar(out):
@@ -468,16 +467,13 @@ def test_fragment_planes_carried_into_coarse_matching(sd, dev, B, N, hc, wc):
         y3, y2 = arena.typed(x3.shape, F32, name="y3d"), arena.typed(x2.shape, F32, name="y2d")
         o = coarse_buffers(arena, B, N, M, False)
         ews, cws = ws(enc_bytes, "encoder workspace"), ws(4 * nfloats, "coarse workspace")
-        o["wsp"] = P(cws, None)
         pa, pb = ctypes.c_void_p(), ctypes.c_void_p()
         hip.call("ophip_coarse_frag_planes", P(cws, None), B, N, M, ctypes.byref(pa), ctypes.byref(pb))
         lo, hi = cws.data_ptr(), cws.data_ptr() + cws.numel()
         assert lo <= pa.value < pb.value < hi and pa.value % 64 == 0
         hip.call("ophip_encoder_layer_x3w8_frag", P(d3), P(d2), P(y3), P(y2), B, N, M, P(w, None), None, 1, 0, 0, P(ews, None), pa, pb,
                  hip.stream_handle())
-        hip.call("ophip_coarse_match", P(y3), P(y2), P(dk), N * 3, B, N, M, wc, 0.08, 0.1, 2, 8.0, *coarse_tail(o), 3 | hip.COARSE_PLANES_READY,
-                 hip.stream_handle())
-        del o["wsp"]
+        matchcall.coarse_match(y3, y2, dk, kpts_bstride=N * 3, nsplit=3, planes_ready=True, **coarse_kw(wc), **coarse_outputs(o, cws))
         return {**o, "y3d": y3, "y2d": y2}
 
     def bar(out):
@@ -547,10 +543,8 @@ def test_coarse_match_2d(dev, B, hw0, hw1, masked, form):
         d0, d1, dp = arena.put(f0, name="feat0"), arena.put(f1, name="feat1"), arena.put(pts0(L0, hw0[1]), name="points0")
         dm = [arena.put(m.flatten(1).view(U8), name=f"mask{k}") for k, m in enumerate((m0, m1))] if masked else []
         o = coarse_buffers(arena, B, L0, L1, lazy)
-        o["wsp"] = P(ws(4 * nfloats), None)
-        hip.call("ophip_coarse_match_2d_masked" if masked else "ophip_coarse_match_2d", P(d0), P(d1), P(dp), 0, B, L0, L1, hw0[1], hw1[1],
-                 tls.TEMP, tls.THR, tls.BD, 8.0, *coarse_tail(o), 3, *[P(t, U8) for t in dm], hip.stream_handle())
-        del o["wsp"]
+        matchcall.coarse_match_2d(d0, d1, dp, w0c=hw0[1], w1c=hw1[1], temperature=tls.TEMP, thr=tls.THR, border_rm=tls.BD, scale=8.0,
+                                  masks=dm or None, **coarse_outputs(o, ws(4 * nfloats)))
         return o
 
     def bar(out):
@@ -593,11 +587,8 @@ def test_coarse_match_2d_sinkhorn(dev, grids, iters, masked):
         dm = [arena.put(m.flatten(1).view(U8), name=f"mask{k}") for k, m in enumerate((m0, m1))] if masked else []
         o = coarse_buffers(arena, B, L0, L1, False)
         wsp = ws(4 * nfloats)
-        o["wsp"] = P(wsp, None)
-        tail = coarse_tail(o)
-        hip.call("ophip_coarse_match_2d_sinkhorn_masked" if masked else "ophip_coarse_match_2d_sinkhorn", P(d0), P(d1), P(dp), 0, B, L0, L1, w0, w1,
-                 bin_score, iters, prefilter, tls.THR, tls.BD, 8.0, *tail, *[P(t, U8) for t in dm], hip.stream_handle())
-        del o["wsp"]
+        matchcall.coarse_match_2d(d0, d1, dp, w0c=w0, w1c=w1, sinkhorn=(bin_score, iters, prefilter), thr=tls.THR, border_rm=tls.BD, scale=8.0,
+                                  masks=dm or None, **coarse_outputs(o, wsp))
         at = dual_at + (16 - (wsp.data_ptr() // 4 + dual_at) % 16) % 16               # "rounded up to a 64-byte boundary"
         assert 4 * (at + B * (up + vp)) <= wsp.numel()
         duals = wsp.view(F32)[at:at + B * (up + vp)]

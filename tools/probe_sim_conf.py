@@ -3,7 +3,7 @@ run beside sim(t + 1) would see.  Two workspaces / conf buffers; stream A runs t
 statistics merge + confidence pass of frame 0.  Prints each alone and both together (wall per iteration)."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from onepose_st_amd import hip
+from onepose_st_amd import hip, matchcall
 hip.load(); dev = torch.device("cuda:0")
 B, N, M, wc = 1, 7000, 4800, 80
 g = torch.Generator().manual_seed(0)
@@ -17,17 +17,11 @@ cap = B * N
 
 
 def frame():
-    return dict(conf=torch.empty(B, N, M, device=dev), ws=torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev),
-                ids=[torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)], mconf=torch.empty(cap, device=dev),
-                mk3=torch.empty(cap, 3, device=dev), mkc=torch.empty(cap, 2, device=dev), gt=torch.empty(cap, dtype=torch.uint8, device=dev),
-                cnt=torch.zeros(2, dtype=torch.int32, device=dev))
+    return dict(ws=torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev), lists=matchcall.MatchLists.empty(cap, dev, conf_shape=(B, N, M)))
 
 
 def call(fr, parts, stream):
-    P = hip.ptr
-    hip.call("ophip_coarse_match_masked", P(f3), P(f2), P(kp), 0, B, N, M, wc, 0.08, 0.1, 2, 8.0, P(fr["conf"]), P(fr["ws"]),
-             P(fr["ids"][0], torch.int64), P(fr["ids"][1], torch.int64), P(fr["ids"][2], torch.int64), P(fr["mconf"]), P(fr["mk3"]), P(fr["mkc"]),
-             P(fr["ids"][3], torch.int64), P(fr["gt"], torch.uint8), P(fr["cnt"], torch.int32), 3, parts, None, None, __import__("ctypes").c_void_p(stream.cuda_stream))
+    matchcall.coarse_match(f3, f2, kp, wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=3, lists=fr["lists"], conf=fr["lists"].conf, workspace=fr["ws"], parts=parts, stream=stream)
 
 
 A, Bs = torch.cuda.Stream(), torch.cuda.Stream()

@@ -2,7 +2,7 @@
 a screen for ordering bugs in the LDS-DMA ring of sim_frag (counted vmcnt + barrier).  Not part of the product."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from onepose_st_amd import hip
+from onepose_st_amd import hip, matchcall
 hip.load(); dev = torch.device("cuda:0")
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 bad = 0
@@ -16,20 +16,16 @@ for (B, N, hc, wc) in ((1, 7000, 60, 80), (2, 3000, 40, 52), (1, 1000, 30, 40), 
         cells = torch.randperm(M, generator=g)[:P]
         f2[b, cells] = f3[b, :P] * 1.5 + 0.1 * torch.randn(P, 256, generator=g)
     f3, f2, kp = f3.to(dev), f2.to(dev), torch.randn(B, N, 3, generator=g).to(dev)
-    cap = B * N
-    conf = torch.empty(B, N, M, device=dev)
     ws = torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev)
-    ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3)]
-    mconf, mk3, mkc = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    L = matchcall.MatchLists.empty(B * N, dev, conf_shape=(B, N, M))
+    conf = L.conf
     first = None
     n = reps if N < 10000 else max(10, reps // 10)
     for r in range(n):
         conf.fill_(float("nan"))
-        hip.call("ophip_coarse_match", hip.ptr(f3), hip.ptr(f2), hip.ptr(kp), kp.stride(0), B, N, M, wc, 0.08, 0.1, 2, 8.0, hip.ptr(conf), hip.ptr(ws),
-                 *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), None, None, hip.ptr(cnt, torch.int32), 3, hip.stream_handle())
-        K = int(cnt.item())
-        sig = (K, float(conf.double().sum().item()), int(ids[1][:K].sum().item()), int(ids[2][:K].sum().item()), float(mconf[:K].double().sum().item()))
+        matchcall.coarse_match(f3, f2, kp, wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=3, lists=L, conf=conf, workspace=ws)
+        K = int(L.count[0])
+        sig = (K, float(conf.double().sum().item()), int(L.i_ids[:K].sum().item()), int(L.j_ids[:K].sum().item()), float(L.mconf[:K].double().sum().item()))
         if first is None:
             first = sig
         elif sig != first:

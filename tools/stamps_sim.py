@@ -2,19 +2,16 @@
 Stamps per workgroup: 0 start | 1 end of the k-loop | 2 tile maximum known | 3 end of the store + statistics pass | 4 end."""
 import sys, os, ctypes, numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from onepose_st_amd import hip
+from onepose_st_amd import hip, matchcall
 dev = torch.device("cuda:0"); hip.load()
 N, M, wc = 7000, 4800, 80
 g = torch.Generator().manual_seed(0)
 f3, f2 = torch.randn(1, N, 256, generator=g).to(dev), torch.randn(1, M, 256, generator=g).to(dev)
 kp = torch.zeros(1, N, 3, device=dev)
-conf = torch.empty(1, N, M, device=dev); ws = torch.empty(hip.load().ophip_coarse_workspace_floats(1, N, M), device=dev)
-ids = [torch.empty(N, dtype=torch.int64, device=dev) for _ in range(3)]
-mconf, mk3, mkc = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 2, device=dev)
-cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+ws = torch.empty(hip.load().ophip_coarse_workspace_floats(1, N, M), device=dev)
+lists = matchcall.MatchLists.empty(N, dev, conf_shape=(1, N, M))
 def run():
-    hip.call("ophip_coarse_match", hip.ptr(f3), hip.ptr(f2), hip.ptr(kp), kp.stride(0), 1, N, M, wc, 0.08, 0.1, 2, 8.0, hip.ptr(conf), hip.ptr(ws),
-             *[hip.ptr(t, torch.int64) for t in ids], hip.ptr(mconf), hip.ptr(mk3), hip.ptr(mkc), None, None, hip.ptr(cnt, torch.int32), 3, hip.stream_handle())
+    matchcall.coarse_match(f3, f2, kp, wc=wc, temperature=0.08, thr=0.1, border_rm=2, scale=8.0, nsplit=3, lists=lists, conf=lists.conf, workspace=ws)
 for _ in range(3): run()
 nwg = 8 * 7 * 38
 buf = torch.zeros(nwg * 32, dtype=torch.int64, device=dev)

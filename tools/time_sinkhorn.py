@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from onepose_st_amd import hip  # noqa: E402
+from onepose_st_amd import hip, matchcall  # noqa: E402
 
 
 def timed(fn, iters, warmup):
@@ -51,7 +51,6 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = hip.load()
-    P, S = hip.ptr, hip.stream_handle()
     shapes = [("4096x4096", 1, (64, 64), (64, 64), False), ("15x4096x4096_shared_query", 15, (64, 64), (64, 64), True),
               ("4096x43200", 1, (64, 64), (180, 240), False)]
     for name, B, (h0, w0), (h1, w1), shared in shapes:
@@ -61,23 +60,16 @@ def main():
         f1 = torch.randn(1, L1, 256, device=dev, generator=g).expand(B, -1, -1).contiguous() if shared else torch.randn(B, L1, 256, device=dev, generator=g)
         ii = torch.arange(L0, device=dev)
         pts0 = torch.stack([(ii % w0).float() * 8, (ii // w0).float() * 8, torch.zeros(L0, device=dev)], 1)[None].contiguous()
-        conf = torch.empty(B, L0, L1, device=dev)
-        cap = B * L0
-        ids = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(4)]
-        mconf, mk0, mk1 = torch.empty(cap, device=dev), torch.empty(cap, 3, device=dev), torch.empty(cap, 2, device=dev)
-        gt = torch.empty(cap, dtype=torch.bool, device=dev)
-        cnt = torch.zeros(4, dtype=torch.int32, device=dev)
-        outs = (P(ids[0], torch.int64), P(ids[1], torch.int64), P(ids[2], torch.int64), P(mconf), P(mk0), P(mk1), P(ids[3], torch.int64),
-                P(gt, torch.bool), P(cnt, torch.int32))
+        lists = matchcall.MatchLists.empty(B * L0, dev, conf_shape=(B, L0, L1))
+        outs = dict(w0c=w0, w1c=w1, thr=0.2, border_rm=2, scale=8.0, lists=lists, conf=lists.conf)
         ws_d = torch.empty(lib.ophip_coarse_workspace_floats(B, L0, L1), device=dev)
         ws_s = torch.empty(lib.ophip_coarse_sinkhorn_workspace_floats(B, L0, L1), device=dev)
 
         def dual():
-            hip.call("ophip_coarse_match_2d", P(f0), P(f1), P(pts0), 0, B, L0, L1, w0, w1, 0.1, 0.2, 2, 8.0, P(conf), P(ws_d), *outs, 3, S)
+            matchcall.coarse_match_2d(f0, f1, pts0, temperature=0.1, workspace=ws_d, **outs)
 
         def skh(iters, prefilter):
-            return lambda: hip.call("ophip_coarse_match_2d_sinkhorn", P(f0), P(f1), P(pts0), 0, B, L0, L1, w0, w1, 1.0, iters, prefilter,
-                                    0.2, 2, 8.0, P(conf), P(ws_s), *outs, S)
+            return lambda: matchcall.coarse_match_2d(f0, f1, pts0, sinkhorn=(1.0, iters, prefilter), workspace=ws_s, **outs)
         t_dual = timed(dual, args.iters, args.warmup)
         run = skh(args.skh_iters, 1)
         t_skh = timed(run, args.iters, args.warmup)
@@ -103,7 +95,7 @@ def main():
                           "sweep_tbps": round(sweep_passes * mat / (t_sweep * 1e-6) / 1e12, 2),
                           "final_us": round(per["skh_final"], 1), "final_bytes": 3 * mat,
                           "final_tbps": round(3 * mat / (per["skh_final"] * 1e-6) / 1e12, 2)}), flush=True)
-        del conf, ws_d, ws_s, f0, f1
+        del lists, outs, ws_d, ws_s, f0, f1
         torch.cuda.empty_cache()
 
 
