@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 
 import torch
 
@@ -91,6 +92,42 @@ def stream_handle():
 def stream_arg(stream):
     """The handle of ``stream`` (a ``torch.cuda.Stream``); ``None``: the current stream"""
     return ctypes.c_void_p(stream.cuda_stream) if stream is not None else stream_handle()
+
+
+def _void_ptr(t):
+    """``void*``: a tensor of any dtype (packed byte blocks), or an address C handed out (``ophip_coarse_frag_planes``) as it is"""
+    return t if isinstance(t, ctypes.c_void_p) else ptr(t, None)
+
+
+def _byte_ptr(t):
+    """``unsigned char*`` (masks, gt_mask): bytes, as ``torch.bool`` or ``torch.uint8``"""
+    return ptr(t, torch.bool if t is not None and t.dtype == torch.bool else torch.uint8)
+
+
+_CONVERTER = {"int": int, "long long": int, "float": float, "double": float, "unsigned": lambda v: ctypes.c_uint(int(v)),
+              "float*": ptr, "long long*": functools.partial(ptr, dtype=torch.int64), "int*": functools.partial(ptr, dtype=torch.int32),
+              "unsigned char*": _byte_ptr, "void*": _void_ptr}
+_CONVERT = {}
+
+
+def converters(entry: str) -> dict:
+    """``{parameter name: converter}`` of ``entry`` without ``stream``, in the header's order and each from the header's C type of that
+    parameter (``const`` set aside); made on first use"""
+    if entry not in _CONVERT:
+        names = [n for _, n in PROTOTYPES[entry].params]
+        _CONVERT[entry] = ({n: _CONVERTER[c.replace("const ", "")] for c, n in PROTOTYPES[entry].params if n != "stream"}, names.index("stream"))
+    return _CONVERT[entry][0]
+
+
+def launch(entry: str, named: dict, stream=None) -> None:
+    """``call`` of ``entry`` on ``stream`` (a ``torch.cuda.Stream``; ``None``: the current one), every argument bound by its name in the
+    header and turned into what the header's C type of that parameter asks for: the launch step of ``matchcall`` and ``layercall``"""
+    conv = converters(entry)
+    if named.keys() != conv.keys():
+        order(entry, **named, stream=None)                     # TypeError: names every missing and every unknown parameter
+    args = [c(named[n]) for n, c in conv.items()]
+    args.insert(_CONVERT[entry][1], stream_arg(stream))
+    call(entry, *args)                                         # this module's ``call``: whoever replaces it (a test's spy) sees these calls too
 
 
 def seed_arg(seed):

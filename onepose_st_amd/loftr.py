@@ -68,7 +68,7 @@ import ctypes
 import torch
 import torch.nn as nn
 
-from . import hip, host_math, packing
+from . import hip, host_math, layercall, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .lazy_conf import LazyConfMatrixBase
@@ -196,7 +196,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         V, L0, L1 = int(V), int(hw0_c[0]) * int(hw0_c[1]), int(hw1_c[0]) * int(hw1_c[1])
         rows = 4 * V * (L0 + L1) * 256 * 4
         Lm = max(L0, L1)
-        enc = lib.ophip_encoder_full_stream_workspace_bytes(V, Lm, Lm) if self.coarse_full else lib.ophip_encoder_x3w8_workspace_bytes(V, L0, L1)
+        enc = layercall.workspace_bytes("full", V, Lm, Lm, stream_form=True) if self.coarse_full else layercall.workspace_bytes("bf16x3", V, L0, L1)
         cws = 4 * (lib.ophip_coarse_sinkhorn_workspace_floats if self.sinkhorn else lib.ophip_coarse_workspace_floats)(V, L0, L1)
         lists = (57 + 24) * V * L0 + 64 * L0 + 8192
         return int(rows + enc + cws + lists + (0 if lazy else 4 * V * L0 * L1))
@@ -227,22 +227,19 @@ class LoFTR_for_OnePose_Plus(nn.Module):
     def _coarse_linear(self, Wc, fc0, fc1, shared1, V, L0, L1, masks=None):
         """``masks``: None or the flattened padding masks ``(m0 [V, L0], m1 [V, L1])`` (bool, contiguous; a shared query's mask already
         repeated with its rows)"""
-        call, P, S = hip.call, hip.ptr, hip.stream_handle()
         x0 = fc0.contiguous()
         x1 = (fc1.expand(V, -1, -1) if shared1 else fc1).contiguous()
-        ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(V, L0, L1), dtype=torch.uint8, device=x0.device)
-        mk = () if masks is None else (P(masks[0], torch.bool), P(masks[1], torch.bool))
-        sfx = "" if masks is None else "_masks"
+        fixed = dict(mode="bf16x3", workspace=layercall.workspace("bf16x3", V, L0, L1, x0.device), masks=masks)
         for w, name in zip(Wc, self.loftr_coarse.layer_names):
             if name == "self":
                 b0, b1 = torch.empty_like(x0), torch.empty_like(x1)
-                call("ophip_encoder_layer_x3w8" + sfx, P(x0), P(x1), P(b0), P(b1), V, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None), *mk, S)
+                layercall.layer(x0, x1, b0, b1, wpack=w, is_cross=0, **fixed)
                 x0, x1 = b0, b1
             else:
                 n0 = torch.empty_like(x0)              # image 0 against image 1
-                call("ophip_encoder_layer_x3w8_streams" + sfx, P(x0), P(x1), P(n0), None, V, L0, L1, P(w, None), 1, 1, P(ws, None), *mk, S)
+                layercall.layer(x0, x1, n0, None, wpack=w, is_cross=1, streams=1, **fixed)
                 n1 = torch.empty_like(x1)              # image 1 against the UPDATED image 0
-                call("ophip_encoder_layer_x3w8_streams" + sfx, P(n0), P(x1), None, P(n1), V, L0, L1, P(w, None), 1, 2, P(ws, None), *mk, S)
+                layercall.layer(n0, x1, None, n1, wpack=w, is_cross=1, streams=2, **fixed)
                 x0, x1 = n0, n1
         return x0, x1
 
@@ -250,16 +247,12 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         """full attention, one query stream per launch; ``x1 [1, L1, 256]`` against ``x0 [V, L0, 256]`` is one query image shared by the
         V pairs: it is read with batch stride 0 (projected once) until the first cross layer gives every pair its own rows, and a self
         layer before that runs on it once"""
-        call, P, S = hip.call, hip.ptr, hip.stream_handle()
         Lm = max(L0, L1)
-        ws = torch.empty(hip.load().ophip_encoder_full_stream_workspace_bytes(V, Lm, Lm), dtype=torch.uint8, device=x0.device)
+        ws = layercall.workspace("full", V, Lm, Lm, x0.device, stream_form=True)
 
         def layer(x, src, w):
-            B = max(x.shape[0], src.shape[0])
-            y = torch.empty(B, x.shape[1], 256, device=x.device)
-            bs = lambda t: t.stride(0) if t.shape[0] > 1 else 0
-            call("ophip_encoder_layer_full_x3_stream", P(x), bs(x), P(src), bs(src), P(y), B, x.shape[1], src.shape[1], P(w, None),
-                 P(ws, None), S)
+            y = torch.empty(max(x.shape[0], src.shape[0]), x.shape[1], 256, device=x.device)
+            layercall.layer_full_stream(x, src, y, wpack=w, workspace=ws)
             return y
         for w, name in zip(Wc, self.loftr_coarse.layer_names):
             if name == "self":

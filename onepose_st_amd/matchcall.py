@@ -7,15 +7,12 @@ Each call is two steps.  ``plan_*`` is pure: it chooses the entry point and retu
 header's C type of that parameter asks for and calls the entry on ``stream`` (a ``torch.cuda.Stream``; ``None``: the current one)."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import hip
 
 _TAIL = ("b_ids", "i_ids", "j_ids", "mconf", "mk3d", "mkc", "m_bids", "gt_mask", "count")
-_POINTER = {"float*": torch.float32, "long long*": torch.int64, "int*": torch.int32, "void*": None}
-_SCALAR = {"int": int, "long long": int, "float": float, "double": float, "unsigned": lambda v: ctypes.c_uint(int(v))}
+launch = hip.launch          # the launch step, shared with layercall
 
 
 class MatchLists:
@@ -42,26 +39,6 @@ class MatchLists:
     def named(self, mk3d, mkc):
         """under the header's parameter names; ``mk3d`` and ``mkc``: those of the two keypoint lists"""
         return {{"mk3d": mk3d, "mkc": mkc}.get(k, k): getattr(self, k) for k in _TAIL}
-
-
-def _converter(ctype):
-    bare = ctype.replace("const ", "")
-    if bare in _SCALAR:
-        return _SCALAR[bare]
-    if bare == "unsigned char*":                     # masks and gt_mask: bytes, as torch.bool or torch.uint8
-        return lambda t: hip.ptr(t, torch.bool if t is not None and t.dtype == torch.bool else torch.uint8)
-    return lambda t, dtype=_POINTER[bare]: hip.ptr(t, dtype)
-
-
-# entry -> {parameter name: converter} without ``stream``, from the header's own C types
-_CONVERT = {name: {n: _converter(c) for c, n in proto.params if n != "stream"}
-            for name, proto in hip.PROTOTYPES.items() if name.startswith(("ophip_coarse_match", "ophip_fine_refine"))}
-
-
-def launch(entry, named, stream=None):
-    conv = _CONVERT[entry]
-    args = {n: conv[n](v) if n in conv else v for n, v in named.items()}          # (a name the header lacks goes on: call_named says so)
-    hip.call_named(entry, **args, stream=hip.stream_arg(stream))
 
 
 def _floats(helper, x0, x1):

@@ -29,7 +29,7 @@ from collections import namedtuple
 import torch
 import torch.nn as nn
 
-from . import hip, host_math, ops, packing
+from . import hip, host_math, layercall, ops, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .config import encoder_layer_names, validate_config
@@ -489,36 +489,27 @@ class OnePosePlus_model(nn.Module):
             lib_call("ophip_transpose_cl", P(src), P(x3d), Bo, 256, fi.N, hip.stream_handle())
         return x3d
 
-    def _coarse_layer_launch(self, fi, S):
+    def _coarse_layer_launch(self, fi, S, rows):
         """The coarse encoder layer in this model's arithmetic mode: ``launch(li, name, x3d, x2d, y3d, y2d)`` runs layer ``li`` (``name``
-        "self" or "cross") from the x rows into the y rows on stream ``S``.  A mode is its workspace, entry point and argument tuple."""
-        lib, lib_call, P = hip.load(), hip.call, hip.ptr
-        B, N, M, W = fi.B, fi.N, fi.M, fi.W
-        names = self.loftr_coarse.layer_names
-        sfx, pm = ("", ()) if fi.qmask is None else ("_masked", (P(fi.qmask, torch.uint8),))
-        u8 = dict(device=fi.dev, dtype=torch.uint8)
-        if self.precision == "f32" or self.coarse_full:
-            # exact f32 (csrc/encoder.hip), or full (softmax) attention: projections, split-bf16 flash attention, tail
-            # (csrc/encoder_full.hip; its entry point takes no mask); both read the f32 layer block
-            if self.precision == "f32":
-                entry, ws, mask = "ophip_encoder_layer" + sfx, torch.empty(lib.ophip_encoder_workspace_floats(B, N, M), device=fi.dev, dtype=torch.float32), pm
-            else:
-                entry, ws, mask = "ophip_encoder_layer_full_x3", torch.empty(lib.ophip_encoder_full_workspace_bytes(B, N, M), **u8), ()
+        "self" or "cross") from the x rows into the y rows on stream ``S`` (a ``torch.cuda.Stream``).  A mode is its workspace, weight
+        blocks and whether its layers chain.  The entry and what a frame's layers share are planned once, here, from the first layer's
+        ``rows`` (x3d, x2d, y3d, y2d); a call sets its own rows, weights and chain state (the staged path's host cost, section 6q)."""
+        # "f32": exact (csrc/encoder.hip); "full": softmax attention -- projections, split-bf16 flash attention, tail (csrc/encoder_full.hip;
+        # its entry point takes no mask); both read the f32 layer block.  "bf16x3": 16-token tiles, one eight-wave workgroup per CU, per-wave
+        # weight streams (csrc/encoder_x3w8.hip); "bf16": the plain-bf16 kernel.  In the last two, layer li's attn_apply also emits layer
+        # li+1's K/V partial slabs from the on-chip output tile.
+        mode = "full" if self.coarse_full and self.precision != "f32" else self.precision
+        Wl = fi.W[{"f32": "coarse", "full": "coarse", "bf16x3": "coarse_x3", "bf16": "coarse_bf16"}[mode]]
+        last = len(self.loftr_coarse.layer_names) - 1
+        entry, named = layercall.plan_layer(*rows, mode=mode, wpack=None, is_cross=0, workspace=layercall.workspace(mode, fi.B, fi.N, fi.M, fi.dev),
+                                            query_mask=None if mode == "full" else fi.qmask)
+        chained = "slot" in named
 
-            def launch(li, name, x3d, x2d, y3d, y2d):
-                lib_call(entry, P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(W["coarse"][li]), 1 if name == "cross" else 0, P(ws, None), *mask, S)
-        else:
-            # "bf16x3": 16-token tiles, one eight-wave workgroup per CU, per-wave weight streams (csrc/encoder_x3w8.hip); "bf16": the plain-bf16
-            # kernel with nsplit 1.  Layer li's attn_apply also emits layer li+1's K/V partial slabs from the on-chip output tile.
-            if self.precision == "bf16x3":
-                entry, Wl, nsplit, ws = "ophip_encoder_layer_x3w8", W["coarse_x3"], (), torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(B, N, M), **u8)
-            else:
-                entry, Wl, nsplit, ws = "ophip_encoder_layer_bf16", W["coarse_bf16"], (1,), torch.empty(lib.ophip_encoder_bf16_workspace_bytes(B, N, M), **u8)
-
-            def launch(li, name, x3d, x2d, y3d, y2d):
-                nxt = Wl[li + 1] if li + 1 < len(names) else None
-                lib_call(entry + sfx, P(x3d), P(x2d), P(y3d), P(y2d), B, N, M, P(Wl[li], None), P(nxt, None), *nsplit,
-                         1 if name == "cross" else 0, 1 if li > 0 else 0, li & 1, P(ws, None), *pm, S)
+        def launch(li, name, x3d, x2d, y3d, y2d):
+            named.update(x3d=x3d, x2d=x2d, y3d=y3d, y2d=y2d, wpack=Wl[li], is_cross=1 if name == "cross" else 0)
+            if chained:
+                named.update(wpack_next=Wl[li + 1] if li < last else None, kv_from_prev=1 if li > 0 else 0, slot=li & 1)
+            hip.launch(entry, named, S)
         return launch
 
     def _coarse_encoder_stage(self, fi, x3d, x2d, main, fkey):
@@ -531,7 +522,7 @@ class OnePosePlus_model(nn.Module):
         prev = self._fine_streams.get(fkey)
         if (names or self.precision == "f32") and self.overlap_fine and prev is not None and prev[1] is not None:
             main.wait_event(prev[1])          # (the exact-f32 mode waits with no layer to run as well)
-        launch = self._coarse_layer_launch(fi, ctypes.c_void_p(main.cuda_stream))
+        launch = self._coarse_layer_launch(fi, main, (x3d, x2d, y3d, y2d))
         for li, name in enumerate(names):
             launch(li, name, x3d, x2d, y3d, y2d)
             # Ping-pong: the layer's outputs become the next layer's inputs, its inputs the next outputs.  The one invariant of this
@@ -656,7 +647,6 @@ class OnePosePlus_model(nn.Module):
         """The object's cache entry ``{"x3d", "y3d0", "kv1", "ev"}`` (``ophip_object_cache``), built on a miss on ``stream`` with the kernels a
         frame would run.  Keyed on the object tensors' storage + version and the packed weights; ``Bo`` = 1 rows when the batch shares one
         object block (stride-0 expand / batch-1 tensors under a larger query batch), else B."""
-        lib_call, P = hip.call, hip.ptr
         B, N, dev, kpts_d, desc_in_d, W = fi.B, fi.N, fi.dev, fi.kpts_d, fi.desc_in_d, fi.W
         Bo = 1 if (B > 1 and kpts_d.shape[0] == 1 and desc_in_d.shape[0] == 1) else B
         names = self.loftr_coarse.layer_names
@@ -672,12 +662,10 @@ class OnePosePlus_model(nn.Module):
             x3d = self._encode_keypoints(fi, Bo)
             y3d0 = kv1 = None
             if deep:
-                lib = hip.load()
                 y3d0 = torch.empty(Bo, N, 256, device=dev, dtype=torch.float32)
-                kv1 = torch.empty(Bo, lib.ophip_encoder_x3w8_kv_block_bytes(), device=dev, dtype=torch.uint8)
-                ws = torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(Bo, N, 1), device=dev, dtype=torch.uint8)
-                lib_call("ophip_encoder_object_x3w8", P(x3d), Bo, N, P(W["coarse_x3"][0], None), P(W["coarse_x3"][1], None), P(ws, None),
-                         P(y3d0), P(kv1, None), 1 if masked else 0, hip.stream_handle())
+                kv1 = torch.empty(Bo, layercall.kv_block_bytes(), device=dev, dtype=torch.uint8)
+                layercall.object_rows(x3d, wpack0=W["coarse_x3"][0], wpack1=W["coarse_x3"][1], workspace=layercall.workspace("bf16x3", Bo, N, 1, dev),
+                                      y3d0=y3d0, kv1=kv1, masked_frames=1 if masked else 0)
             ev = torch.cuda.Event()
             ev.record(stream)
         ent = {"key": ckey, "x3d": x3d, "y3d0": y3d0, "kv1": kv1, "ev": ev, "keep": (kpts_d, desc_in_d, W)}      # the key's tensors stay alive with the entry

@@ -27,7 +27,7 @@ import itertools
 
 import torch
 
-from . import hip
+from . import hip, layercall
 from .matchcall import MatchLists, coarse_match, fine_refine
 
 _lib = torch.library.Library("onepose_hip", "DEF")
@@ -68,18 +68,17 @@ def _kpt_encode(keypoints3d, desc_bcn, wpack, out_bnc):
 
 
 def _layer_args(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace):
-    B, L3, _ = x3d.shape
-    L2 = x2d.shape[1]
-    need = hip.load().ophip_encoder_x3w8_workspace_bytes(B, L3, L2)
+    """the op's own contract (dense float32 rows, a workspace of the helper's size), then ``layercall.layer``'s arguments"""
+    need = layercall.workspace_bytes("bf16x3", x3d.shape[0], x3d.shape[1], x2d.shape[1])
     if workspace.numel() * workspace.element_size() < need:
         raise ValueError(f"workspace: {need} bytes needed (ophip_encoder_x3w8_workspace_bytes)")
-    return (hip.ptr(_f32(x3d, "x3d")), hip.ptr(_f32(x2d, "x2d")), hip.ptr(_f32(y3d, "y3d")), hip.ptr(_f32(y2d, "y2d")),
-            B, L3, L2, hip.ptr(wpack, None), hip.ptr(wpack_next, None), int(is_cross), int(kv_from_prev), int(slot), hip.ptr(workspace, None))
+    return (_f32(x3d, "x3d"), _f32(x2d, "x2d"), _f32(y3d, "y3d"), _f32(y2d, "y2d")), dict(
+        mode="bf16x3", wpack=wpack, wpack_next=wpack_next, is_cross=is_cross, kv_from_prev=kv_from_prev, slot=slot, workspace=workspace)
 
 
 def _encoder_layer_x3w8(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace):
-    hip.call("ophip_encoder_layer_x3w8", *_layer_args(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace),
-             hip.stream_handle())
+    rows, kw = _layer_args(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace)
+    layercall.layer(*rows, **kw)
 
 
 def _encoder_layer_x3w8_frag(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace, coarse_workspace):
@@ -90,8 +89,8 @@ def _encoder_layer_x3w8_frag(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv
         raise ValueError("coarse_workspace: ophip_coarse_workspace_floats(B, N, M) float32 elements needed")
     p3, p2 = ctypes.c_void_p(), ctypes.c_void_p()
     hip.call("ophip_coarse_frag_planes", hip.ptr(coarse_workspace), B, L3, L2, ctypes.byref(p3), ctypes.byref(p2))
-    hip.call("ophip_encoder_layer_x3w8_frag", *_layer_args(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace),
-             p3, p2, hip.stream_handle())
+    rows, kw = _layer_args(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace)
+    layercall.layer(*rows, frag=(p3, p2), **kw)
 
 
 def _coarse_match(feat3d, feat2d, keypoints3d, wc, temperature, thr, border_rm, scale, nsplit):

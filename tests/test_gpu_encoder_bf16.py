@@ -32,7 +32,7 @@ layers 1 and 2 read the device's previous output, for which no stand-in is compu
 import pytest
 import torch
 
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, layercall, packing
 from tests import bf16_faithful as bf
 
 pytestmark = pytest.mark.gpu
@@ -54,14 +54,14 @@ def wpack(sd, dev):
     def get(p):
         if p not in cache:
             cache[p] = packing.pack_coarse_layer_bf16(sd, p).to(dev)
-            assert cache[p].numel() == hip.load().ophip_encoder_bf16_wpack_bytes()
+            assert cache[p].numel() == layercall.wpack_bytes("bf16")
         return cache[p]
     return get
 
 
 def workspace(dev, B, L3, L2):
     """every byte 0xFF: NaN as f32 and as bf16"""
-    return torch.full((hip.load().ophip_encoder_bf16_workspace_bytes(B, L3, L2),), 255, dtype=torch.uint8, device=dev)
+    return torch.full((layercall.workspace_bytes("bf16", B, L3, L2),), 255, dtype=torch.uint8, device=dev)
 
 
 def layer(d3, d2, w, ws, cross, mask=None, w_next=None, kv_from_prev=0, slot=0, nsplit=1, y3=None, y2=None):
@@ -69,13 +69,8 @@ def layer(d3, d2, w, ws, cross, mask=None, w_next=None, kv_from_prev=0, slot=0, 
     B, L3, L2 = d3.shape[0], d3.shape[1], d2.shape[1]
     y3 = torch.full_like(d3, float("nan")) if y3 is None else y3
     y2 = torch.full_like(d2, float("nan")) if y2 is None else y2
-    A = hip.ptr
-    head = (A(d3), A(d2), A(y3), A(y2), B, L3, L2, A(w, None), A(w_next, None), nsplit, int(cross), kv_from_prev, slot, A(ws, None))
-    if mask is None:
-        hip.call("ophip_encoder_layer_bf16", *head, hip.stream_handle())
-    else:
-        dm = mask.to(d3.device).view(torch.uint8).contiguous()
-        hip.call("ophip_encoder_layer_bf16_masked", *head, A(dm, torch.uint8), hip.stream_handle())
+    layercall.layer(d3, d2, y3, y2, mode="bf16", wpack=w, wpack_next=w_next, nsplit=nsplit, is_cross=int(cross), kv_from_prev=kv_from_prev, slot=slot,
+                    workspace=ws, query_mask=None if mask is None else mask.to(d3.device).view(torch.uint8).contiguous())
     torch.cuda.synchronize()
     off = bf.kv_block_offset(ws.data_ptr(), B, L3, L2)
     blk = ws[off:off + B * 2 * bf.KV_BLOCK_BYTES].cpu().view(B, 2, bf.KV_BLOCK_BYTES)
@@ -180,8 +175,9 @@ def test_arguments(dev, wpack):
     with pytest.raises(ValueError):
         layer(x3, x2, w, ws, 0, mask, slot=2)
     y3, y2 = torch.full_like(x3, float("nan")), torch.full_like(x2, float("nan"))
+    entry, named = layercall.plan_layer(x3, x2, y3, y2, mode="bf16", wpack=w, is_cross=0, workspace=ws, query_mask=mask)
+    assert entry == "ophip_encoder_layer_bf16_masked"
     with pytest.raises(ValueError):
-        hip.call("ophip_encoder_layer_bf16_masked", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), None, 1, 0, 0, 0,
-                 hip.ptr(ws, None), None, hip.stream_handle())
+        hip.launch(entry, dict(named, query_mask=None))                             # the masked entry refuses a NULL mask
     torch.cuda.synchronize()
     assert bool(torch.isnan(y3).all()) and bool(torch.isnan(y2).all())              # a refused call launches nothing

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, layercall, packing
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.synthetic import make_synthetic_inputs
 from tests import full_attention_oracle as foracle
@@ -78,11 +78,10 @@ def test_encoder_layer_full(sd, dev, cross, B, L3, L2):
         else:
             r2, r3 = foracle.encoder_layer(sd, p, x2, x2, 8), foracle.encoder_layer(sd, p, x3, x3, 8)
     w = packing.pack_coarse_layer(sd, p).to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_full_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
+    kw = dict(mode="full", wpack=w, is_cross=cross, workspace=layercall.workspace("full", B, L3, L2, dev))
     d3, d2 = x3.to(dev), x2.to(dev)
     y3, y2 = torch.full_like(d3, float("nan")), torch.full_like(d2, float("nan"))
-    hip.call("ophip_encoder_layer_full_x3", hip.ptr(d3), hip.ptr(d2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w), cross,
-             hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(d3, d2, y3, y2, **kw)
     e3, e2 = (y3.cpu() - r3).abs().max().item(), (y2.cpu() - r2).abs().max().item()
     print(f"full cross={cross} B={B} L=({L3},{L2}): max abs err 3D {e3:.3e} 2D {e2:.3e}")
     close(y3, r3, rtol=3e-4, atol=1e-4, msg="3D stream")
@@ -90,13 +89,10 @@ def test_encoder_layer_full(sd, dev, cross, B, L3, L2):
     # a batch element's rows do not depend on its batch position
     if B > 1:
         y3b, y2b = torch.empty_like(d3[1:2]), torch.empty_like(d2[1:2])
-        ws1 = torch.empty(hip.load().ophip_encoder_full_workspace_bytes(1, L3, L2), dtype=torch.uint8, device=dev)
-        hip.call("ophip_encoder_layer_full_x3", hip.ptr(d3[1:2].contiguous()), hip.ptr(d2[1:2].contiguous()), hip.ptr(y3b), hip.ptr(y2b),
-                 1, L3, L2, hip.ptr(w), cross, hip.ptr(ws1, None), hip.stream_handle())
+        layercall.layer(d3[1:2].contiguous(), d2[1:2].contiguous(), y3b, y2b, **dict(kw, workspace=layercall.workspace("full", 1, L3, L2, dev)))
         assert torch.equal(y3b, y3[1:2]) and torch.equal(y2b, y2[1:2])
     with pytest.raises(ValueError):
-        hip.call("ophip_encoder_layer_full_x3", hip.ptr(d3), hip.ptr(d2), hip.ptr(d3), hip.ptr(y2), B, L3, L2, hip.ptr(w), cross,
-                 hip.ptr(ws, None), hip.stream_handle())
+        layercall.layer(d3, d2, d3, y2, **kw)
 
 
 def _attention_f64(q, k, v):

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from onepose_st_amd import hip, loftr, packing
+from onepose_st_amd import hip, layercall, loftr, packing
 from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
 from tests import loftr_full_oracle as lfo
 from tests import test_gpu_loftr as tgl
@@ -62,11 +62,13 @@ close = tgl.close
 # ------------------------------------------------------------------------------------------------
 # one-stream coarse layer
 # ------------------------------------------------------------------------------------------------
-def _layer(dev, w, x, xbs, src, sbs, B, L, S, y=None):
-    ws = torch.empty(hip.load().ophip_encoder_full_stream_workspace_bytes(B, L, S), dtype=torch.uint8, device=dev)
-    y = torch.full((B, L, 256), float("nan"), device=dev) if y is None else y
-    hip.call("ophip_encoder_layer_full_x3_stream", hip.ptr(x), xbs, hip.ptr(src), sbs, hip.ptr(y), B, L, S, hip.ptr(w), hip.ptr(ws, None),
-             hip.stream_handle())
+def _layer(dev, w, x, src, nb, y=None, **override):
+    """``nb``: the batch extent of the output and the workspace; ``override``: header arguments put in place of the planned ones (a batch
+    extent, a stride the plan would not choose)"""
+    L, S = x.shape[1], src.shape[1]
+    y = torch.full((nb, L, 256), float("nan"), device=dev) if y is None else y
+    entry, named = layercall.plan_layer_full_stream(x, src, y, wpack=w, workspace=layercall.workspace("full", nb, L, S, dev, stream_form=True))
+    hip.launch(entry, dict(named, **override))
     return y
 
 
@@ -87,21 +89,19 @@ def test_one_stream_layer(lsd, dev, mode, B, L, S):
     w = packing.pack_coarse_layer(lsd, p).to(dev)
     dx = x.to(dev)
     ds = dx if mode == "self" else src.to(dev)
-    xbs = 0 if nx == 1 else L * 256
-    sbs = 0 if ns == 1 else S * 256
-    y = _layer(dev, w, dx, xbs, ds, sbs, B, L, S)
+    y = _layer(dev, w, dx, ds, B)
     err = (y.cpu() - ref).abs().max().item()
     print(f"one-stream {mode} B={B} L={L} S={S}: max abs err {err:.3e}")
     close(y, ref, 3e-4, 1e-4, f"{mode} layer")
     # a batch element's rows are those of a B = 1 call on its own inputs
     for b in range(1, B):
         xb, sb = dx[min(b, nx - 1)][None].contiguous(), ds[min(b, ns - 1)][None].contiguous()
-        yb = _layer(dev, w, xb, L * 256, xb if mode == "self" else sb, S * 256, 1, L, S)
+        yb = _layer(dev, w, xb, xb if mode == "self" else sb, 1, x_bstride=L * 256, src_bstride=S * 256)
         assert torch.equal(yb[0], y[b]), (mode, b)
     with pytest.raises(ValueError):                    # in place
-        _layer(dev, w, dx, xbs, ds, sbs, nx, L, S, y=dx)
+        _layer(dev, w, dx, ds, nx, y=dx, B=nx)
     with pytest.raises(ValueError):                    # a stride that overlaps rows
-        _layer(dev, w, dx, 128, ds, sbs, B, L, S)
+        _layer(dev, w, dx, ds, B, x_bstride=128)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from onepose_st_amd import hip, loftr, packing
+from onepose_st_amd import hip, layercall, loftr, packing
 from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
 from tests import loftr_masked_oracle as lmo
 from tests.loftr_helpers import planted_pair
@@ -77,30 +77,25 @@ def test_encoder_layer_with_two_masks_against_the_oracle(lsd, dev, B, hw0, hw1):
     m0, m1 = rect_masks(B, hw0, ext0).flatten(1), rect_masks(B, hw1, ext1).flatten(1)
     p = "loftr_coarse.layers.3."
     w = packing.pack_coarse_layer_x3w8(lsd, p).to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, L0, L1), dtype=torch.uint8, device=dev)
     d0, d1, dm0, dm1 = x0.to(dev), x1.to(dev), m0.to(dev), m1.to(dev)
-    P, S = hip.ptr, hip.stream_handle()
+    kw = dict(mode="bf16x3", wpack=w, workspace=layercall.workspace("bf16x3", B, L0, L1, dev))
     tol = dict(rtol=3e-4, atol=1e-4)
     # self
     y0, y1 = torch.full_like(d0, float("nan")), torch.full_like(d1, float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_masks", P(d0), P(d1), P(y0), P(y1), B, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None),
-             P(dm0, torch.bool), P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, y0, y1, is_cross=0, masks=(dm0, dm1), **kw)
     r0, r1 = lmo.masked_layer(lsd, p, x0, x0, m0, m0), lmo.masked_layer(lsd, p, x1, x1, m1, m1)
     assert (r0 - lmo.masked_layer(lsd, p, x0, x0)).abs().max() > 1e-2          # the masks matter
     close(y0, r0, msg="self, stream 0", **tol)
     close(y1, r1, msg="self, stream 1", **tol)
     # cross: image 0 against image 1, then image 1 against image 0 (one stream per launch)
     n0 = torch.full_like(d0, float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_streams_masks", P(d0), P(d1), P(n0), None, B, L0, L1, P(w, None), 1, 1, P(ws, None),
-             P(dm0, torch.bool), P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, n0, None, is_cross=1, streams=1, masks=(dm0, dm1), **kw)
     close(n0, lmo.masked_layer(lsd, p, x0, x1, m0, m1), msg="cross, image 0 against image 1", **tol)
     n1 = torch.full_like(d1, float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_streams_masks", P(d0), P(d1), None, P(n1), B, L0, L1, P(w, None), 1, 2, P(ws, None),
-             P(dm0, torch.bool), P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, None, n1, is_cross=1, streams=2, masks=(dm0, dm1), **kw)
     close(n1, lmo.masked_layer(lsd, p, x1, x0, m1, m0), msg="cross, image 1 against image 0", **tol)
     # one mask NULL: that stream unmasked
-    hip.call("ophip_encoder_layer_x3w8_streams_masks", P(d0), P(d1), P(n0), None, B, L0, L1, P(w, None), 1, 1, P(ws, None),
-             None, P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, n0, None, is_cross=1, streams=1, masks=(None, dm1), **kw)
     close(n0, lmo.masked_layer(lsd, p, x0, x1, None, m1), msg="cross, mask0 NULL", **tol)
     assert torch.equal(dm0.cpu(), m0) and torch.equal(dm1.cpu(), m1)                # the masks are read only
 

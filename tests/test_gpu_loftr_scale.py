@@ -19,7 +19,7 @@ import copy
 import pytest
 import torch
 
-from onepose_st_amd import hip, loftr, matchcall, packing
+from onepose_st_amd import hip, layercall, loftr, matchcall, packing
 from onepose_st_amd.synthetic import make_synthetic_loftr_state_dict
 from tests import loftr_masked_oracle as lmo
 from tests import test_gpu_loftr_masked as tglm
@@ -462,42 +462,37 @@ def test_encoder_layer_at_size(lsd, dev, name):
     p = "loftr_coarse.layers.3."
     sd = {k: v.to(dev).double() for k, v in lsd.items() if k.startswith(p)}
     w = packing.pack_coarse_layer_x3w8(lsd, p).to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, L0, L1), dtype=torch.uint8, device=dev)
     d0, d1, dm0, dm1 = x0.to(dev), x1.to(dev), m0.to(dev), m1.to(dev)
     r0, r1, rm0, rm1 = d0.double(), d1.double(), dm0, dm1
-    P, S = hip.ptr, hip.stream_handle()
+    kw = dict(mode="bf16x3", wpack=w, workspace=layercall.workspace("bf16x3", B, L0, L1, dev))
     layer = lambda x, s, mx=None, ms=None: lmo.masked_layer(sd, p, x, s, mx, ms)
     check = lambda got, want, what: _close_dev(got, want, 3e-4, 1e-4, f"{name}: {what}")
     # masked self
     y0, y1 = torch.full_like(d0, float("nan")), torch.full_like(d1, float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_masks", P(d0), P(d1), P(y0), P(y1), B, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None),
-             P(dm0, torch.bool), P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, y0, y1, is_cross=0, masks=(dm0, dm1), **kw)
     check(y0, layer(r0, r0, rm0, rm0), "masked self, stream 0")
     check(y1, layer(r1, r1, rm1, rm1), "masked self, stream 1")
     # masked cross, one direction per launch, then mask0 NULL
     n0, n1 = torch.full_like(d0, float("nan")), torch.full_like(d1, float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_streams_masks", P(d0), P(d1), P(n0), None, B, L0, L1, P(w, None), 1, 1, P(ws, None),
-             P(dm0, torch.bool), P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, n0, None, is_cross=1, streams=1, masks=(dm0, dm1), **kw)
     check(n0, layer(r0, r1, rm0, rm1), "masked cross, image 0 against image 1")
-    hip.call("ophip_encoder_layer_x3w8_streams_masks", P(d0), P(d1), None, P(n1), B, L0, L1, P(w, None), 1, 2, P(ws, None),
-             P(dm0, torch.bool), P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, None, n1, is_cross=1, streams=2, masks=(dm0, dm1), **kw)
     check(n1, layer(r1, r0, rm1, rm0), "masked cross, image 1 against image 0")
     n0.fill_(float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_streams_masks", P(d0), P(d1), P(n0), None, B, L0, L1, P(w, None), 1, 1, P(ws, None),
-             None, P(dm1, torch.bool), S)
+    layercall.layer(d0, d1, n0, None, is_cross=1, streams=1, masks=(None, dm1), **kw)
     check(n0, layer(r0, r1, None, rm1), "masked cross, mask0 NULL")
     assert torch.equal(dm0.cpu(), m0) and torch.equal(dm1.cpu(), m1)                # the masks are read only
     # the unmasked entries
     y0.fill_(float("nan"))
     y1.fill_(float("nan"))
-    hip.call("ophip_encoder_layer_x3w8", P(d0), P(d1), P(y0), P(y1), B, L0, L1, P(w, None), None, 0, 0, 0, P(ws, None), S)
+    layercall.layer(d0, d1, y0, y1, is_cross=0, **kw)
     check(y0, layer(r0, r0), "self, stream 0")
     check(y1, layer(r1, r1), "self, stream 1")
     n0.fill_(float("nan"))
     n1.fill_(float("nan"))
-    hip.call("ophip_encoder_layer_x3w8_streams", P(d0), P(d1), P(n0), None, B, L0, L1, P(w, None), 1, 1, P(ws, None), S)
+    layercall.layer(d0, d1, n0, None, is_cross=1, streams=1, **kw)
     check(n0, layer(r0, r1), "cross, image 0 against image 1")
-    hip.call("ophip_encoder_layer_x3w8_streams", P(d0), P(d1), None, P(n1), B, L0, L1, P(w, None), 1, 2, P(ws, None), S)
+    layercall.layer(d0, d1, None, n1, is_cross=1, streams=2, **kw)
     check(n1, layer(r1, r0), "cross, image 1 against image 0")
 
 

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, matchcall, packing
+from onepose_st_amd import hip, layercall, matchcall, packing
 from onepose_st_amd.synthetic import make_synthetic_inputs
 from tests.test_gpu_parity import TOL, _check_against, _model, _planted_features, close, dev, model, to_dev  # noqa: F401  (dev, model: fixtures)
 
@@ -42,25 +42,10 @@ def test_encoder_layer_masked(sd, dev, mode, cross, B, L3, L2):
     assert (unmasked2 - r2).abs().max() > 1e-2           # the mask matters in this case
     d3, d2, dm = x3.to(dev), x2.to(dev), mask.to(dev).view(torch.uint8)
     y3, y2 = torch.full_like(d3, float("nan")), torch.full_like(d2, float("nan"))
-    P, S = hip.ptr, hip.stream_handle()
-    lib = hip.load()
-    if mode == "f32":
-        w = packing.pack_coarse_layer(sd, p).to(dev)
-        ws = torch.empty(lib.ophip_encoder_workspace_floats(B, L3, L2), device=dev)
-        hip.call("ophip_encoder_layer_masked", P(d3), P(d2), P(y3), P(y2), B, L3, L2, P(w), cross, P(ws), P(dm, torch.uint8), S)
-        tol = dict(rtol=1e-4, atol=2e-5)
-    elif mode == "bf16x3":
-        w = packing.pack_coarse_layer_x3w8(sd, p).to(dev)
-        ws = torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
-        hip.call("ophip_encoder_layer_x3w8_masked", P(d3), P(d2), P(y3), P(y2), B, L3, L2, P(w, None), None, cross, 0, 0, P(ws, None),
-                 P(dm, torch.uint8), S)
-        tol = dict(rtol=3e-4, atol=1e-4)
-    else:
-        w = packing.pack_coarse_layer_bf16(sd, p).to(dev)
-        ws = torch.empty(lib.ophip_encoder_bf16_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
-        hip.call("ophip_encoder_layer_bf16_masked", P(d3), P(d2), P(y3), P(y2), B, L3, L2, P(w, None), None, 1, cross, 0, 0, P(ws, None),
-                 P(dm, torch.uint8), S)
-        tol = dict(rtol=5e-2, atol=5e-2)
+    packer, tol = {"f32": (packing.pack_coarse_layer, dict(rtol=1e-4, atol=2e-5)), "bf16x3": (packing.pack_coarse_layer_x3w8, dict(rtol=3e-4, atol=1e-4)),
+                   "bf16": (packing.pack_coarse_layer_bf16, dict(rtol=5e-2, atol=5e-2))}[mode]
+    layercall.layer(d3, d2, y3, y2, mode=mode, wpack=packer(sd, p).to(dev), is_cross=cross, workspace=layercall.workspace(mode, B, L3, L2, dev),
+                    query_mask=dm)
     print(f"{mode} cross={cross} B={B} L=({L3},{L2}): max abs err 3D {(y3.cpu() - r3).abs().max():.3e} 2D {(y2.cpu() - r2).abs().max():.3e}")
     close(y3, r3, msg="3D stream", **tol)
     close(y2, r2, msg="2D stream", **tol)
@@ -70,9 +55,10 @@ def test_masked_entry_points_refuse_null(dev):
     x = torch.zeros(1, 32, 256, device=dev)
     y = torch.zeros_like(x)
     w = torch.zeros(16, device=dev)
+    entry, named = layercall.plan_layer(x, x, y, y, mode="f32", wpack=w, is_cross=0, workspace=w, query_mask=torch.ones(1, 32, dtype=torch.uint8, device=dev))
+    assert entry == "ophip_encoder_layer_masked"
     with pytest.raises(ValueError):
-        hip.call("ophip_encoder_layer_masked", hip.ptr(x), hip.ptr(x), hip.ptr(y), hip.ptr(y), 1, 32, 32, hip.ptr(w), 0, hip.ptr(w), None,
-                 hip.stream_handle())
+        hip.launch(entry, dict(named, query_mask=None))
 
 
 @pytest.mark.parametrize("nsplit,rtol", [(0, 1e-4), (3, 1e-3)])

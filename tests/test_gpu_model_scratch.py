@@ -1,5 +1,5 @@
 """The product's own allocations under guard (run with ``-m gpu`` on the MI355X): for the duration of a call, ``torch.empty`` /
-``torch.empty_like`` as ``onepose_st_amd.model``, ``.loftr`` and ``.matchcall`` look them up hand out regions of a ``tests.guarded.Arena``
+``torch.empty_like`` as ``onepose_st_amd.model``, ``.loftr``, ``.matchcall`` and ``.layercall`` look them up hand out regions of a ``tests.guarded.Arena``
 -- every workspace, intermediate, output and frame block of the call at exactly the size the product asks for, 1 MiB of guard on each
 side, filled 0xFF (NaN / -1) or 0x00 instead of whatever the caching allocator last held there.
 
@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from onepose_st_amd import loftr as loftr_module
-from onepose_st_amd import hip, matchcall as matchcall_module, model as model_module
+from onepose_st_amd import hip, layercall as layercall_module, matchcall as matchcall_module, model as model_module
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_loftr_state_dict
 from tests import test_gpu_loftr_masked as tglm
@@ -22,7 +22,7 @@ from tests.test_gpu_workspace_contract import FILLS, FRAME_KEYS, same_bits
 
 pytestmark = pytest.mark.gpu
 
-MODULES = [model_module, loftr_module, matchcall_module]
+MODULES = [model_module, loftr_module, matchcall_module, layercall_module]
 ARENA_BYTES = 320 << 20
 
 
@@ -54,6 +54,7 @@ def under_guard(dev, fill, call):
     with guarded_empty(arena, fill, MODULES):
         out = call()
         torch.cuda.synchronize()
+    print(f"fill {fill:#04x}: {len(arena.regions)} allocations of the call went through the arena")
     assert len(arena.regions) >= 1, "no allocation of the call went through the arena"
     arena.check()
     return out
@@ -110,6 +111,7 @@ def test_three_pipelined_frames(sd, cfg, dev, frames):
         # the product reuses one block for every frame: the same pipeline again, frame t in the blocks frame t + 1 has just used, so the
         # stale bytes it finds are another frame's results
         per_frame = len(log) // len(feats)
+        print(f"fill {fill:#04x}: {len(arena.regions)} allocations of the three frames went through the arena")
         assert per_frame >= 1 and len(log) == per_frame * len(feats)
         assert all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(log, log[per_frame:]))
         with guarded_empty(arena, fill, MODULES, reuse=log[per_frame:] + log[:per_frame]):

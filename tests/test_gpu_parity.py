@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, host_math, matchcall, packing
+from onepose_st_amd import hip, host_math, layercall, matchcall, packing
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.pnp import ransac_PnP
 from onepose_st_amd.synthetic import make_synthetic_inputs
@@ -131,16 +131,14 @@ def test_encoder_layer(sd, dev, cross, B, L3, L2):
     else:
         r2, r3 = orc.encoder_layer(sd, p, x2, x2, 8), orc.encoder_layer(sd, p, x3, x3, 8)
     w = packing.pack_coarse_layer(sd, p).to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_workspace_floats(B, L3, L2), device=dev)
+    kw = dict(mode="f32", wpack=w, is_cross=cross, workspace=layercall.workspace("f32", B, L3, L2, dev))
     d3, d2 = x3.to(dev), x2.to(dev)
     y3, y2 = torch.full_like(d3, float("nan")), torch.full_like(d2, float("nan"))
-    hip.call("ophip_encoder_layer", hip.ptr(d3), hip.ptr(d2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w), cross,
-             hip.ptr(ws), hip.stream_handle())
+    layercall.layer(d3, d2, y3, y2, **kw)
     close(y3, r3, msg="3D stream", **LAYER_TOL["f32"])
     close(y2, r2, msg="2D stream", **LAYER_TOL["f32"])
     with pytest.raises(ValueError):           # in-place is refused (cross layers read pre-update streams)
-        hip.call("ophip_encoder_layer", hip.ptr(d3), hip.ptr(d2), hip.ptr(d3), hip.ptr(y2), B, L3, L2, hip.ptr(w), cross,
-                 hip.ptr(ws), hip.stream_handle())
+        layercall.layer(d3, d2, d3, y2, **kw)
 
 
 @pytest.mark.parametrize("nsplit,rtol,atol", [(1, LAYER_TOL["bf16"]["rtol"], LAYER_TOL["bf16"]["atol"])])
@@ -157,23 +155,21 @@ def test_encoder_layer_bf16(sd, dev, nsplit, rtol, atol, cross, B, L3, L2):
     else:
         r2, r3 = orc.encoder_layer(sd, p, x2, x2, 8), orc.encoder_layer(sd, p, x3, x3, 8)
     w = packing.pack_coarse_layer_bf16(sd, p).to(dev)
-    assert w.numel() == hip.load().ophip_encoder_bf16_wpack_bytes()
-    ws = torch.empty(hip.load().ophip_encoder_bf16_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
+    assert w.numel() == layercall.wpack_bytes("bf16")
+    kw = dict(mode="bf16", wpack=w, is_cross=cross, workspace=layercall.workspace("bf16", B, L3, L2, dev))
     d3, d2 = x3.to(dev), x2.to(dev)
     y3, y2 = torch.full_like(d3, float("nan")), torch.full_like(d2, float("nan"))
-    hip.call("ophip_encoder_layer_bf16", hip.ptr(d3), hip.ptr(d2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), None, nsplit, cross, 0, 0,
-             hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(d3, d2, y3, y2, nsplit=nsplit, **kw)
     e3 = (y3.cpu() - r3).abs().max().item()
     e2 = (y2.cpu() - r2).abs().max().item()
     print(f"nsplit={nsplit} cross={cross} B={B} L=({L3},{L2}): max abs err 3D {e3:.3e} 2D {e2:.3e}")
     close(y3, r3, rtol=rtol, atol=atol, msg="3D stream")
     close(y2, r2, rtol=rtol, atol=atol, msg="2D stream")
     with pytest.raises(ValueError):
-        hip.call("ophip_encoder_layer_bf16", hip.ptr(d3), hip.ptr(d2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), None, 3, cross, 0, 0,
-                 hip.ptr(ws, None), hip.stream_handle())
+        layercall.layer(d3, d2, y3, y2, nsplit=3, **kw)
 
 
-X3_KERNELS = {"x3w8": ("ophip_encoder_layer_x3w8", "ophip_encoder_x3w8_wpack_bytes", "ophip_encoder_x3w8_workspace_bytes", "pack_coarse_layer_x3w8")}
+X3_KERNELS = {"x3w8": ("bf16x3", "pack_coarse_layer_x3w8")}          # kernel -> (layercall mode, packer)
 
 
 @pytest.mark.parametrize("kern", ["x3w8"])
@@ -189,22 +185,20 @@ def test_encoder_layer_x3(sd, dev, cross, B, L3, L2, kern):
         r2, r3 = orc.encoder_layer(sd, p, x2, x3, 8), orc.encoder_layer(sd, p, x3, x2, 8)
     else:
         r2, r3 = orc.encoder_layer(sd, p, x2, x2, 8), orc.encoder_layer(sd, p, x3, x3, 8)
-    entry, wbytes, wsbytes, packer = X3_KERNELS[kern]
+    mode, packer = X3_KERNELS[kern]
     w = getattr(packing, packer)(sd, p).to(dev)
-    assert w.numel() == getattr(hip.load(), wbytes)()
-    ws = torch.empty(getattr(hip.load(), wsbytes)(B, L3, L2), dtype=torch.uint8, device=dev)
+    assert w.numel() == layercall.wpack_bytes(mode)
+    kw = dict(mode=mode, wpack=w, is_cross=cross, workspace=layercall.workspace(mode, B, L3, L2, dev))
     d3, d2 = x3.to(dev), x2.to(dev)
     y3, y2 = torch.full_like(d3, float("nan")), torch.full_like(d2, float("nan"))
-    hip.call(entry, hip.ptr(d3), hip.ptr(d2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), None, cross, 0, 0,
-             hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(d3, d2, y3, y2, **kw)
     e3 = (y3.cpu() - r3).abs().max().item()
     e2 = (y2.cpu() - r2).abs().max().item()
     print(f"{kern} cross={cross} B={B} L=({L3},{L2}): max abs err 3D {e3:.3e} 2D {e2:.3e}")
     close(y3, r3, msg="3D stream", **LAYER_TOL["bf16x3"])
     close(y2, r2, msg="2D stream", **LAYER_TOL["bf16x3"])
     with pytest.raises(ValueError):
-        hip.call(entry, hip.ptr(d3), hip.ptr(d2), hip.ptr(d3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), None, cross, 0, 0,
-                 hip.ptr(ws, None), hip.stream_handle())
+        layercall.layer(d3, d2, d3, y2, **kw)
 
 
 @pytest.mark.parametrize("cross", [0, 1])
@@ -215,22 +209,19 @@ def test_encoder_layer_on_one_stream_equals_the_two_stream_rows(sd, dev, cross, 
     g = torch.Generator().manual_seed(12)
     x3, x2 = torch.randn(B, L3, 256, generator=g).to(dev), torch.randn(B, L2, 256, generator=g).to(dev)
     w = packing.pack_coarse_layer_x3w8(sd, "loftr_coarse.layers.1.").to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
+    kw = dict(mode="bf16x3", wpack=w, is_cross=cross, workspace=layercall.workspace("bf16x3", B, L3, L2, dev))
     y3, y2 = torch.empty_like(x3), torch.empty_like(x2)
-    hip.call("ophip_encoder_layer_x3w8", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), None, cross, 0, 0,
-             hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(x3, x2, y3, y2, **kw)
     for streams, (ya, yb) in ((1, (y3, None)), (2, (None, y2))):
         o3, o2 = torch.full_like(x3, float("nan")), torch.full_like(x2, float("nan"))
-        hip.call("ophip_encoder_layer_x3w8_streams", hip.ptr(x3), hip.ptr(x2), hip.ptr(o3) if streams & 1 else None, hip.ptr(o2) if streams & 2 else None,
-                 B, L3, L2, hip.ptr(w, None), cross, streams, hip.ptr(ws, None), hip.stream_handle())
+        layercall.layer(x3, x2, o3 if streams & 1 else None, o2 if streams & 2 else None, streams=streams, **kw)
         torch.cuda.synchronize()
         if streams & 1:
             assert torch.equal(o3, y3) and bool(torch.isnan(o2).all())
         else:
             assert torch.equal(o2, y2) and bool(torch.isnan(o3).all())
     with pytest.raises(ValueError):
-        hip.call("ophip_encoder_layer_x3w8_streams", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None), cross, 0,
-                 hip.ptr(ws, None), hip.stream_handle())
+        layercall.layer(x3, x2, y3, y2, streams=0, **kw)
 
 
 @pytest.mark.parametrize("B,N,hc,wc", [(1, 100, 5, 15), (2, 333, 13, 20), (1, 1000, 30, 40)])
@@ -244,7 +235,7 @@ def test_encoder_layer_writes_the_similarity_fragments(sd, dev, B, N, hc, wc):
     kp = torch.randn(B, N, 3, generator=g).to(dev)
     p = "loftr_coarse.layers.5."
     w = packing.pack_coarse_layer_x3w8(sd, p).to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, N, M), dtype=torch.uint8, device=dev)
+    kw = dict(mode="bf16x3", wpack=w, is_cross=1, workspace=layercall.workspace("bf16x3", B, N, M, dev))
     cap = B * N
 
     def coarse(flag, cws, y3, y2):
@@ -258,8 +249,7 @@ def test_encoder_layer_writes_the_similarity_fragments(sd, dev, B, N, hc, wc):
         return conf, [t[:K].clone() for t in ids], mconf[:K].clone()
 
     y3a, y2a = torch.empty_like(x3), torch.empty_like(x2)
-    hip.call("ophip_encoder_layer_x3w8", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3a), hip.ptr(y2a), B, N, M, hip.ptr(w, None), None, 1, 0, 0,
-             hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(x3, x2, y3a, y2a, **kw)
     cws_a = torch.empty(hip.load().ophip_coarse_workspace_floats(B, N, M), device=dev)
     ref = coarse(0, cws_a, y3a, y2a)
 
@@ -267,8 +257,7 @@ def test_encoder_layer_writes_the_similarity_fragments(sd, dev, B, N, hc, wc):
     cws_b = torch.full((hip.load().ophip_coarse_workspace_floats(B, N, M),), float("nan"), device=dev)      # padding must be written, not assumed
     pa, pb = ctypes.c_void_p(), ctypes.c_void_p()
     hip.call("ophip_coarse_frag_planes", hip.ptr(cws_b), B, N, M, ctypes.byref(pa), ctypes.byref(pb))
-    hip.call("ophip_encoder_layer_x3w8_frag", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3b), hip.ptr(y2b), B, N, M, hip.ptr(w, None), None, 1, 0, 0,
-             hip.ptr(ws, None), pa, pb, hip.stream_handle())
+    layercall.layer(x3, x2, y3b, y2b, frag=(pa, pb), **kw)
     got = coarse(hip.COARSE_PLANES_READY, cws_b, y3b, y2b)
     assert torch.equal(y3a, y3b) and torch.equal(y2a, y2b)
     assert torch.equal(ref[0], got[0]) and all(torch.equal(a, b) for a, b in zip(ref[1], got[1])) and torch.equal(ref[2], got[2])
@@ -289,18 +278,17 @@ def test_encoder_x3_chain_with_fused_kv_tail(sd, dev, B, L3, L2, kern):
             r2, r3 = orc.encoder_layer(sd, p, r2, r3, 8), orc.encoder_layer(sd, p, r3, r2, 8)
         else:
             r2, r3 = orc.encoder_layer(sd, p, r2, r2, 8), orc.encoder_layer(sd, p, r3, r3, 8)
-    entry, _, wsbytes, packer = X3_KERNELS[kern]
+    mode, packer = X3_KERNELS[kern]
     ws_ = [getattr(packing, packer)(sd, f"loftr_coarse.layers.{li}.").to(dev) for li in range(3)]
-    ws = torch.empty(getattr(hip.load(), wsbytes)(B, L3, L2), dtype=torch.uint8, device=dev)
+    ws = layercall.workspace(mode, B, L3, L2, dev)
 
     def chain(fused):
         a3, a2 = x3.to(dev), x2.to(dev)
         b3, b2 = torch.full_like(a3, float("nan")), torch.full_like(a2, float("nan"))
         for li, nm in enumerate(names):
             nxt = ws_[li + 1] if (fused and li + 1 < 3) else None
-            hip.call(entry, hip.ptr(a3), hip.ptr(a2), hip.ptr(b3), hip.ptr(b2), B, L3, L2, hip.ptr(ws_[li], None),
-                     hip.ptr(nxt, None), 1 if nm == "cross" else 0, 1 if (fused and li > 0) else 0, (li & 1) if fused else 0,
-                     hip.ptr(ws, None), hip.stream_handle())
+            layercall.layer(a3, a2, b3, b2, mode=mode, wpack=ws_[li], wpack_next=nxt, is_cross=1 if nm == "cross" else 0,
+                            kv_from_prev=1 if (fused and li > 0) else 0, slot=(li & 1) if fused else 0, workspace=ws)
             a3, b3, a2, b2 = b3, a3, b2, a2
         return a3.clone(), a2.clone()
     f3, f2 = chain(True)
@@ -1102,13 +1090,10 @@ def test_object_cache_is_bit_identical(sd, cfg, dev, monkeypatch):
     assert cached._obj_cache is entry                           # same block: the cached entry was used
     # the cached rows ARE the uncached first layer's 3D rows: ophip_encoder_object_x3w8 against the plain layer call on both streams
     W = cached._weights(dev)
-    lib = hip.load()
-    P = hip.ptr
     x2 = torch.randn(1, 24 * 16, 256, device=dev)
     y3, y2 = torch.empty_like(entry["x3d"]), torch.empty_like(x2)
-    ws = torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(1, 1100, 24 * 16), device=dev, dtype=torch.uint8)
-    hip.call("ophip_encoder_layer_x3w8", P(entry["x3d"]), P(x2), P(y3), P(y2), 1, 1100, 24 * 16, P(W["coarse_x3"][0], None), P(W["coarse_x3"][1], None),
-             0, 0, 0, P(ws, None), hip.stream_handle())
+    layercall.layer(entry["x3d"], x2, y3, y2, mode="bf16x3", wpack=W["coarse_x3"][0], wpack_next=W["coarse_x3"][1], is_cross=0,
+                    workspace=layercall.workspace("bf16x3", 1, 1100, 24 * 16, dev))
     torch.cuda.synchronize()
     assert torch.equal(y3, entry["y3d0"])
     # the encoding alone (depth 1), and both depths pipelined with the input kernels (and the first layer's K / V half) on the side stream
@@ -1300,12 +1285,11 @@ def test_custom_ops_match_the_c_abi(sd, cfg, dev):
     L2 = hc * wc
     x3, x2 = torch.randn(B, L3, 256, generator=g).to(dev), torch.randn(B, L2, 256, generator=g).to(dev)
     w = packing.pack_coarse_layer_x3w8(sd, "loftr_coarse.layers.0.").to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
+    ws = layercall.workspace("bf16x3", B, L3, L2, dev)
     y3, y2 = torch.empty_like(x3), torch.empty_like(x2)
     torch.ops.onepose_hip.encoder_layer_x3w8(x3, x2, y3, y2, w, None, False, False, 0, ws)
     z3, z2 = torch.empty_like(x3), torch.empty_like(x2)
-    hip.call("ophip_encoder_layer_x3w8", hip.ptr(x3), hip.ptr(x2), hip.ptr(z3), hip.ptr(z2), B, L3, L2, hip.ptr(w, None), None, 0, 0, 0,
-             hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(x3, x2, z3, z2, mode="bf16x3", wpack=w, is_cross=0, workspace=ws)
     assert torch.equal(y3, z3) and torch.equal(y2, z2)
     # the fragment-writing form: same rows, and coarse matching fed from the planes gives the same matches
     cws = torch.empty(hip.load().ophip_coarse_workspace_floats(B, L3, L2), device=dev)

@@ -24,7 +24,7 @@ import pytest
 import torch
 
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, matchcall, model as model_module, packing, postopt
+from onepose_st_amd import hip, layercall, matchcall, model as model_module, packing, postopt
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_sfm_tracks
 from tests import bf16_faithful as bf
@@ -135,6 +135,21 @@ ENC = {
     "full": ("ophip_encoder_layer_full_x3", "bf16x3", "pack_coarse_layer", "ophip_encoder_full_workspace_bytes", 16),
     "full_stream": ("ophip_encoder_layer_full_x3_stream", "bf16x3", "pack_coarse_layer", "ophip_encoder_full_stream_workspace_bytes", 16),
 }
+# variant -> what ``layercall.layer`` is given beside the rows, the weights, ``is_cross`` and the workspace region; M3 / M2 stand for the
+# arena's copies of the 3D / 2D stream's mask.  (full_stream: ``layercall.layer_full_stream``, which has no options)
+M3, M2 = "mask0", "mask1"
+X3 = dict(mode="bf16x3")
+ENC_KW = {
+    "f32": dict(mode="f32"), "f32_masked": dict(mode="f32", query_mask=M2),
+    "bf16": dict(mode="bf16"), "bf16_masked": dict(mode="bf16", query_mask=M2),
+    "x3w8": X3, "x3w8_masked": dict(X3, query_mask=M2),
+    "x3w8_masks": dict(X3, masks=(M3, M2)), "x3w8_masks_null0": dict(X3, masks=(None, M2)), "x3w8_masks_null1": dict(X3, masks=(M3, None)),
+    **{f"x3w8_streams{s}": dict(X3, streams=s) for s in (1, 2, 3)},
+    **{f"x3w8_streams_masks{s}": dict(X3, streams=s, masks=(M3, M2)) for s in (1, 2, 3)},
+    "x3w8_kv_first": dict(X3, kv_from_prev=2),                    # after layercall.kv_first: "the summed block is there"
+    "full": dict(mode="full"), "full_stream": {},
+}
+assert set(ENC_KW) == set(ENC)
 _ENC_CASES = {}
 
 
@@ -165,11 +180,10 @@ def test_encoder_layer(sd, dev, variant, B, L3, L2, cross):
     x3, x2, m3, m2 = enc_case(B, L3, L2)
     w = weights(sd, dev, packer, LAYER)
     lib = hip.load()
-    masked2 = variant in ("f32_masked", "bf16_masked", "x3w8_masked")
-    both = "masks" in variant
-    use3 = both and not variant.endswith("null0")
-    use2 = masked2 or (both and not variant.endswith("null1"))
-    streams = int(variant[-1]) if "streams" in variant else 3
+    kw = ENC_KW[variant]
+    masked2 = "query_mask" in kw
+    use3, use2 = M3 in kw.get("masks", ()), masked2 or M2 in kw.get("masks", ())
+    streams = kw.get("streams", 3)
     S3 = L2 if cross else L3                                    # full_stream: the 3D rows against their source
     nbytes = getattr(lib, helper)(B, L3, S3 if variant == "full_stream" else L2) * (4 if helper.endswith("floats") else 1)
     seen = {}
@@ -180,27 +194,18 @@ def test_encoder_layer(sd, dev, variant, B, L3, L2, cross):
         dm3 = arena.put(m3.view(U8), name="mask0") if use3 else None
         dm2 = arena.put(m2.view(U8), name="mask1") if use2 else None
         wsp = ws(nbytes)
-        S = hip.stream_handle()
-        head = (P(d3), P(d2), P(y3), P(y2), B, L3, L2)
-        if variant in ("f32", "full"):
-            hip.call(entry, *head, P(w), cross, P(wsp, None), S)
-        elif variant == "f32_masked":
-            hip.call(entry, *head, P(w), cross, P(wsp, None), P(dm2, U8), S)
-        elif variant in ("bf16", "bf16_masked"):
-            hip.call(entry, *head, P(w, None), None, 1, cross, 0, 0, P(wsp, None), *([P(dm2, U8)] if masked2 else []), S)
-        elif variant in ("x3w8", "x3w8_masked"):
-            hip.call(entry, *head, P(w, None), None, cross, 0, 0, P(wsp, None), *([P(dm2, U8)] if masked2 else []), S)
-        elif variant.startswith("x3w8_masks"):
-            hip.call(entry, *head, P(w, None), None, cross, 0, 0, P(wsp, None), P(dm3, U8), P(dm2, U8), S)
-        elif "streams" in variant:
-            hip.call(entry, P(d3), P(d2), P(y3) if streams & 1 else None, P(y2) if streams & 2 else None, B, L3, L2, P(w, None), cross,
-                     streams, P(wsp, None), *([P(dm3, U8), P(dm2, U8)] if both else []), S)
-        elif variant == "x3w8_kv_first":                          # the K / V half, then the layer told that the summed block is there
-            hip.call(entry, P(d3), P(d2), B, L3, L2, P(w, None), 0, P(wsp, None), None, S)
-            hip.call("ophip_encoder_layer_x3w8", *head, P(w, None), None, cross, 2, 0, P(wsp, None), S)
-        else:                                                     # full_stream: the 3D rows as the query stream
-            src = d2 if cross else d3
-            hip.call(entry, P(d3), L3 * 256, P(src), S3 * 256, P(y3), B, L3, S3, P(w), P(wsp, None), S)
+        region = wsp.view(F32) if helper.endswith("floats") else wsp                 # the f32 entries take float*
+        if variant == "full_stream":                              # the 3D rows as the query stream
+            layercall.layer_full_stream(d3, d2 if cross else d3, y3, wpack=w, workspace=region)
+        else:
+            put = {M3: dm3, M2: dm2}
+            call = {k: tuple(put.get(m) for m in v) if k == "masks" else put.get(v, v) for k, v in kw.items()}
+            if variant == "x3w8_kv_first":                        # the K / V half first
+                layercall.kv_first(d3, d2, wpack=w, slot=0, workspace=region)
+            plan = layercall.plan_layer(d3, d2, y3 if streams & 1 else None, y2 if streams & 2 else None, wpack=w, is_cross=cross,
+                                        workspace=region, **call)
+            assert plan[0] == ("ophip_encoder_layer_x3w8" if variant == "x3w8_kv_first" else entry)      # the row's entry is the one that runs
+            hip.launch(*plan)
         if mode == "bf16" and "block" not in seen:                # (c) of the plain-bf16 layer reads the K^T V | Ksum block of the first run
             torch.cuda.synchronize()
             off = bf.kv_block_offset(wsp.data_ptr(), B, L3, L2)
@@ -245,8 +250,8 @@ def test_fused_chain(sd, dev, kind, B, L3, L2):
         layers = []
         for li, nm in enumerate(CHAIN):
             nxt = ws_[li + 1] if li + 1 < 3 else None
-            tail = (1 if nm == "cross" else 0, 1 if li > 0 else 0, li & 1, P(wsp, None), hip.stream_handle())
-            hip.call(entry, P(a3), P(a2), P(b3), P(b2), B, L3, L2, P(ws_[li], None), P(nxt, None), *([1] if kind == "bf16" else []), *tail)
+            layercall.layer(a3, a2, b3, b2, wpack=ws_[li], wpack_next=nxt, is_cross=1 if nm == "cross" else 0, kv_from_prev=1 if li > 0 else 0,
+                            slot=li & 1, workspace=wsp, **ENC_KW[kind])
             if kind == "bf16" and "layers" not in seen:
                 torch.cuda.synchronize()
                 off = bf.kv_block_offset(wsp.data_ptr(), B, L3, L2)
@@ -286,8 +291,7 @@ def test_encoder_object(sd, dev, Bo, N, masked_frames):
     def run(arena, ws):
         d3 = arena.put(x3, name="x3d")
         y3d0, kv1 = arena.typed(x3.shape, F32, name="y3d0"), arena.typed((Bo, kvb), U8, align=256, shift=16, name="kv1")
-        hip.call("ophip_encoder_object_x3w8", P(d3), Bo, N, P(w0, None), P(w1, None), P(ws(nbytes), None), P(y3d0), P(kv1, None), masked_frames,
-                 hip.stream_handle())
+        layercall.object_rows(d3, wpack0=w0, wpack1=w1, workspace=ws(nbytes), y3d0=y3d0, kv1=kv1, masked_frames=masked_frames)
         return {"y3d0": y3d0, "kv1": kv1}
 
     def bar(out):
@@ -296,9 +300,7 @@ def test_encoder_object(sd, dev, Bo, N, masked_frames):
         if not masked_frames:           # tests/test_gpu_parity.py::test_object_cache_is_bit_identical: the rows ARE the plain layer's 3D rows
             d3, d2 = x3.to(dev), torch.randn(Bo, 32, 256, device=dev)
             y3, y2 = torch.empty_like(d3), torch.empty_like(d2)
-            wsp = torch.empty(lib.ophip_encoder_x3w8_workspace_bytes(Bo, N, 32), device=dev, dtype=U8)
-            hip.call("ophip_encoder_layer_x3w8", P(d3), P(d2), P(y3), P(y2), Bo, N, 32, P(w0, None), P(w1, None), 0, 0, 0, P(wsp, None),
-                     hip.stream_handle())
+            layercall.layer(d3, d2, y3, y2, wpack=w0, wpack_next=w1, is_cross=0, workspace=layercall.workspace("bf16x3", Bo, N, 32, dev), **X3)
             torch.cuda.synchronize()
             assert torch.equal(y3, out["y3d0"])
 
@@ -471,16 +473,14 @@ def test_fragment_planes_carried_into_coarse_matching(sd, dev, B, N, hc, wc):
         hip.call("ophip_coarse_frag_planes", P(cws, None), B, N, M, ctypes.byref(pa), ctypes.byref(pb))
         lo, hi = cws.data_ptr(), cws.data_ptr() + cws.numel()
         assert lo <= pa.value < pb.value < hi and pa.value % 64 == 0
-        hip.call("ophip_encoder_layer_x3w8_frag", P(d3), P(d2), P(y3), P(y2), B, N, M, P(w, None), None, 1, 0, 0, P(ews, None), pa, pb,
-                 hip.stream_handle())
+        layercall.layer(d3, d2, y3, y2, wpack=w, is_cross=1, workspace=ews, frag=(pa, pb), **X3)
         matchcall.coarse_match(y3, y2, dk, kpts_bstride=N * 3, nsplit=3, planes_ready=True, **coarse_kw(wc), **coarse_outputs(o, cws))
         return {**o, "y3d": y3, "y2d": y2}
 
     def bar(out):
         d3, d2, dk = x3.to(dev), x2.to(dev), kp.to(dev)
         y3, y2 = torch.empty_like(d3), torch.empty_like(d2)
-        ews = torch.empty(enc_bytes, dtype=U8, device=dev)
-        hip.call("ophip_encoder_layer_x3w8", P(d3), P(d2), P(y3), P(y2), B, N, M, P(w, None), None, 1, 0, 0, P(ews, None), hip.stream_handle())
+        layercall.layer(d3, d2, y3, y2, wpack=w, is_cross=1, workspace=torch.empty(enc_bytes, dtype=U8, device=dev), **X3)
         conf, ids, mconf, mk3, mkc = par._coarse_match(dev, y3, y2, dk, wc, nsplit=3)
         got = coarse_lists(out)
         assert torch.equal(out["y3d"], y3) and torch.equal(out["y2d"], y2)
@@ -740,7 +740,7 @@ def test_frame_block(sd, cfg, dev, monkeypatch, form):
             fast._obj_cache = None
             calls = ops.CALLS["frame_enqueue"]
             log = []
-            with guarded_empty(arena, fill, [model_module], align, shift, log=log):
+            with guarded_empty(arena, fill, [model_module, layercall], align, shift, log=log):      # (layercall: the object cache's workspace)
                 d = dict(obj)
                 fast.enqueue_features(d, fc, ff, f["image_hw"], inputs_ready=True, host_copy=True).finish()
                 if form == "lazy_conf":

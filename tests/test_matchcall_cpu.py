@@ -132,7 +132,7 @@ def test_match_lists_empty_and_trim():
 def test_every_entry_of_the_two_stages_has_a_plan_and_a_converter():
     """the twelve entries and no more; the launch step's converters come from the header's C types, one per parameter but ``stream``"""
     planned = {e for _, e in COARSE_ROWS} | {e for _, e in ROWS_2D} | {e for _, _, e in FINE_ROWS}
-    assert planned == set(mc._CONVERT) == {n for n in hip.PROTOTYPES if n.startswith(("ophip_coarse_match", "ophip_fine_refine"))}
-    assert len(planned) == 12 and all(set(mc._CONVERT[e]) == names(e) for e in planned)
+    assert planned == {n for n in hip.PROTOTYPES if n.startswith(("ophip_coarse_match", "ophip_fine_refine"))}
+    assert len(planned) == 12 and all(set(hip.converters(e)) == names(e) for e in planned) and mc.launch is hip.launch
     with pytest.raises(hip.HipLibraryError):                               # a CPU tensor reaches no kernel
         mc.launch(*coarse()[0])

@@ -3,7 +3,7 @@ stand-alone K / V half against the oracle.  Not part of the product."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from oracle import onepose_oracle as orc
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, layercall, packing
 from onepose_st_amd.config import default_config
 from onepose_st_amd.synthetic import make_synthetic_state_dict
 sd = make_synthetic_state_dict(0, default_config()); dev = torch.device("cuda:0"); hip.load()
@@ -12,15 +12,15 @@ g = torch.Generator().manual_seed(5)
 x3, x2 = torch.randn(B, L3, 256, generator=g), torch.randn(B, L2, 256, generator=g)
 names = ["self", "cross", "self"]
 ws_ = [packing.pack_coarse_layer_x3w8(sd, f"loftr_coarse.layers.{li}.").to(dev) for li in range(3)]
-ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
+ws = layercall.workspace("bf16x3", B, L3, L2, dev)
 def chain(fused, reps=1):
     outs = []
     a3, a2 = x3.to(dev), x2.to(dev)
     b3, b2 = torch.full_like(a3, float("nan")), torch.full_like(a2, float("nan"))
     for li, nm in enumerate(names):
         nxt = ws_[li + 1] if (fused and li + 1 < 3) else None
-        hip.call("ophip_encoder_layer_x3w8", hip.ptr(a3), hip.ptr(a2), hip.ptr(b3), hip.ptr(b2), B, L3, L2, hip.ptr(ws_[li], None),
-                 hip.ptr(nxt, None), 1 if nm == "cross" else 0, 1 if (fused and li > 0) else 0, (li & 1) if fused else 0, hip.ptr(ws, None), hip.stream_handle())
+        layercall.layer(a3, a2, b3, b2, mode="bf16x3", wpack=ws_[li], wpack_next=nxt, is_cross=1 if nm == "cross" else 0,
+                        kv_from_prev=1 if (fused and li > 0) else 0, slot=(li & 1) if fused else 0, workspace=ws)
         torch.cuda.synchronize()
         t3, t2 = (L3 + 47) // 48, (L2 + 47) // 48
         part_floats = B * (t3 + t2) * (8 * 1024 + 8 * 32)

@@ -2,7 +2,7 @@
 import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from onepose_st_amd import hip, packing
+from onepose_st_amd import hip, layercall, packing
 from onepose_st_amd.config import default_config
 from onepose_st_amd.synthetic import make_synthetic_state_dict
 sd = make_synthetic_state_dict(0, default_config()); dev = torch.device("cuda:0"); hip.load()
@@ -11,13 +11,11 @@ L3, L2 = 7000, 4800
 g = torch.Generator().manual_seed(0)
 x3, x2 = torch.randn(B, L3, 256, generator=g).to(dev), torch.randn(B, L2, 256, generator=g).to(dev)
 y3, y2 = torch.empty_like(x3), torch.empty_like(x2)
-ENTRY = "ophip_encoder_layer_x3w8"
 w = packing.pack_coarse_layer_x3w8(sd, "loftr_coarse.layers.0.").to(dev)
-ws = torch.empty(hip.load().ophip_encoder_x3w8_workspace_bytes(B, L3, L2), dtype=torch.uint8, device=dev)
+ws = layercall.workspace("bf16x3", B, L3, L2, dev)
 fuse = not os.environ.get("NOFUSE")
 def run():
-    hip.call(ENTRY, hip.ptr(x3), hip.ptr(x2), hip.ptr(y3), hip.ptr(y2), B, L3, L2, hip.ptr(w, None),
-             hip.ptr(w, None) if fuse else None, 0, 0, 0, hip.ptr(ws, None), hip.stream_handle())
+    layercall.layer(x3, x2, y3, y2, mode="bf16x3", wpack=w, wpack_next=w if fuse else None, is_cross=0, workspace=ws)
 for _ in range(3): run()
 torch.cuda.synchronize()
 import time

@@ -26,7 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from onepose_st_amd import hip, packing  # noqa: E402
+from onepose_st_amd import hip, layercall, packing  # noqa: E402
 from onepose_st_amd.config import default_config  # noqa: E402
 from onepose_st_amd.model import OnePosePlus_model  # noqa: E402
 from onepose_st_amd.synthetic import make_synthetic_inputs, make_synthetic_loftr_state_dict, make_synthetic_state_dict  # noqa: E402
@@ -80,9 +80,8 @@ def detector_items(args, dev):
         x = torch.randn(1, L, 256, generator=g).to(dev)
         src = x if name.endswith("self") else torch.randn(1, Sk, 256, generator=g).to(dev)
         y = torch.empty_like(x)
-        ws = torch.empty(hip.load().ophip_encoder_full_stream_workspace_bytes(1, L, Sk), dtype=torch.uint8, device=dev)
-        us = timed(lambda: hip.call("ophip_encoder_layer_full_x3_stream", hip.ptr(x), 0, hip.ptr(src), 0, hip.ptr(y), 1, L, Sk, hip.ptr(w),
-                                    hip.ptr(ws, None), S()), args.iters, args.warmup)
+        ws = layercall.workspace("full", 1, L, Sk, dev, stream_form=True)
+        us = timed(lambda: layercall.layer_full_stream(x, src, y, wpack=w, workspace=ws), args.iters, args.warmup)
         print(json.dumps({"item": "loftr_layer_full_stream", "shape": name, "L": L, "S": Sk, "us": round(us, 1),
                           "attention_tflops_algorithmic_whole_layer": round(4.0 * L * Sk * 256 / us * 1e-6, 1)}))
         del x, src, y, ws
@@ -129,10 +128,9 @@ def c2_items(args, dev):
     x3, x2 = torch.randn(1, 7000, 256, generator=g).to(dev), torch.randn(1, 4800, 256, generator=g).to(dev)
     y3, y2 = torch.empty_like(x3), torch.empty_like(x2)
     w = packing.pack_coarse_layer(sd, "loftr_coarse.layers.0.").to(dev)
-    ws = torch.empty(hip.load().ophip_encoder_full_workspace_bytes(1, 7000, 4800), dtype=torch.uint8, device=dev)
+    ws = layercall.workspace("full", 1, 7000, 4800, dev)
     for cross in (0, 1):
-        us = timed(lambda: hip.call("ophip_encoder_layer_full_x3", hip.ptr(x3), hip.ptr(x2), hip.ptr(y3), hip.ptr(y2), 1, 7000, 4800,
-                                    hip.ptr(w), cross, hip.ptr(ws, None), S()), args.iters, args.warmup)
+        us = timed(lambda: layercall.layer(x3, x2, y3, y2, mode="full", wpack=w, is_cross=cross, workspace=ws), args.iters, args.warmup)
         attn = 4.0 * 256 * ((7000 * 4800 * 2) if cross else (7000 * 7000 + 4800 * 4800))
         print(json.dumps({"item": "layer_full_x3", "cross": cross, "us": round(us, 1), "attention_tflops_algorithmic_whole_layer": round(attn / us * 1e-6, 1)}))
     del x3, x2, y3, y2, ws
