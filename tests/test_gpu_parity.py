@@ -23,6 +23,7 @@ from onepose_st_amd import hip, host_math, layercall, matchcall, packing
 from onepose_st_amd.model import OnePosePlus_model
 from onepose_st_amd.pnp import ransac_PnP
 from onepose_st_amd.synthetic import make_synthetic_inputs
+from tests.coarse_faithful import plain_bf16_confidence          # float64 confidences of plain bf16, rounded where the kernel rounds
 
 pytestmark = pytest.mark.gpu
 
@@ -356,14 +357,6 @@ def coarse_equals_oracle(conf, ids, mconf, mk3, mkc, ref_conf, ref, rtol, mconf_
 
 
 PLAIN_BF16_LIKE_FOR_LIKE_TOL = dict(rtol=1e-3, atol=1e-7)
-
-
-def plain_bf16_confidence(f3, f2, temperature=0.08):
-    """float64 dual-softmax confidences of plain bf16 (nsplit 1), rounded where the kernel rounds: see the test below"""
-    from tests.bf16_faithful import bf16_round
-    inv_temp = float(np.float32(1.0) / np.float32(temperature + 1e-4))
-    sim = torch.einsum("nlc,nsc->nls", bf16_round(f3 * 0.0625).double(), bf16_round(f2 * 0.0625).double()) * inv_temp
-    return torch.softmax(sim, 1) * torch.softmax(sim, 2)
 
 
 @pytest.mark.parametrize("B,N,hc,wc", [(1, 300, 10, 13), (2, 129, 9, 9), (1, 1000, 30, 40)])
