@@ -1,8 +1,8 @@
 """Reader of the project's C headers (``include/onepose_*.h``: one per entry of ``LIBRARIES`` below, plus ``onepose_pnp.h`` of the host
 library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures, the constants and the loaded
 handle of one HIP library.  The headers are the only place a C signature or a constant is written; the modules ``LIBRARIES`` names and
-``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES``; the host library alone keeps a loader of its own
-(``pnp.py``).
+``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES`` or, with its header under ``include/ext/``, of
+``EXTENSIONS``; the host library alone keeps a loader of its own (``pnp.py``).
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -36,6 +36,16 @@ SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c
 RETURN_TYPES = (*SCALARS, "const char*", "void", "void*")
 _POINTEES = (*SCALARS, "char", "unsigned char", "void")
 _NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp'])})_\w+"          # oppnp: the host library (pnp.py)
+
+# Libraries outside the table above: the same five columns, the header under include/ext/ (so the header path holds
+# the directory).  Bound with ``Binding.of`` like an entry of ``LIBRARIES``, read with the library's own prefix (``names_of``), and checked
+# and loaded by __graft_entry__.build() too.
+EXTENSIONS = (Library("opfcx", "ext/onepose_fine_context.h", "libonepose_fine_context.so", "OPFCX_LIB", "fine_context"),)
+
+
+def names_of(*prefixes: str) -> str:
+    """The pattern of an entry point's name for libraries with these C prefixes: what ``parse`` and ``Binding`` take as ``names``"""
+    return rf"\b(?:{'|'.join(prefixes)})_\w+"
 
 
 class HeaderError(ValueError):
@@ -71,7 +81,9 @@ def _declarator(text: str, where: str, structs=()) -> tuple:
     return ctype, m.group(2), int(m.group(3)) if m.group(3) else None
 
 
-def parse(text: str) -> Header:
+def parse(text: str, names: str | None = None) -> Header:
+    """``names``: the pattern of an entry point's name (``names_of``); ``None``: the table's prefixes and the host library's (``_NAME``)"""
+    names = _NAME if names is None else names
     text = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group().count("\n"), text, flags=re.S)      # comments go, line numbers stay
     text = re.sub(r"//[^\n]*", "", text)
 
@@ -91,7 +103,7 @@ def parse(text: str) -> Header:
         structs[m.group(2)] = tuple(fields)
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
     prototypes, read_at = {}, set()
-    for m in re.finditer(rf"(?:\A|(?<=[;{{}}]))\s*([\w\s*]+?)\s*({_NAME})\s*\(", text):
+    for m in re.finditer(rf"(?:\A|(?<=[;{{}}]))\s*([\w\s*]+?)\s*({names})\s*\(", text):
         where, ret = f"{line(m.start(2))}, {m.group(2)}", _type(m.group(1))
         end = re.compile(r"([^();{}]*)\)\s*;").match(text, m.end())
         if ret not in RETURN_TYPES or end is None:
@@ -100,7 +112,7 @@ def parse(text: str) -> Header:
         prototypes[m.group(2)] = Prototype(m.group(2), ret, tuple(
             _declarator(p, where, structs)[:2] for p in ([] if params in ("", "void") else params.split(","))))
         read_at.add(m.start(2))
-    for m in re.finditer(rf"({_NAME})\s*\(", text):          # nothing that looks like an entry point may be left out silently
+    for m in re.finditer(rf"({names})\s*\(", text):          # nothing that looks like an entry point may be left out silently
         if m.start() not in read_at:
             raise HeaderError(f"{line(m.start())}, {m.group(1)}: declared in a form this reader does not know")
     return Header(prototypes, defines, structs)
@@ -144,12 +156,12 @@ class Binding:
     ``signatures`` (name -> (restype, argtypes)), ``exported_symbols``, ``abi_version`` (``constant("ABI_VERSION")``), ``path``
     (the environment variable ``env``, read once here, or ``lib/<so>``) and ``handle`` (``None`` until ``load()``)."""
 
-    def __init__(self, header: str, so: str, prefix: str, env: str, mirrors: dict | None = None):
+    def __init__(self, header: str, so: str, prefix: str, env: str, mirrors: dict | None = None, names: str | None = None):
         pkg = os.path.dirname(os.path.abspath(__file__))
         self.so, self.prefix = so, prefix
         self.path = os.environ.get(env) or os.path.join(pkg, "lib", so)
         self.header_path = os.path.join(os.path.dirname(pkg), "include", header)         # where csrc/Makefile finds it too
-        self.header = parse(open(self.header_path).read() if os.path.exists(self.header_path) else "")
+        self.header = parse(open(self.header_path).read() if os.path.exists(self.header_path) else "", names)
         self.signatures = {name: signature(proto, mirrors) for name, proto in self.header.prototypes.items()}
         self.exported_symbols = tuple(self.signatures)
         self.handle = None
@@ -159,9 +171,9 @@ class Binding:
 
     @classmethod
     def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
-        """The binding of the ``LIBRARIES`` entry whose module is ``module`` (a ``__name__``)"""
-        entry, = [e for e in LIBRARIES if e.module == module.rpartition(".")[2]]
-        return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors)
+        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``) entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES + EXTENSIONS if e.module == module.rpartition(".")[2]]
+        return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors, names_of(entry.prefix) if entry in EXTENSIONS else None)
 
     @property
     def abi_version(self):

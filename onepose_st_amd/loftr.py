@@ -56,6 +56,12 @@ matching again eagerly on the same final rows; ``lazy_reruns`` counts those call
 sub-batches of pairs within ``n`` bytes (:meth:`LoFTR_for_OnePose_Plus.coarse_batch_bytes`).  Sinkhorn matching needs the matrix:
 ``"lazy"`` with it is a ``ValueError``, as is any other value.
 
+``fine_concat_coarse_feat`` = ``True`` (LoFTR's published setting): the model owns ``fine_preprocess.down_proj`` and
+``fine_preprocess.merge_feat`` (``Linear(256, 128)`` with bias each, also with ``enable_fine_matching=False``: the public checkpoints load
+strictly), and between the window gather and the fine transformer every window row becomes ``merge_feat(cat[row, down_proj(coarse row of
+its match)])`` on both images: ``fine_context.merge`` (``opfcx_merge`` of ``libonepose_fine_context.so``), in place, on the coarse
+transformer's final rows.  The fine-only branch has no such rows and raises, as does ``sfm_fine``.
+
 Malformed masks (a lone mask, another dtype, image-resolution masks, a wrong batch or grid), malformed scale / keypoint tensors, a tensor
 without its partner, V > 1 with provided matches or extraction, and coarse extraction with a ``feature_hook`` raise
 ``NotImplementedError`` before anything runs.  No CPU fallback.
@@ -68,7 +74,7 @@ import ctypes
 import torch
 import torch.nn as nn
 
-from . import hip, host_math, layercall, packing
+from . import fine_context, hip, host_math, layercall, packing
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .lazy_conf import LazyConfMatrixBase
@@ -78,6 +84,9 @@ from .rows import rows_encoder_layer
 
 # this build's own config keys and their defaults.  "hip_conf_matrix": "eager" stores conf_matrix, "lazy" does not (see the module text)
 BUILD_KEYS = {"hip_conf_matrix": "eager"}
+# what the fine-only branch (and sfm_fine, which is built on it) says of a matcher with fine_concat_coarse_feat
+FINE_ONLY_WITH_CONTEXT = ("fine_concat_coarse_feat with provided coarse matches: the fine windows take their context from the coarse "
+                          "transformer's output, which the fine-only branch does not compute (the published class fails there too)")
 
 
 class _ReferenceConfig(dict):
@@ -145,8 +154,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                 raise NotImplementedError("match_coarse.sparse_spvs: training output (conf_matrix_with_bin)")
         if cc["temp_bug_fix"]:
             raise NotImplementedError("temp_bug_fix: the reference's detector config runs the original (floor-division) position table")
-        if config["fine_concat_coarse_feat"]:
-            raise NotImplementedError("fine_concat_coarse_feat")
+        self.fine_context = bool(config["fine_concat_coarse_feat"])
         W = int(config["fine_window_size"])
         if W < 3 or W % 2 == 0 or W * W > 128:             # FineMatching's grid step is 2 / (W - 1); W * W heat-map slots <= 128
             raise ValueError("fine_window_size must be odd, from 3 to 11")
@@ -158,6 +166,10 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                                                       "block_dims": list(config["resnetfpn"]["block_dims"]), "output_layers": [3, 1]}})
         self.loftr_coarse = EncoderParams(cc["layer_names"], cc["d_model"], cc["nhead"])
         self.loftr_fine = EncoderParams(cf["layer_names"], cf["d_model"], cf["nhead"])
+        if self.fine_context:                          # the published FinePreprocess holds them whether or not the fine stage runs
+            self.fine_preprocess = nn.Module()
+            self.fine_preprocess.down_proj = nn.Linear(cc["d_model"], cf["d_model"], bias=True)
+            self.fine_preprocess.merge_feat = nn.Linear(2 * cf["d_model"], cf["d_model"], bias=True)
         if self.sinkhorn:                              # the reference's CoarseMatching holds bin_score in the sinkhorn form only
             self.coarse_matching = nn.Module()
             self.coarse_matching.bin_score = nn.Parameter(torch.tensor(float(mc["skh_init_bin_score"]), requires_grad=True))
@@ -214,6 +226,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                 "fine": [{n: t.to(device) for n, t in packing.pack_fine_layer_full_x3(sd, f"loftr_fine.layers.{i}.").items()}
                          for i in range(len(self.loftr_fine.layer_names))],
                 "bin_score": float(sd["coarse_matching.bin_score"]) if self.sinkhorn else None,
+                "context": packing.pack_fine_context(sd).to(device) if self.fine_context else None,
             })
         return self._packed[1]
 
@@ -300,6 +313,8 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                 raise NotImplementedError("'mkpts0_c' and 'mkpts1_c' must hold the same number of matches")
             if V != 1 or V1 != 1:
                 raise NotImplementedError("provided coarse matches: one pair per call (the reference's b_ids are all 0)")
+            if self.fine_context:
+                raise NotImplementedError(FINE_ONLY_WITH_CONTEXT)
         if ext_c or ext_f:
             if V != 1 or V1 != 1:
                 raise NotImplementedError("feature extraction: one pair per call (the reference squeezes scale0 to [2])")
@@ -346,7 +361,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
                          "mconf": mconf, "mkpts0_c": mk0c, "mkpts1_c": mk1c})
         if self.enable_fine_matching:
             self._fine(Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, b_ids.shape[0], hw0_c, hw0_f, hw1_c, hw1_f, img0.shape[2], s1,
-                       scaled=has_s or fine_only, debug=debug)
+                       scaled=has_s or fine_only, debug=debug, x0=x0, x1=x1)
         else:
             data.update({"mkpts0_f": mk0c, "mkpts1_f": mk1c})
         if debug and x0 is not None:
@@ -477,10 +492,11 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         return b_ids, i_ids, j_ids, m_bids, gt_mask, mconf, mk0[:, :2].contiguous(), mk1c.contiguous()
 
     def _fine(self, Wb, data, ff0, ff1, b_ids, i_ids, j_ids, mk0c, mk1c, K, hw0_c, hw0_f, hw1_c, hw1_f, h0i, s1, scaled, debug,
-              b_ids1=None, scale_ids=None):
+              b_ids1=None, scale_ids=None, x0=None, x1=None):
         """fine stage (windows on both images, two-stream fine transformer, correlation + soft-argmax) on the matches' cells.
         ``b_ids1`` / ``scale_ids`` (``sfm_fine``: every row names its own two images): the batch index into ``ff1`` and the row of ``s1``
-        when they are not ``b_ids``"""
+        when they are not ``b_ids``.  ``x0 [V, L0, 256]``, ``x1 [V, L1, 256]``: the coarse transformer's final rows, which a matcher with
+        ``fine_concat_coarse_feat`` merges into the windows (``fine_context.merge``, in place) ahead of the fine transformer"""
         b_ids1 = b_ids if b_ids1 is None else b_ids1
         scale_ids = b_ids if scale_ids is None else scale_ids
         call, P, S = hip.call, hip.ptr, hip.stream_handle()
@@ -497,6 +513,12 @@ class LoFTR_for_OnePose_Plus(nn.Module):
              P(i_ids, torch.int64), K, hw0_c[1], stride, Wf, P(f0), S)
         call("ophip_fine2_gather_b", P(ff1c), ff1c.stride(0) if ff1c.shape[0] > 1 else 0, P(b_ids1, torch.int64), hw1_f[0], hw1_f[1],
              P(j_ids, torch.int64), K, hw1_c[1], hw1_f[0] // hw1_c[0], Wf, P(f1), S)
+        if self.fine_context:
+            if x0 is None or x1 is None:
+                raise NotImplementedError(FINE_ONLY_WITH_CONTEXT)
+            fine_context.merge(f0, f1, x0, x1, b_ids, i_ids, j_ids, Wf, Wb["context"])
+            if debug:                                  # the windows the fine transformer reads (its layers write new tensors)
+                data["_fine_in0"], data["_fine_in1"] = f0, f1
         T = K * WW
         attn = "ophip_fine2_full_attention" if self.fine_full else "ophip_fine2_attention"
 
@@ -552,9 +574,10 @@ class LoFTR_for_OnePose_Plus(nn.Module):
 def build_2D_match_model(args: dict) -> LoFTR_for_OnePose_Plus:
     """``local_feature_2D_detector.py:24-37``: LoFTR with the default config, checkpoint loaded strictly (``weights_only=True``:
     nothing from the file is executed), ``eval()``.  The reference also seeds the global generators (``pl.seed_everything``): inference
-    draws no random numbers, so there is nothing to seed here."""
+    draws no random numbers, so there is nothing to seed here.  ``args["config"]`` (optional, this build's): another config, e.g. the
+    published LoFTR one (``fine_concat_coarse_feat`` True, window 5) for the public checkpoints."""
     if args["method"] != "LoFTR":
         raise NotImplementedError
-    matcher = LoFTR_for_OnePose_Plus(config=copy.deepcopy(default_cfg))
+    matcher = LoFTR_for_OnePose_Plus(config=copy.deepcopy(args.get("config") or default_cfg))
     state_dict = torch.load(args["weight_path"], map_location="cpu", weights_only=True)["state_dict"]
     return load_matcher_checkpoint(matcher, state_dict)

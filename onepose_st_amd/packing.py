@@ -103,6 +103,20 @@ def _bytes(*tensors) -> torch.Tensor:
     return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in tensors])
 
 
+def pack_fine_context(sd: dict, prefix: str = "fine_preprocess.") -> torch.Tensor:
+    """uint8 block ``[hi: Wd | Wm[:, :128] | Wm[:, 128:]][lo: same][bd bm f32]`` for ``opfcx_merge`` (``opfcx_wpack_bytes()`` long):
+    ``down_proj`` and the two halves of ``merge_feat`` -- the fine (window) half first, as the published ``FinePreprocess`` concatenates
+    -- in the 16-k fragment order of :func:`pack_linear_frag16`, split-bf16 planes."""
+    wd, wm = sd[prefix + "down_proj.weight"], sd[prefix + "merge_feat.weight"]
+    if tuple(wd.shape) != (128, 256) or tuple(wm.shape) != (128, 256):
+        raise ValueError("the fine-context kernel is specialised for down_proj and merge_feat of Linear(256, 128)")
+    hi, lo = split_planes(torch.cat([pack_linear_frag16(m) for m in (wd, wm[:, :128], wm[:, 128:])]))
+    bias = torch.cat([sd[prefix + n].detach().float().cpu().reshape(-1) for n in ("down_proj.bias", "merge_feat.bias")])
+    out = _bytes(hi, lo, bias)
+    assert out.numel() == 2 * 2 * 128 * 512 + 4 * 256
+    return out
+
+
 def pack_coarse_layer_bf16(sd: dict, prefix: str) -> torch.Tensor:
     """uint8 block ``[hi: Wq | Wkv | Wm | W0 | W2][lo: same][norm1.w norm1.b norm2.w norm2.b f32]`` for
     ``ophip_encoder_layer_bf16`` (Wkv in the per-wave row order of :func:`pack_coarse_layer`)."""

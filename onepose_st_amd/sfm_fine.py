@@ -62,6 +62,9 @@ def _check_matcher(matcher):
         raise NotImplementedError("a matcher without fine matching has nothing to refine")
     if matcher.training:
         raise NotImplementedError("inference only")
+    if getattr(matcher, "fine_context", False):
+        from .loftr import FINE_ONLY_WITH_CONTEXT
+        raise NotImplementedError(FINE_ONLY_WITH_CONTEXT)
 
 
 # ---- 1. the feature bank ----------------------------------------------------------------------------------------------------------------

@@ -77,9 +77,11 @@ def make_synthetic_state_dict(seed: int = 0, config: dict | None = None, backbon
     return {k: v.float().contiguous() for k, v in sd.items()}
 
 
-def make_synthetic_loftr_state_dict(seed: int = 0, n_coarse: int = 8, n_fine: int = 2) -> dict:
+def make_synthetic_loftr_state_dict(seed: int = 0, n_coarse: int = 8, n_fine: int = 2, fine_concat_coarse_feat: bool = False) -> dict:
     """Seeded weights with the key layout of ``LoFTR_for_OnePose_Plus`` (``loftr_for_sfm/loftr.py:16-31``: ``backbone.*``,
-    ``loftr_coarse.layers.{0..7}.*``, ``loftr_fine.layers.{0,1}.*``; what ``build_2D_match_model`` loads strictly)."""
+    ``loftr_coarse.layers.{0..7}.*``, ``loftr_fine.layers.{0,1}.*``; what ``build_2D_match_model`` loads strictly).
+    ``fine_concat_coarse_feat``: also ``fine_preprocess.down_proj.*`` and ``fine_preprocess.merge_feat.*`` (``Linear(256, 128)`` with bias,
+    the published LoFTR checkpoints' layout), drawn after every other tensor: the other keys keep their values."""
     gen = torch.Generator().manual_seed(seed)
     sd: dict = {}
     torch_state = torch.random.get_rng_state()
@@ -96,6 +98,10 @@ def make_synthetic_loftr_state_dict(seed: int = 0, n_coarse: int = 8, n_fine: in
         sd["backbone." + k] = v
     _encoder_state(gen, "loftr_coarse", 256, n_coarse, sd)
     _encoder_state(gen, "loftr_fine", 128, n_fine, sd)
+    if fine_concat_coarse_feat:
+        for name in ("down_proj", "merge_feat"):
+            sd[f"fine_preprocess.{name}.weight"] = _xavier(gen, 128, 256)
+            sd[f"fine_preprocess.{name}.bias"] = (torch.rand(128, generator=gen) * 2 - 1) / math.sqrt(256)
     return {k: v.float().contiguous() for k, v in sd.items()}
 
 
