@@ -2,7 +2,7 @@
 library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures, the constants and the loaded
 handle of one HIP library.  The headers are the only place a C signature or a constant is written; the modules ``LIBRARIES`` names and
 ``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES`` or, with its header under ``include/ext/``, of
-``EXTENSIONS``; the host library alone keeps a loader of its own (``pnp.py``).
+``EXTENSIONS`` or ``ADDONS``; the host library alone keeps a loader of its own (``pnp.py``).
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -41,6 +41,9 @@ _NAME = rf"\b(?:{'|'.join([entry.prefix for entry in LIBRARIES] + ['oppnp'])})_\
 # the directory).  Bound with ``Binding.of`` like an entry of ``LIBRARIES``, read with the library's own prefix (``names_of``), and checked
 # and loaded by __graft_entry__.build() too.
 EXTENSIONS = (Library("opfcx", "ext/onepose_fine_context.h", "libonepose_fine_context.so", "OPFCX_LIB", "fine_context"),)
+# Libraries beside the inference path (training and validation signals): rows like those of ``EXTENSIONS`` in every respect, kept apart
+# because that table is the LoFTR matcher's.
+ADDONS = (Library("opsup", "ext/onepose_supervision.h", "libonepose_supervision.so", "OPSUP_LIB", "supervision"),)
 
 
 def names_of(*prefixes: str) -> str:
@@ -171,9 +174,9 @@ class Binding:
 
     @classmethod
     def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
-        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``) entry whose module is ``module`` (a ``__name__``)"""
-        entry, = [e for e in LIBRARIES + EXTENSIONS if e.module == module.rpartition(".")[2]]
-        return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors, names_of(entry.prefix) if entry in EXTENSIONS else None)
+        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, or ``ADDONS``) entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS if e.module == module.rpartition(".")[2]]
+        return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors, None if entry in LIBRARIES else names_of(entry.prefix))
 
     @property
     def abi_version(self):
