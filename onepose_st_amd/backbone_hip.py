@@ -71,13 +71,12 @@ class HipBackbone:
         Ho, Wo = (x.H + 2 * (ks // 2) - ks) // stride + 1, (x.W + 2 * (ks // 2) - ks) // stride + 1
         out = _Planes(B, Ho, Wo, cop, dev, self.nsplit == 3) if planes else None
         o32 = torch.empty(B, Ho, Wo, f32_channels, dtype=torch.float32, device=dev) if f32_channels else None
-        P = hip.ptr
-        hip.call("ophip_conv2d_bf16", P(x.hi, None), P(x.lo, None), B, x.H, x.W, cip, P(wpack, None), cop, ks, stride, act,
-                 P(res.hi, None) if res is not None else None, P(res.lo, None) if res is not None else None,
-                 P(up) if up is not None else None, up.shape[1] if up is not None else 0, up.shape[2] if up is not None else 0,
-                 P(table) if table is not None else None,
-                 P(out.hi, None) if out is not None else None, P(out.lo, None) if out is not None else None,
-                 P(o32) if o32 is not None else None, f32_channels, self.nsplit, hip.stream_handle())
+        hip.launch("ophip_conv2d_bf16", dict(
+            in_hi=x.hi, in_lo=x.lo, B=B, Hin=x.H, Win=x.W, cin_pad=cip, wpack=wpack, cout_pad=cop, ks=ks, stride=stride, act=act,
+            res_hi=res.hi if res is not None else None, res_lo=res.lo if res is not None else None,
+            up=up, Hup=up.shape[1] if up is not None else 0, Wup=up.shape[2] if up is not None else 0, table=table,
+            out_hi=out.hi if out is not None else None, out_lo=out.lo if out is not None else None, out_f32=o32, out_c=f32_channels,
+            nsplit=self.nsplit))
         return out if planes else o32
 
     @torch.no_grad()
@@ -96,8 +95,7 @@ class HipBackbone:
         dev = img.device
         split = self.nsplit == 3
         x0 = _Planes(B, H // 2, W // 2, 128, dev, split)
-        hip.call("ophip_stem_conv7", hip.ptr(img), B, H, W, hip.ptr(blocks["stem"]), hip.ptr(x0.hi, None), hip.ptr(x0.lo, None),
-                 self.nsplit, hip.stream_handle())
+        hip.launch("ophip_stem_conv7", dict(image=img, B=B, H=H, W=W, wpack=blocks["stem"], out_hi=x0.hi, out_lo=x0.lo, nsplit=self.nsplit))
         x = x0
         for layer, stride in (("layer1", 1), ("layer2", 2), ("layer3", 2)):
             for i in range(2):

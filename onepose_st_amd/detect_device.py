@@ -34,6 +34,7 @@ from .track_device import MAX_CROP, TrackState, check_crop_size, check_K
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 MAX_VIEWS, MAX_TRIALS, DEFAULT_TRIALS, MAX_ROWS, MAX_SIDE, SCORE_CHUNK, STATUS_NO_MODEL, STATUS_DEGENERATE, STATUS_NEEDS_MORE = map(_BINDING.constant, (
@@ -110,7 +111,6 @@ def vote(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size: int = 512, coun
     a = _Inputs(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size, count)
     V, cap, dev = a.V, a.cap, a.dev
     nbytes = load().opdet_workspace_bytes(cap, V, int(trials))
-    P = hip.ptr
     with hip.enqueue_on(dev, stream):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         boxes = torch.empty(V, 4, dtype=torch.int32, device=dev)
@@ -119,11 +119,10 @@ def vote(mkpts0, mkpts1, b_ids, view_hw, query_hw, K, crop_size: int = 512, coun
         mask = torch.zeros(cap, dtype=torch.uint8, device=dev)
         winner = torch.empty(1, dtype=torch.int32, device=dev)
         st = TrackState(dev)
-        call("opdet_detect", P(a.mk0), P(a.mk1), P(a.b_ids, torch.int64), P(a.count, torch.int32), cap, V, P(a.view_hw, torch.int32), a.H, a.W,
-             P(a.K, torch.float64), a.S, int(min_matches), float(ransac_reproj_threshold), float(confidence), int(trials), hip.seed_arg(seed), P(ws, None),
-             nbytes, P(boxes, torch.int32), P(n_in, torch.int32), P(affine, torch.float64), P(status, torch.int32), P(mask, torch.uint8),
-             P(winner, torch.int32), P(st.box, torch.int32), P(st.flag, torch.int32), P(st.K_crop, torch.float64), P(st.trans, torch.float64),
-             hip.stream_arg(stream))
+        launch("opdet_detect", dict(mk0=a.mk0, mk1=a.mk1, b_ids=a.b_ids, count=a.count, cap=cap, V=V, view_hw=a.view_hw, H=a.H, W=a.W, K=a.K, S=a.S,
+                                    min_matches=min_matches, reproj_thr=ransac_reproj_threshold, confidence=confidence, trials=trials, seed=seed,
+                                    workspace=ws, workspace_bytes=nbytes, boxes=boxes, n_inliers=n_in, affine=affine, status=status,
+                                    inlier_mask=mask, winner=winner, box=st.box, flag=st.flag, K_crop=st.K_crop, trans=st.trans), stream)
     ranges = ws[:8 * V].view(torch.int32).view(V, 2)       # the first table of the workspace
     return DeviceDetection(st, boxes, n_in, affine, status, winner, mask, ranges, keep=(ws, a))
 
@@ -134,7 +133,7 @@ class stages:
     @staticmethod
     def ranges(b_ids, count, cap, views, stream=None):
         out = torch.empty(views, 2, dtype=torch.int32, device=b_ids.device)
-        call("opdet_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(views), hip.ptr(out, torch.int32), hip.stream_arg(stream))
+        launch("opdet_ranges", dict(b_ids=b_ids, count=count, cap=cap, V=views, ranges=out), stream)
         return out
 
     @staticmethod
@@ -143,8 +142,8 @@ class stages:
         V, dev = ranges.shape[0], mkpts0.device
         samples = torch.empty(V, trials, 3, dtype=torch.int32, device=dev)
         cnt = torch.empty(V, trials, dtype=torch.int32, device=dev)
-        call("opdet_score", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), mkpts0.shape[0], V, int(trials), int(min_matches),
-             float(reproj), hip.seed_arg(seed), hip.ptr(samples, torch.int32), hip.ptr(cnt, torch.int32), hip.stream_arg(stream))
+        launch("opdet_score", dict(mk0=mkpts0, mk1=mkpts1, ranges=ranges, cap=mkpts0.shape[0], V=V, trials=trials, min_matches=min_matches,
+                                   reproj_thr=reproj, seed=seed, samples=samples, cnt=cnt), stream)
         return samples, cnt
 
     @staticmethod
@@ -153,9 +152,9 @@ class stages:
         V, trials, dev = cnt.shape[0], cnt.shape[1], mkpts0.device
         best, n_in, status = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(3))
         mask = torch.zeros(mkpts0.shape[0], dtype=torch.uint8, device=dev)
-        call("opdet_select", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), hip.ptr(count, torch.int32), hip.ptr(samples, torch.int32),
-             hip.ptr(cnt, torch.int32), mkpts0.shape[0], V, trials, int(min_matches), float(reproj), float(confidence), hip.ptr(best, torch.int32),
-             hip.ptr(n_in, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
+        launch("opdet_select", dict(mk0=mkpts0, mk1=mkpts1, ranges=ranges, count=count, samples=samples, cnt=cnt, cap=mkpts0.shape[0], V=V,
+                                    trials=trials, min_matches=min_matches, reproj_thr=reproj, confidence=confidence, best=best, n_inliers=n_in,
+                                    status=status, inlier_mask=mask), stream)
         return best, n_in, status, mask
 
     @staticmethod
@@ -164,9 +163,8 @@ class stages:
         V, dev = ranges.shape[0], mkpts0.device
         affine = torch.empty(V, 6, dtype=torch.float64, device=dev)
         boxes = torch.empty(V, 4, dtype=torch.int32, device=dev)
-        call("opdet_fit_box", hip.ptr(mkpts0), hip.ptr(mkpts1), hip.ptr(ranges, torch.int32), hip.ptr(view_hw, torch.int32), mkpts0.shape[0], V,
-             int(query_hw[0]), int(query_hw[1]), hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8),
-             hip.ptr(affine, torch.float64), hip.ptr(boxes, torch.int32), hip.stream_arg(stream))
+        launch("opdet_fit_box", dict(mk0=mkpts0, mk1=mkpts1, ranges=ranges, view_hw=view_hw, cap=mkpts0.shape[0], V=V, H=query_hw[0], W=query_hw[1],
+                                     n_inliers=n_inliers, status=status, inlier_mask=mask, affine=affine, boxes=boxes), stream)
         return affine, boxes
 
     @staticmethod
@@ -176,7 +174,6 @@ class stages:
         winner = torch.empty(1, dtype=torch.int32, device=dev)
         st = TrackState(dev)
         K = K.contiguous().view(9)
-        call("opdet_vote", hip.ptr(boxes, torch.int32), hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), boxes.shape[0], int(query_hw[0]),
-             int(query_hw[1]), hip.ptr(K, torch.float64), int(crop_size), hip.ptr(winner, torch.int32), hip.ptr(st.box, torch.int32),
-             hip.ptr(st.flag, torch.int32), hip.ptr(st.K_crop, torch.float64), hip.ptr(st.trans, torch.float64), hip.stream_arg(stream))
+        launch("opdet_vote", dict(boxes=boxes, n_inliers=n_inliers, status=status, V=boxes.shape[0], H=query_hw[0], W=query_hw[1], K=K, S=crop_size,
+                                  winner=winner, box=st.box, flag=st.flag, K_crop=st.K_crop, trans=st.trans), stream)
         return winner, st

@@ -13,6 +13,7 @@ from . import cabi, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call, order = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call, _BINDING.order
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 TILE_ROWS, MAX_ROWS = map(_BINDING.constant, ("TILE_ROWS", "MAX_ROWS"))
@@ -47,10 +48,8 @@ def merge(win0, win1, x0, x1, b_ids, i_ids, j_ids, W, wpack, out=None):
             raise ValueError(f"{name}: a contiguous tensor [{K}], got {list(t.shape)}")
     if K == 0:                                          # nothing to launch (and empty tensors have no address to hand over)
         return out0, out1
-    P = hip.ptr
     context = torch.empty(2 * K * 128, device=win0.device)
-    _BINDING.call_named("opfcx_merge", win0=P(win0), win1=P(win1), coarse0=P(x0), coarse0_bstride=hip.bstride(x0), coarse1=P(x1),
-                        coarse1_bstride=hip.bstride(x1), b_ids=P(b_ids, torch.int64), i_ids=P(i_ids, torch.int64), j_ids=P(j_ids, torch.int64),
-                        K=K, B=B, L0=x0.shape[1], L1=x1.shape[1], W=int(W), wpack=P(wpack, None), context=P(context), out0=P(out0),
-                        out1=P(out1), stream=hip.stream_handle())
+    launch("opfcx_merge", dict(win0=win0, win1=win1, coarse0=x0, coarse0_bstride=hip.bstride(x0), coarse1=x1, coarse1_bstride=hip.bstride(x1),
+                               b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, K=K, B=B, L0=x0.shape[1], L1=x1.shape[1], W=W, wpack=wpack, context=context,
+                               out0=out0, out1=out1))
     return out0, out1

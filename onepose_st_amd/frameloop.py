@@ -95,8 +95,8 @@ def crop_query(frame_u8: torch.Tensor, bbox, crop_size: int = 512) -> torch.Tens
     frame_u8 = frame_u8.contiguous()
     out = torch.empty(1, 1, crop_size, crop_size, dtype=torch.float32, device=frame_u8.device)
     x0, y0, x1, y1 = [int(v) for v in bbox]
-    hip.call("ophip_crop_resize_gray", hip.ptr(frame_u8, torch.uint8), frame_u8.shape[0], frame_u8.shape[1], x0, y0, x1, y1, crop_size,
-             hip.ptr(out), hip.stream_handle())
+    hip.launch("ophip_crop_resize_gray", dict(image=frame_u8, H=frame_u8.shape[0], W=frame_u8.shape[1], x0=x0, y0=y0, x1=x1, y1=y1, S=crop_size,
+                                              out=out))
     return out
 
 

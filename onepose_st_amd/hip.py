@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import functools
 
 import torch
 
@@ -94,45 +93,87 @@ def stream_arg(stream):
     return ctypes.c_void_p(stream.cuda_stream) if stream is not None else stream_handle()
 
 
-def _void_ptr(t):
-    """``void*``: a tensor of any dtype (packed byte blocks), or an address C handed out (``ophip_coarse_frag_planes``) as it is"""
-    return t if isinstance(t, ctypes.c_void_p) else ptr(t, None)
-
-
-def _byte_ptr(t):
-    """``unsigned char*`` (masks, gt_mask): bytes, as ``torch.bool`` or ``torch.uint8``"""
-    return ptr(t, torch.bool if t is not None and t.dtype == torch.bool else torch.uint8)
-
-
-_CONVERTER = {"int": int, "long long": int, "float": float, "double": float, "unsigned": lambda v: ctypes.c_uint(int(v)),
-              "float*": ptr, "long long*": functools.partial(ptr, dtype=torch.int64), "int*": functools.partial(ptr, dtype=torch.int32),
-              "unsigned char*": _byte_ptr, "void*": _void_ptr}
-_CONVERT = {}
-
-
-def converters(entry: str) -> dict:
-    """``{parameter name: converter}`` of ``entry`` without ``stream``, in the header's order and each from the header's C type of that
-    parameter (``const`` set aside); made on first use"""
-    if entry not in _CONVERT:
-        names = [n for _, n in PROTOTYPES[entry].params]
-        _CONVERT[entry] = ({n: _CONVERTER[c.replace("const ", "")] for c, n in PROTOTYPES[entry].params if n != "stream"}, names.index("stream"))
-    return _CONVERT[entry][0]
-
-
-def launch(entry: str, named: dict, stream=None) -> None:
-    """``call`` of ``entry`` on ``stream`` (a ``torch.cuda.Stream``; ``None``: the current one), every argument bound by its name in the
-    header and turned into what the header's C type of that parameter asks for: the launch step of ``matchcall`` and ``layercall``"""
-    conv = converters(entry)
-    if named.keys() != conv.keys():
-        order(entry, **named, stream=None)                     # TypeError: names every missing and every unknown parameter
-    args = [c(named[n]) for n, c in conv.items()]
-    args.insert(_CONVERT[entry][1], stream_arg(stream))
-    call(entry, *args)                                         # this module's ``call``: whoever replaces it (a test's spy) sees these calls too
-
-
 def seed_arg(seed):
     """An ``unsigned long long`` seed: ``seed`` mod 2^64"""
     return ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))
+
+
+_CDATA = (ctypes.c_int.__mro__[-2], type(ctypes.byref(ctypes.c_int())))      # every ctypes object, and what ``ctypes.byref`` returns
+
+
+def _pointer(dtype):
+    """The converter of a pointer: ``None`` -> NULL; a ctypes object as it is (an address C handed out, a ``ctypes.byref`` out-parameter);
+    else ``ptr`` of a device tensor of ``dtype`` (``None``: any, e.g. packed byte blocks and bf16 planes)"""
+    return lambda t: t if isinstance(t, _CDATA) else ptr(t, dtype)
+
+
+def _byte_ptr(t):
+    """``unsigned char*`` (masks, gt_mask, images): bytes, as ``torch.bool`` or ``torch.uint8``"""
+    return t if isinstance(t, _CDATA) else ptr(t, torch.bool if t is not None and t.dtype == torch.bool else torch.uint8)
+
+
+def _ctypes_object(t):
+    """``void**`` and a pointer to a mirrored structure: a ctypes object (or ``None``) as it is"""
+    if t is None or isinstance(t, _CDATA):
+        return t
+    if isinstance(t, torch.Tensor) and not t.is_cuda:
+        raise HipLibraryError(NO_CPU_FALLBACK)
+    raise TypeError(f"expected a ctypes object, got {type(t).__name__}")
+
+
+# The one table from a parameter's C type (``const`` set aside) to what turns a Python value into it.  A new C parameter type is one row here.
+_CONVERTER = {"int": int, "long long": int, "size_t": int, "float": float, "double": float, "unsigned": lambda v: ctypes.c_uint(int(v)),
+              "unsigned long long": seed_arg, "float*": _pointer(torch.float32), "double*": _pointer(torch.float64),
+              "long long*": _pointer(torch.int64), "int*": _pointer(torch.int32), "unsigned char*": _byte_ptr, "void*": _pointer(None),
+              "void**": _ctypes_object}
+
+
+def launcher(binding: cabi.Binding, module: dict):
+    """The launch step of one library: ``launch`` (and ``launch.converters``) of ``binding``, calling through ``module["call"]`` (the
+    binding module's ``globals()``: whoever replaces ``<module>.call``, a test's spy, sees these calls too)."""
+    made = {}
+
+    def converters(entry: str) -> dict:
+        """``{parameter name: converter}`` of ``entry`` without ``stream``, in the header's order and each from the header's C type of
+        that parameter (``const`` set aside); made on first use.  ``HeaderError`` for a type the table has no row for."""
+        if entry not in made:
+            conv = {}
+            for c, n in binding.header.prototypes[entry].params:
+                bare = c.replace("const ", "")
+                if n != "stream" and bare not in _CONVERTER and bare[:-1] not in binding.header.structs:
+                    raise cabi.HeaderError(f"{entry}, {n}: no converter for {c!r} (hip._CONVERTER)")
+                conv[n] = _CONVERTER.get(bare, _ctypes_object)
+            if "stream" not in conv:
+                raise cabi.HeaderError(f"{entry} takes no stream: it is called with call / call_named")
+            made[entry] = (conv, list(conv).index("stream"))
+            del conv["stream"]
+        return made[entry][0]
+
+    def launch(entry: str, named: dict, stream=None) -> None:
+        """``call`` of ``entry`` on ``stream`` (a ``torch.cuda.Stream``; ``None``: the current one), every argument bound by its name in
+        the header and turned into what the header's C type of that parameter asks for.  A refused value raises what ``ptr`` raises, with
+        the entry and the parameter in front."""
+        conv = converters(entry)
+        if named.keys() != conv.keys():
+            binding.order(entry, **named, stream=None)          # TypeError: names every missing and every unknown parameter
+        try:
+            args = [c(named[n]) for n, c in conv.items()]
+        except (HipLibraryError, TypeError, ValueError):
+            for n, c in conv.items():                           # again, one at a time, for the name
+                try:
+                    c(named[n])
+                except (HipLibraryError, TypeError, ValueError) as e:
+                    raise type(e)(f"{entry}, {n}: {e}") from None
+            raise
+        args.insert(made[entry][1], stream_arg(stream))
+        module["call"](entry, *args)
+
+    launch.converters = converters
+    return launch
+
+
+launch = launcher(_BINDING, globals())
+converters = launch.converters
 
 
 @contextlib.contextmanager

@@ -404,15 +404,15 @@ class LoFTR_for_OnePose_Plus(nn.Module):
     def _provided_matches(self, dev, mk0c, mk1c, hw0_i, hw1_i, hw0_c, hw1_c, scale, s0, s1):
         """the fine-only branch (loftr.py:79-115): the caller's coarse keypoints clipped IN PLACE and rounded to cells; no coarse
         transformer, no matching -> ``b_ids`` (zeros), ``i_ids``, ``j_ids``"""
-        call, P = hip.call, hip.ptr
         K = mk0c.shape[0]
         b_ids = torch.zeros(K, dtype=torch.int64, device=dev)
         i_ids, j_ids = torch.empty(K, dtype=torch.int64, device=dev), torch.empty(K, dtype=torch.int64, device=dev)
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         a0, a1 = mk0c.contiguous(), mk1c.contiguous()
-        call("ophip_loftr_coarse_ids", P(a0, None), int(a0.dtype == torch.float64), P(a1, None), int(a1.dtype == torch.float64), K,
-             hw0_i[0], hw0_i[1], hw1_i[0], hw1_i[1], hw0_c[0], hw0_c[1], hw1_c[0], hw1_c[1], float(scale),
-             P(s0), P(s1), P(i_ids, torch.int64), P(j_ids, torch.int64), P(bad, torch.int32), hip.stream_handle())
+        hip.launch("ophip_loftr_coarse_ids", dict(
+            mkpts0=a0, mk0_double=a0.dtype == torch.float64, mkpts1=a1, mk1_double=a1.dtype == torch.float64, K=K, h0i=hw0_i[0], w0i=hw0_i[1],
+            h1i=hw1_i[0], w1i=hw1_i[1], h0c=hw0_c[0], w0c=hw0_c[1], h1c=hw1_c[0], w1c=hw1_c[1], coarse_scale=scale, scale0=s0, scale1=s1,
+            i_ids=i_ids, j_ids=j_ids, bad_count=bad))
         for a, t in ((a0, mk0c), (a1, mk1c)):
             if a.data_ptr() != t.data_ptr():
                 t.copy_(a)
@@ -499,7 +499,6 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         ``fine_concat_coarse_feat`` merges into the windows (``fine_context.merge``, in place) ahead of the fine transformer"""
         b_ids1 = b_ids if b_ids1 is None else b_ids1
         scale_ids = b_ids if scale_ids is None else scale_ids
-        call, P, S = hip.call, hip.ptr, hip.stream_handle()
         dev = ff0.device
         Wf = int(self.config["fine_window_size"])
         WW = Wf * Wf
@@ -509,10 +508,10 @@ class LoFTR_for_OnePose_Plus(nn.Module):
         stride = hw0_f[0] // hw0_c[0]
         f0, f1 = torch.empty(K, WW, 128, device=dev), torch.empty(K, WW, 128, device=dev)
         ff0c, ff1c = ff0.contiguous(), ff1.contiguous()          # [V or 1][hf * wf][128] channels-last
-        call("ophip_fine2_gather_b", P(ff0c), ff0c.stride(0) if ff0c.shape[0] > 1 else 0, P(b_ids, torch.int64), hw0_f[0], hw0_f[1],
-             P(i_ids, torch.int64), K, hw0_c[1], stride, Wf, P(f0), S)
-        call("ophip_fine2_gather_b", P(ff1c), ff1c.stride(0) if ff1c.shape[0] > 1 else 0, P(b_ids1, torch.int64), hw1_f[0], hw1_f[1],
-             P(j_ids, torch.int64), K, hw1_c[1], hw1_f[0] // hw1_c[0], Wf, P(f1), S)
+        hip.launch("ophip_fine2_gather_b", dict(feat_cl=ff0c, feat_bstride=ff0c.stride(0) if ff0c.shape[0] > 1 else 0, b_ids=b_ids, hf=hw0_f[0],
+                                                wf=hw0_f[1], cell_ids=i_ids, K=K, wc=hw0_c[1], stride=stride, W=Wf, out=f0))
+        hip.launch("ophip_fine2_gather_b", dict(feat_cl=ff1c, feat_bstride=ff1c.stride(0) if ff1c.shape[0] > 1 else 0, b_ids=b_ids1, hf=hw1_f[0],
+                                                wf=hw1_f[1], cell_ids=j_ids, K=K, wc=hw1_c[1], stride=hw1_f[0] // hw1_c[0], W=Wf, out=f1))
         if self.fine_context:
             if x0 is None or x1 is None:
                 raise NotImplementedError(FINE_ONLY_WITH_CONTEXT)
@@ -520,10 +519,16 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             if debug:                                  # the windows the fine transformer reads (its layers write new tensors)
                 data["_fine_in0"], data["_fine_in1"] = f0, f1
         T = K * WW
-        attn = "ophip_fine2_full_attention" if self.fine_full else "ophip_fine2_attention"
+
+        def attention(q, k, v, msg):
+            named = dict(q=q, k=k, v=v, K=K, L=WW, S=WW, msg=msg)
+            if self.fine_full:
+                hip.launch("ophip_fine2_full_attention", named)
+            else:
+                hip.launch("ophip_fine2_attention", named)
 
         def fine_layer(x, src, w):
-            return rows_encoder_layer(x, T, src, T, w, lambda q, k, v, msg: call(attn, P(q), P(k), P(v), K, WW, WW, P(msg), S))
+            return rows_encoder_layer(x, T, src, T, w, attention)
         for w, name in zip(Wb["fine"], self.loftr_fine.layer_names):
             if name == "self":
                 f0, f1 = fine_layer(f0, f0, w), fine_layer(f1, f1, w)
@@ -537,11 +542,13 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             s1 = s1 if s1 is not None else torch.ones(1, 2, device=dev)
             mk1c_ = mk1c.contiguous()
             mk1f = torch.empty(K, 2, dtype=mk1c.dtype, device=dev)
-            call("ophip_fine2_match_scaled", P(f0), P(f1), P(mk1c_, None), int(mk1c.dtype == torch.float64), P(scale_ids, torch.int64), P(s1),
-                 2 if s1.shape[0] > 1 else 0, K, Wf, float(h0i / hw0_f[0]), P(expec), P(mk1f, None), S)
+            hip.launch("ophip_fine2_match_scaled", dict(f0=f0, f1=f1, mkpts1_c=mk1c_, mk_double=mk1c.dtype == torch.float64, b_ids=scale_ids,
+                                                        scale1=s1, scale1_bstride=2 if s1.shape[0] > 1 else 0, K=K, W=Wf, scale=h0i / hw0_f[0],
+                                                        expec_f=expec, mkpts1_f=mk1f))
         else:
             mk1f = torch.empty(K, 2, device=dev)
-            call("ophip_fine2_match", P(f0), P(f1), P(mk1c), K, Wf, float((Wf // 2) * (h0i / hw0_f[0])), P(expec), P(mk1f), S)
+            hip.launch("ophip_fine2_match", dict(f0=f0, f1=f1, mkpts1_c=mk1c, K=K, W=Wf, scale=(Wf // 2) * (h0i / hw0_f[0]), expec_f=expec,
+                                                 mkpts1_f=mk1f))
         data.update({"expec_f": expec, "mkpts0_f": mk0c, "mkpts1_f": mk1f})
         if debug:
             data["_fine_f0"], data["_fine_f1"] = f0, f1
@@ -567,7 +574,7 @@ class LoFTR_for_OnePose_Plus(nn.Module):
             jobs.append(hip.SampleJob(fmap.data_ptr(), kp.data_ptr(), sc.data_ptr(), out.data_ptr(), hw[0], hw[1], C, kp.shape[0],
                                       hw_i[0], hw_i[1], int(kp.dtype == torch.float64), nearest))
         arr = (hip.SampleJob * len(jobs))(*jobs)
-        hip.call("ophip_sample_features", arr, len(jobs), hip.stream_handle())
+        hip.launch("ophip_sample_features", dict(jobs=arr, n_jobs=len(jobs)))
         data.update({name: o[0] for name, o in outs.items()})
 
 

@@ -425,7 +425,6 @@ class OnePosePlus_model(nn.Module):
         They depend on nothing but the caller's tensors.  With ``inputs_ready`` the caller states that those are complete (no producer still
         queued on this stream): the kernels then go to a side stream and start at once -- on the CUs the 246-workgroup encoder of the previous
         frame leaves idle and beside its coarse stage -- instead of behind everything queued before; the compute stream waits for their event."""
-        lib_call, P = hip.call, hip.ptr
         B, N, M, hf, wf, dev = fi.B, fi.N, fi.M, fi.hf, fi.wf, fi.dev
         C = feat_c.shape[1]
         f32 = dict(device=dev, dtype=torch.float32)
@@ -433,8 +432,7 @@ class OnePosePlus_model(nn.Module):
         if inputs_ready and self.overlap_fine and not _pe_applied:
             sprep = _side_stream(self._prep_streams, fkey, dev)
             prep_ctx = torch.cuda.stream(sprep)
-        with prep_ctx:
-            S_in = hip.stream_handle()
+        with prep_ctx:                   # the launches below go to the stream that is current in here
             # ---- a1: positional encoding + flatten ------------------------------------------------
             if _pe_applied:          # the HIP backbone wrote [B, M, C] with the encoding added; the encoder may reuse that buffer
                 x2d = feat_c.permute(0, 2, 3, 1).reshape(B, M, C)
@@ -443,7 +441,7 @@ class OnePosePlus_model(nn.Module):
             else:
                 x2d = torch.empty(B, M, C, **f32)
                 pe = self._pe_table(fi.hc, fi.wc, dev) if self._pe_enable else None
-                lib_call("ophip_pe_add_transpose", P(_dense(feat_c)), P(pe), P(x2d), B, C, M, S_in)
+                hip.launch("ophip_pe_add_transpose", dict(feat_nchw=_dense(feat_c), pe_nlc=pe, out_nlc=x2d, B=B, C=C, M=M))
             # ---- fine map to channels-last (input kernel of the fine stage; here so that it runs under the previous frame's
             #      fine stage instead of in front of this frame's) ------------------------------------------------------
             ff = ff_strides = None
@@ -454,7 +452,7 @@ class OnePosePlus_model(nn.Module):
                 else:                                      # NCHW: one streaming transpose, then every window pixel is a 512-byte row
                     ff = ff.contiguous()
                     ff_cl = torch.empty(B, hf * wf, ff.shape[1], **f32)
-                    lib_call("ophip_transpose_cl", P(ff), P(ff_cl), B, ff.shape[1], hf * wf, S_in)
+                    hip.launch("ophip_transpose_cl", dict(in_bcl=ff, out_blc=ff_cl, B=B, C=ff.shape[1], L=hf * wf))
                     ff, ff_strides = ff_cl, (hf * wf * ff_cl.shape[2], 1, wf * ff_cl.shape[2], ff_cl.shape[2])
             # ---- a2 + a3: keypoint encoding (frame-invariant: depends on the object block only) -------------------
             if self.cache_object:
@@ -478,15 +476,15 @@ class OnePosePlus_model(nn.Module):
     def _encode_keypoints(self, fi, Bo):
         """Rows a2 + a3 on the current stream: the object block's keypoint encoding ``[Bo, N, 256]``; ``Bo`` = 1 for one object shared by
         the batch, else B."""
-        lib_call, P, kpts_d, desc_in_d = hip.call, hip.ptr, fi.kpts_d, fi.desc_in_d
+        kpts_d, desc_in_d = fi.kpts_d, fi.desc_in_d
         x3d = torch.empty(Bo, fi.N, 256, device=fi.dev, dtype=torch.float32)
         if self.kpt_3d_pos_encoding is not None:
             stats = torch.empty(4 * Bo + 4, device=fi.dev, dtype=torch.float32)
-            lib_call("ophip_kpt_encode", P(kpts_d), bstride(kpts_d), P(desc_in_d), bstride(desc_in_d), P(fi.W["kpt"]),
-                     P(stats), P(x3d), Bo, fi.N, hip.stream_handle())
+            hip.launch("ophip_kpt_encode", dict(keypoints3d=kpts_d, kpts_bstride=bstride(kpts_d), desc_bcn=desc_in_d,
+                                                desc_bstride=bstride(desc_in_d), wpack=fi.W["kpt"], stats=stats, out_bnc=x3d, B=Bo, N=fi.N))
         else:
             src = desc_in_d if desc_in_d.shape[0] == Bo else desc_in_d.expand(Bo, -1, -1).contiguous()
-            lib_call("ophip_transpose_cl", P(src), P(x3d), Bo, 256, fi.N, hip.stream_handle())
+            hip.launch("ophip_transpose_cl", dict(in_bcl=src, out_blc=x3d, B=Bo, C=256, L=fi.N))
         return x3d
 
     def _coarse_layer_launch(self, fi, S, rows):
@@ -620,27 +618,25 @@ class OnePosePlus_model(nn.Module):
         (transformer.py:133-171 on [K, 1, C] 3D tokens and [K, 25, C] windows; a cross layer's 3D update reads the pre-update windows), then
         FineMatching on the one 3D token per match into ``expec`` and ``cb["mk2d"]``.  Every row count is the capacity: the kernels read the device-side count.  Returns the
         encoder's output rows (windows [cap, 25, 128], 3D tokens [cap, 128])."""
-        lib_call, P, S = hip.call, hip.ptr, hip.stream_handle()
         f32 = dict(device=fi.dev, dtype=torch.float32)
-        desc, cap = fi.desc_fine_d, fi.B * fi.N
-        b_ids, i_ids, j_ids = (P(cb[k], torch.int64) for k in ("b_ids", "i_ids", "j_ids"))
-        cnt = P(cb["count"], torch.int32)
+        desc, cap, cnt = fi.desc_fine_d, fi.B * fi.N, cb["count"]
         WS, WW = 5, 25
         win, f3 = torch.empty(cap, WW, 128, **f32), torch.empty(cap, 128, **f32)
-        lib_call("ophip_fine_full_gather", P(ff), *ff_strides, fi.hf, fi.wf, P(desc), bstride(desc), desc.stride(1), b_ids, i_ids, j_ids,
-                 cnt, cap, fi.wc, stride, WS, P(win), P(f3), S)
+        hip.launch("ophip_fine_full_gather", dict(zip(("fs_b", "fs_c", "fs_y", "fs_x"), ff_strides), feat_f=ff, hf=fi.hf, wf=fi.wf, desc3d_f=desc,
+                                                  d_bs=bstride(desc), d_cs=desc.stride(1), b_ids=cb["b_ids"], i_ids=cb["i_ids"],
+                                                  j_ids=cb["j_ids"], count=cnt, cap=cap, wc=fi.wc, stride=stride, W=WS, windows=win, feat3d=f3))
 
         def layer(x, Lx, src, Ls, w):                     # LoFTREncoderLayer with FullAttention over each match's Lx x Ls tokens
-            return rows_encoder_layer(x, cap * Lx, src, cap * Ls, w, lambda q, k, v, msg: lib_call(
-                "ophip_fine_full_attention", P(q), P(k), P(v), cap, Lx, Ls, cnt, P(msg), S))
+            return rows_encoder_layer(x, cap * Lx, src, cap * Ls, w, lambda q, k, v, msg: hip.launch(
+                "ophip_fine_full_attention", dict(q=q, k=k, v=v, K=cap, L=Lx, S=Ls, count=cnt, msg=msg)))
         if bool(self.config["loftr_fine"]["enable"]):
             for w, name in zip(fi.W["fine_full"], self.loftr_fine.layer_names):
                 if name == "self":
                     win, f3 = layer(win, WW, win, WW, w), layer(f3, 1, f3, 1, w)
                 else:
                     win, f3 = layer(win, WW, f3, 1, w), layer(f3, 1, win, WW, w)
-        lib_call("ophip_fine_full_match", P(f3), P(win), P(cb["mkc"]), b_ids, P(fi.qscale), cnt, cap, WS, float(scale), P(expec),
-                 P(cb["mk2d"]), S)
+        hip.launch("ophip_fine_full_match", dict(feat3d=f3, windows=win, mkpts_c=cb["mkc"], b_ids=cb["b_ids"], query_scale=fi.qscale, count=cnt,
+                                                 cap=cap, W=WS, scale=scale, expec_f=expec, mkpts_f=cb["mk2d"]))
         return win, f3
 
     def _object_cache_entry(self, fi, stream, masked=False, keep=True):

@@ -56,15 +56,16 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
 
 def _pe_add_transpose(feat_nchw, pe_nlc, out_nlc):
     B, C, h, w = feat_nchw.shape
-    hip.call("ophip_pe_add_transpose", hip.ptr(_f32(feat_nchw, "feat_nchw")), hip.ptr(pe_nlc), hip.ptr(_f32(out_nlc, "out_nlc")), B, C, h * w,
-             hip.stream_handle())
+    hip.launch("ophip_pe_add_transpose", dict(feat_nchw=_f32(feat_nchw, "feat_nchw"), pe_nlc=pe_nlc, out_nlc=_f32(out_nlc, "out_nlc"), B=B, C=C,
+                                              M=h * w))
 
 
 def _kpt_encode(keypoints3d, desc_bcn, wpack, out_bnc):
     B, N, _ = keypoints3d.shape
     stats = torch.empty(4 * B + 4, device=keypoints3d.device, dtype=torch.float32)
-    hip.call("ophip_kpt_encode", hip.ptr(_f32(keypoints3d, "keypoints3d")), keypoints3d.stride(0), hip.ptr(_f32(desc_bcn, "desc_bcn")),
-             desc_bcn.stride(0), hip.ptr(wpack), hip.ptr(stats), hip.ptr(_f32(out_bnc, "out_bnc")), B, N, hip.stream_handle())
+    hip.launch("ophip_kpt_encode", dict(keypoints3d=_f32(keypoints3d, "keypoints3d"), kpts_bstride=keypoints3d.stride(0),
+                                        desc_bcn=_f32(desc_bcn, "desc_bcn"), desc_bstride=desc_bcn.stride(0), wpack=wpack, stats=stats,
+                                        out_bnc=_f32(out_bnc, "out_bnc"), B=B, N=N))
 
 
 def _layer_args(x3d, x2d, y3d, y2d, wpack, wpack_next, is_cross, kv_from_prev, slot, workspace):

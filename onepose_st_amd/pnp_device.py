@@ -40,6 +40,7 @@ from . import cabi, devargs, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 (MAX_TRIALS, DEFAULT_TRIALS, MAX_ROWS, MAX_FRAMES, ROW_DOUBLES, SELECT_BLOCK, SCORE_CHUNK, STATUS_NO_POSE, STATUS_NEEDS_MORE, MIN_INLIERS,
@@ -168,10 +169,9 @@ def ransac_pnp(K, pts_2d, pts_3d, *, count=None, b_ids=None, frames=1, scale=1, 
         n_in = torch.zeros(F, dtype=torch.int32, device=dev)
         status = torch.zeros(F, dtype=torch.int32, device=dev)
         mask = torch.zeros(cap, dtype=torch.uint8, device=dev)
-        P = hip.ptr
-        call("oppnpd_solve", P(a.pts_2d), P(a.pts_3d), P(a.count, torch.int32), cap, P(a.b_ids, torch.int64), F, P(a.K, torch.float64), a.k_shared,
-             float(scale), float(pnp_reprojection_error), float(confidence), int(trials), hip.seed_arg(seed), P(ws, None),
-             nbytes, P(pose, torch.float64), P(n_in, torch.int32), P(status, torch.int32), P(mask, torch.uint8), hip.stream_arg(stream))
+        launch("oppnpd_solve", dict(pts2d=a.pts_2d, pts3d=a.pts_3d, count=a.count, cap=cap, b_ids=a.b_ids, F=F, K=a.K, k_shared=a.k_shared,
+                                    scale=scale, reproj_err_px=pnp_reprojection_error, confidence=confidence, trials=trials, seed=seed,
+                                    workspace=ws, workspace_bytes=nbytes, pose=pose, n_inliers=n_in, status=status, inlier_mask=mask), stream)
     ranges = ws[:8 * F].view(torch.int32).view(F, 2)       # the first table of the workspace
     return DevicePoses(pose, n_in, status, mask, ranges, keep=(ws, a))
 
@@ -201,7 +201,7 @@ class stages:
     @staticmethod
     def ranges(b_ids, count, cap, frames, stream=None):
         out = torch.empty(frames, 2, dtype=torch.int32, device=count.device)
-        call("oppnpd_ranges", hip.ptr(b_ids, torch.int64), hip.ptr(count, torch.int32), int(cap), int(frames), hip.ptr(out, torch.int32), hip.stream_arg(stream))
+        launch("oppnpd_ranges", dict(b_ids=b_ids, count=count, cap=cap, F=frames, ranges=out), stream)
         return out
 
     @staticmethod
@@ -209,16 +209,15 @@ class stages:
         K, k_shared = devargs.k_table(K, int(frames), pts_2d.device)
         cap = pts_2d.shape[0]
         rows = torch.zeros(cap, ROW_DOUBLES, dtype=torch.float64, device=pts_2d.device)
-        call("oppnpd_prep", hip.ptr(pts_2d), hip.ptr(pts_3d), hip.ptr(count, torch.int32), cap, hip.ptr(b_ids, torch.int64), int(frames),
-             hip.ptr(K, torch.float64), k_shared, float(scale), hip.ptr(rows, torch.float64), hip.stream_arg(stream))
+        launch("oppnpd_prep", dict(pts2d=pts_2d, pts3d=pts_3d, count=count, cap=cap, b_ids=b_ids, F=frames, K=K, k_shared=k_shared, scale=scale,
+                                   rows=rows), stream)
         return rows
 
     @staticmethod
     def sample(ranges, trials, seed, stream=None):
         F = ranges.shape[0]
         out = torch.empty(F, trials, 3, dtype=torch.int32, device=ranges.device)
-        call("oppnpd_sample", hip.ptr(ranges, torch.int32), F, int(trials), hip.seed_arg(seed), hip.ptr(out, torch.int32),
-             hip.stream_arg(stream))
+        launch("oppnpd_sample", dict(ranges=ranges, F=F, trials=trials, seed=seed, samples=out), stream)
         return out
 
     @staticmethod
@@ -226,8 +225,7 @@ class stages:
         F, trials = samples.shape[0], samples.shape[1]
         hyps = torch.empty(F, 4 * trials, 3, 4, dtype=torch.float64, device=rows.device)
         nsol = torch.empty(F, trials, dtype=torch.int32, device=rows.device)
-        call("oppnpd_p3p", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(samples, torch.int32), rows.shape[0], F, trials,
-             hip.ptr(hyps, torch.float64), hip.ptr(nsol, torch.int32), hip.stream_arg(stream))
+        launch("oppnpd_p3p", dict(rows=rows, ranges=ranges, samples=samples, cap=rows.shape[0], F=F, trials=trials, hyps=hyps, nsol=nsol), stream)
         return hyps, nsol
 
     @staticmethod
@@ -236,8 +234,8 @@ class stages:
         K, k_shared = devargs.k_table(K, F, rows.device)
         cnt = torch.empty(F, H, dtype=torch.int32, device=rows.device)
         cost = torch.empty(F, H, dtype=torch.float64, device=rows.device)
-        call("oppnpd_score", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), k_shared,
-             hip.ptr(hyps, torch.float64), rows.shape[0], F, H, float(reproj), hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.stream_arg(stream))
+        launch("oppnpd_score", dict(rows=rows, ranges=ranges, K=K, k_shared=k_shared, hyps=hyps, cap=rows.shape[0], F=F, H=H, reproj_err_px=reproj,
+                                    cnt=cnt, cost=cost), stream)
         return cnt, cost
 
     @staticmethod
@@ -248,10 +246,9 @@ class stages:
         partial = torch.empty(16 * F * nblk, dtype=torch.uint8, device=dev)
         best, n_in, status = (torch.empty(F, dtype=torch.int32, device=dev) for _ in range(3))
         mask = torch.zeros(rows.shape[0], dtype=torch.uint8, device=dev)
-        call("oppnpd_select", hip.ptr(cnt, torch.int32), hip.ptr(cost, torch.float64), hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32),
-             hip.ptr(count, torch.int32), hip.ptr(K, torch.float64), k_shared, hip.ptr(hyps, torch.float64), rows.shape[0], F, H,
-             float(reproj), float(confidence), int(trials), hip.ptr(partial, None), hip.ptr(best, torch.int32), hip.ptr(n_in, torch.int32),
-             hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
+        launch("oppnpd_select", dict(cnt=cnt, cost=cost, rows=rows, ranges=ranges, count=count, K=K, k_shared=k_shared, hyps=hyps, cap=rows.shape[0],
+                                     F=F, H=H, reproj_err_px=reproj, confidence=confidence, trials=trials, partial=partial, best=best,
+                                     n_inliers=n_in, status=status, inlier_mask=mask), stream)
         return best, n_in, status, mask
 
     @staticmethod
@@ -260,7 +257,6 @@ class stages:
         F, H = hyps.shape[0], hyps.shape[1]
         K, k_shared = devargs.k_table(K, F, rows.device)
         pose = torch.empty(F, 3, 4, dtype=torch.float64, device=rows.device)
-        call("oppnpd_refine", hip.ptr(rows, torch.float64), hip.ptr(ranges, torch.int32), hip.ptr(K, torch.float64), k_shared,
-             hip.ptr(hyps, torch.float64), hip.ptr(best, torch.int32), rows.shape[0], F, H, float(reproj), float(scale), hip.ptr(pose, torch.float64),
-             hip.ptr(n_inliers, torch.int32), hip.ptr(status, torch.int32), hip.ptr(mask, torch.uint8), hip.stream_arg(stream))
+        launch("oppnpd_refine", dict(rows=rows, ranges=ranges, K=K, k_shared=k_shared, hyps=hyps, best=best, cap=rows.shape[0], F=F, H=H,
+                                     reproj_err_px=reproj, scale=scale, pose=pose, n_inliers=n_inliers, status=status, inlier_mask=mask), stream)
         return pose

@@ -20,6 +20,7 @@ from . import cabi, devargs, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 MAX_FRAMES, MAX_VERTICES, BLOCK, MAX_PAIRS_PER_LAUNCH, NO_POSE, BAD_INPUT = map(_BINDING.constant, (
@@ -183,27 +184,26 @@ def pose_errors(poses, pose_gt, *, status=None, unit="m", model_points=None, K=N
         K, k_shared = devargs.k_table(K, F, dev, exact=True)
     if pair_budget is not None and (int(pair_budget) != pair_budget or not 1 <= pair_budget <= MAX_PAIRS_PER_LAUNCH):
         raise ValueError(f"pair_budget: an integer in [1, {MAX_PAIRS_PER_LAUNCH}]")
-    P, S = hip.ptr, hip.stream_arg(stream)
     with hip.enqueue_on(dev, stream):
         rot_cos, t_err = (torch.empty(F, dtype=torch.float64, device=dev) for _ in range(2))
         flags = torch.empty(F, dtype=torch.int32, device=dev)
-        call("opevl_errors", P(pred, torch.float64), pred_stride, P(gt, torch.float64), gt_stride, P(status, torch.int32),
-             pnp_device.STATUS_NO_POSE, F, UNIT_SCALE[unit], P(rot_cos, torch.float64), P(t_err, torch.float64), P(flags, torch.int32), S)
+        launch("opevl_errors", dict(pose_pred=pred, pred_stride=pred_stride, pose_gt=gt, gt_stride=gt_stride, status=status,
+                                    status_mask=pnp_device.STATUS_NO_POSE, frames=F, unit_scale=UNIT_SCALE[unit], rot_cos=rot_cos, t_err=t_err,
+                                    flags=flags), stream)
         add_dist = proj2d = partials = None
         if verts is not None:
             V = int(verts.shape[0])
-            tables = (P(verts), V, P(pred, torch.float64), pred_stride, P(gt, torch.float64), gt_stride)
             partials = torch.empty(F * ((V + BLOCK - 1) // BLOCK), dtype=torch.float64, device=dev)     # used by one launch after the other
             add_dist = torch.empty(F, dtype=torch.float64, device=dev)
+            tables = dict(verts=verts, V=V, pose_pred=pred, pred_stride=pred_stride, pose_gt=gt, gt_stride=gt_stride, flags=flags, frames=F,
+                          partials=partials)
             if symmetric:
-                call("opevl_adds", *tables, P(flags, torch.int32), F, 0 if pair_budget is None else int(pair_budget),
-                     P(partials, torch.float64), P(add_dist, torch.float64), S)
+                launch("opevl_adds", dict(tables, pair_budget=0 if pair_budget is None else pair_budget, adds_dist=add_dist), stream)
             else:
-                call("opevl_add", *tables, P(flags, torch.int32), F, P(partials, torch.float64), P(add_dist, torch.float64), S)
+                launch("opevl_add", dict(tables, add_dist=add_dist), stream)
             if K is not None:
                 proj2d = torch.empty(F, dtype=torch.float64, device=dev)
-                call("opevl_proj2d", *tables, P(K, torch.float64), k_shared, P(flags, torch.int32), F, P(partials, torch.float64),
-                     P(proj2d, torch.float64), S)
+                launch("opevl_proj2d", dict(tables, K=K, k_shared=k_shared, proj2d=proj2d), stream)
     return DevicePoseErrors(rot_cos, t_err, add_dist, proj2d, flags, symmetric=bool(symmetric),
                             keep=(pred, gt, status, verts, K, partials))
 

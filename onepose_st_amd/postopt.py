@@ -14,7 +14,6 @@ caller; the triangulation is ``sfm_triangulate``'s.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import warnings
 
@@ -156,11 +155,10 @@ def refine_depths(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: torch.
     resid = torch.empty(L, 2, dtype=torch.float64, device=d.device) if return_residuals else None
     ws_bytes = hip.load().ophip_postopt_workspace_bytes(L, P, max_steps)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d.device)
-    p = hip.ptr
-    hip.call("ophip_postopt_refine", p(d, torch.float64), p(offs, torch.int64), P, L, p(K0, torch.float64), p(K1, torch.float64),
-             p(mk0, torch.float64), p(mk1, torch.float64), p(li, torch.int64), p(ri, torch.int64), p(aa, torch.float64), F,
-             p(table, torch.float64), max_steps, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, p(loss, torch.float64), p(steps, torch.int32),
-             p(resid, torch.float64), p(ws, None), ctypes.c_size_t(ws_bytes), hip.stream_handle())
+    hip.launch("ophip_postopt_refine", dict(depth=d, track_offsets=offs, P=P, L=L, intrinsic0=K0, intrinsic1=K1, mkpts0_c=mk0, mkpts1_f=mk1,
+                                            left_idx=li, right_idx=ri, angle_axis=aa, F=F, step_table=table, max_steps=max_steps,
+                                            beta1=ADAM_BETAS[0], beta2=ADAM_BETAS[1], eps=ADAM_EPS, loss=loss, steps_run=steps, residuals=resid,
+                                            workspace=ws, workspace_bytes=ws_bytes))
     n = int(steps.item())                       # the one read-back: depths, loss[] and the step count follow the same stream
     hist = loss[:n]
     lh = hist.tolist()
@@ -199,13 +197,12 @@ def refine_depths_lm(depth: torch.Tensor, n_query: torch.Tensor, intrinsic0: tor
     resid = torch.empty(L, 2, dtype=torch.float64, device=dev) if return_residuals else None
     ws_bytes = postopt_lm.load().oplm_workspace_bytes(L, P)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    p = hip.ptr
-    postopt_lm.call("oplm_refine", p(d, torch.float64), p(offs, torch.int64), P, L, p(K0, torch.float64), p(K1, torch.float64),
-                    p(mk0, torch.float64), p(mk1, torch.float64), p(li, torch.int64), p(ri, torch.int64), p(aa, torch.float64), F,
-                    float(lam0), float(up), float(down), float(lam_min), float(lam_max), float(step_tol), max_iters,
-                    p(ints[0], torch.int32), p(ints[1], torch.int32), p(ints[2], torch.int32), p(reals[0], torch.float64),
-                    p(reals[1], torch.float64), p(reals[2], torch.float64), p(totals[0:1], torch.float64), p(totals[1:2], torch.float64),
-                    p(resid, torch.float64), p(ws, None), ctypes.c_size_t(ws_bytes), hip.stream_handle())
+    postopt_lm.launch("oplm_refine", {
+        "depth": d, "track_offsets": offs, "P": P, "L": L, "intrinsic0": K0, "intrinsic1": K1, "mkpts0_c": mk0, "mkpts1_f": mk1, "left_idx": li,
+        "right_idx": ri, "angle_axis": aa, "F": F, "lam0": lam0, "up": up, "down": down, "lam_min": lam_min, "lam_max": lam_max,
+        "step_tol": step_tol, "max_iters": max_iters, "iterations": ints[0], "rejects": ints[1], "status": ints[2], "lambda": reals[0],
+        "initial_cost": reals[1], "final_cost": reals[2], "initial_residual": totals[0:1], "final_residual": totals[1:2], "residuals": resid,
+        "workspace": ws, "workspace_bytes": ws_bytes})                    # a dict display: ``lambda`` is no keyword argument
     # the one read-back: both totals and the largest iteration count follow the solve on the same stream
     initial, final, steps = torch.cat([totals, ints[0].max().to(torch.float64)[None]]).tolist()
     out = {"depth": d.reshape(P, 1), "iterations": ints[0], "rejects": ints[1], "status": ints[2], "lambda": reals[0],
@@ -236,9 +233,7 @@ def points_from_depth(keypoints: torch.Tensor, depth: torch.Tensor, frame_idx: t
     K, R, t = _frames(K, R, t)
     fi = _dev_index(frame_idx, "frame_idx", N, K.shape[0])
     out = torch.empty(N, 3, dtype=torch.float64, device=kp.device)
-    p = hip.ptr
-    hip.call("ophip_postopt_points_from_depth", p(kp, torch.float64), p(dd, torch.float64), p(fi, torch.int64), N, p(K, torch.float64),
-             p(R, torch.float64), p(t, torch.float64), K.shape[0], p(out, torch.float64), hip.stream_handle())
+    hip.launch("ophip_postopt_points_from_depth", dict(keypoints=kp, depth=dd, frame_idx=fi, N=N, K=K, R=R, t=t, F=K.shape[0], points=out))
     return out
 
 
@@ -250,9 +245,7 @@ def project_points(points: torch.Tensor, frame_idx: torch.Tensor, K: torch.Tenso
     K, R, t = _frames(K, R, t)
     fi = _dev_index(frame_idx, "frame_idx", N, K.shape[0])
     out = torch.empty(N, 2, dtype=torch.float64, device=X.device)
-    p = hip.ptr
-    hip.call("ophip_postopt_project_points", p(X, torch.float64), p(fi, torch.int64), N, p(K, torch.float64), p(R, torch.float64),
-             p(t, torch.float64), K.shape[0], p(out, torch.float64), hip.stream_handle())
+    hip.launch("ophip_postopt_project_points", dict(points=X, frame_idx=fi, N=N, K=K, R=R, t=t, F=K.shape[0], keypoints=out))
     return out
 
 

@@ -97,21 +97,20 @@ def merge_pair_matches(mkpts0: torch.Tensor, mkpts1: torch.Tensor, mconf: torch.
 
     lib = hip.load()
     dev = mconf.device
-    S, Pt = hip.stream_handle(), hip.ptr
     nbytes = lib.ophip_sfm_points2d_workspace_bytes(T, I)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     ucount = torch.zeros(1, dtype=torch.int32, device=dev)
     mk0, mk1, mc = mkpts0.contiguous(), mkpts1.contiguous(), mconf.contiguous()
     po, pi = pair_offsets.contiguous(), pair_images.contiguous()
-    hip.call("ophip_sfm_points2d_group", Pt(mk0), Pt(mk1), Pt(po, torch.int64), Pt(pi, torch.int64), P, T, I, Pt(ws, None), nbytes,
-             Pt(ucount, torch.int32), S)
+    hip.launch("ophip_sfm_points2d_group", dict(mkpts0=mk0, mkpts1=mk1, pair_offsets=po, pair_images=pi, P=P, T=T, I=I, workspace=ws,
+                                                workspace_bytes=nbytes, unique_count=ucount))
     U = int(ucount.item())                                     # the one read-back: it sizes the outputs
     keypoints = torch.empty(U, 2, dtype=torch.float32, device=dev)
     scores = torch.empty(U, dtype=torch.float32, device=dev)
     kpt_offsets = torch.empty(I + 1, dtype=torch.int64, device=dev)
     match_ids = torch.empty(T, 2, dtype=torch.int64, device=dev)
-    hip.call("ophip_sfm_points2d_rank", Pt(mc), T, I, U, Pt(ws, None), nbytes, Pt(keypoints), Pt(scores), Pt(kpt_offsets, torch.int64),
-             Pt(match_ids, torch.int64), S)
+    hip.launch("ophip_sfm_points2d_rank", dict(mconf=mc, T=T, I=I, U=U, workspace=ws, workspace_bytes=nbytes, keypoints=keypoints, scores=scores,
+                                               kpt_offsets=kpt_offsets, match_ids=match_ids))
     return {"keypoints": keypoints, "scores": scores, "kpt_offsets": kpt_offsets, "match_ids": match_ids, "pair_offsets": pair_offsets}
 
 

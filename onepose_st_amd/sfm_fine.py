@@ -44,6 +44,7 @@ from .backbone_hip import HipBackbone
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 MAX_ROWS, CTRL_INTS, NO_ROW = map(_BINDING.constant, ("MAX_ROWS", "CTRL_INTS", "NO_ROW"))
@@ -202,14 +203,14 @@ def _raise_for_image_index(pairs, n_images):
 def row_ids(bank: dict, mkpts0_c, mkpts1_c, row_left, row_right) -> tuple:
     """``opsff_row_ids`` on contiguous device tensors -> ``(mkpts0_c clipped, mkpts1_c clipped, i_ids, j_ids, ctrl [2] int32)``;
     nothing is read back"""
-    P, i64 = hip.ptr, torch.int64
     M, dev = mkpts0_c.shape[0], mkpts0_c.device
     out0, out1 = torch.empty_like(mkpts0_c), torch.empty_like(mkpts1_c)
-    i_ids, j_ids = torch.empty(M, dtype=i64, device=dev), torch.empty(M, dtype=i64, device=dev)
+    i_ids, j_ids = torch.empty(M, dtype=torch.int64, device=dev), torch.empty(M, dtype=torch.int64, device=dev)
     ctrl = torch.empty(CTRL_INTS, dtype=torch.int32, device=dev)
-    call("opsff_row_ids", P(mkpts0_c, None), int(mkpts0_c.dtype == torch.float64), P(mkpts1_c, None), int(mkpts1_c.dtype == torch.float64),
-         P(row_left, i64), P(row_right, i64), P(bank["image_hw"], torch.int32), P(bank["scales"]), bank["n_images"], M, COARSE_SCALE,
-         P(out0, None), P(out1, None), P(i_ids, i64), P(j_ids, i64), P(ctrl, torch.int32), hip.stream_handle())
+    launch("opsff_row_ids", dict(mkpts0=mkpts0_c, mk0_double=mkpts0_c.dtype == torch.float64, mkpts1=mkpts1_c,
+                                 mk1_double=mkpts1_c.dtype == torch.float64, row_left=row_left, row_right=row_right, image_hw=bank["image_hw"],
+                                 image_scale=bank["scales"], I=bank["n_images"], M=M, coarse_scale=COARSE_SCALE, mkpts0_out=out0, mkpts1_out=out1,
+                                 i_ids=i_ids, j_ids=j_ids, ctrl=ctrl))
     return out0, out1, i_ids, j_ids, ctrl
 
 
@@ -217,13 +218,15 @@ def sample_rows(bank: dict, g0: int, g1: int, mkpts0, mkpts1, row_left, row_righ
                 feature0, feature1) -> None:
     """``opsff_sample_rows``: the four feature tables of the rows ``rows`` (a device int64 tensor, or ``None``: ``row0 .. row0 + n``),
     whose left images lie in size group ``g0`` and right images in ``g1``, written at those rows of the ``[M, C]`` outputs"""
-    P, i64 = hip.ptr, torch.int64
     G0, G1 = bank["groups"][g0], bank["groups"][g1]
-    call("opsff_sample_rows", P(G0["coarse"]), G0["coarse"].stride(0), P(G0["fine"]), G0["fine"].stride(0), G0["fine"].shape[0], *G0["hw"],
-         P(G1["coarse"]), G1["coarse"].stride(0), P(G1["fine"]), G1["fine"].stride(0), G1["fine"].shape[0], *G1["hw"],
-         P(mkpts0, None), int(mkpts0.dtype == torch.float64), P(mkpts1, None), int(mkpts1.dtype == torch.float64), P(row_left, i64),
-         P(row_right, i64), P(bank["image_index"], i64), P(bank["scales"]), bank["n_images"], P(rows, i64), row0, n, mkpts0.shape[0],
-         P(feature_c0), P(feature_c1), P(feature0), P(feature1), hip.stream_handle())
+    launch("opsff_sample_rows", dict(coarse0=G0["coarse"], coarse0_bstride=G0["coarse"].stride(0), fine0=G0["fine"],
+                                     fine0_bstride=G0["fine"].stride(0), n_group0=G0["fine"].shape[0], H0=G0["hw"][0], W0=G0["hw"][1],
+                                     coarse1=G1["coarse"], coarse1_bstride=G1["coarse"].stride(0), fine1=G1["fine"],
+                                     fine1_bstride=G1["fine"].stride(0), n_group1=G1["fine"].shape[0], H1=G1["hw"][0], W1=G1["hw"][1],
+                                     mkpts0=mkpts0, mk0_double=mkpts0.dtype == torch.float64, mkpts1=mkpts1,
+                                     mk1_double=mkpts1.dtype == torch.float64, row_left=row_left, row_right=row_right,
+                                     image_index=bank["image_index"], image_scale=bank["scales"], I=bank["n_images"], rows=rows, row0=row0, n=n,
+                                     M=mkpts0.shape[0], feature_c0=feature_c0, feature_c1=feature_c1, feature0=feature0, feature1=feature1))
 
 
 @torch.no_grad()

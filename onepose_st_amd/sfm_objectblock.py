@@ -55,6 +55,7 @@ from . import cabi, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 MAX_ITEMS, PAIR_TILE, PAIR_MAX_CHUNKS = map(_BINDING.constant, ("MAX_ITEMS", "PAIR_TILE", "PAIR_MAX_CHUNKS"))
@@ -133,16 +134,13 @@ def aggregate_track_features(assigned_image, assigned_kpt, row_offsets, ref_imag
         hip.need_device(tuple(zip(names, args)))
     P, R, I, U = check_track_inputs(*args, keypoints_update_method=keypoints_update_method, aggregation_method=aggregation_method)
     dev = feature_c0.device
-    Pt, i64 = hip.ptr, torch.int64
     ws, nbytes = _workspace(U, 0, dev)
     desc_c = torch.empty(U, DIM_COARSE, dtype=torch.float32, device=dev)
     desc_f = torch.empty(U, DIM_FINE, dtype=torch.float32, device=dev)
     written = torch.empty(U, dtype=torch.uint8, device=dev)
     cleared = torch.empty(U, dtype=torch.uint8, device=dev)
-    c = [t.contiguous() for t in args]
-    call("opsfm_aggregate", Pt(c[0], i64), Pt(c[1], i64), Pt(c[2], i64), Pt(c[3], i64), Pt(c[4], i64), Pt(c[5]), Pt(c[6]), Pt(c[7]), Pt(c[8]),
-         Pt(c[9], i64), P, R, I, U, DIM_COARSE, DIM_FINE, Pt(ws, None), nbytes, Pt(desc_c), Pt(desc_f), Pt(written, torch.uint8),
-         Pt(cleared, torch.uint8), hip.stream_handle())
+    launch("opsfm_aggregate", dict(zip(names, (t.contiguous() for t in args)), P=P, R=R, I=I, U=U, dim_c=DIM_COARSE, dim_f=DIM_FINE, workspace=ws,
+                                   workspace_bytes=nbytes, desc_coarse=desc_c, desc_fine=desc_f, written=written, scores_cleared=cleared))
     return {"desc_coarse": desc_c, "desc_fine": desc_f, "written": written.bool(), "scores_cleared": cleared.bool(), "kpt_offsets": kpt_offsets}
 
 
@@ -194,14 +192,14 @@ def select_points(point_ids, xyz, track_len, bbox_corners=None, max_num_kp3d: in
     hip.need_device(named)
     Q = check_point_inputs(point_ids, xyz, track_len, bbox_corners, max_num_kp3d, dist_threshold)
     dev = xyz.device
-    Pt, S, i64, u8 = hip.ptr, hip.stream_handle(), torch.int64, torch.uint8
+    i64, u8 = torch.int64, torch.uint8
     xyz = xyz.contiguous()
     # 1. the box
     if bbox_corners is None:
         idx = torch.arange(Q, device=dev)
     else:
         keep = torch.empty(Q, dtype=u8, device=dev)
-        call("opsfm_box_test", Pt(xyz, torch.float64), Q, Pt(bbox_corners.contiguous(), torch.float64), Pt(keep, u8), S)
+        launch("opsfm_box_test", dict(xyz=xyz, Q=Q, corners=bbox_corners.contiguous(), keep=keep))
         idx = torch.nonzero(keep).squeeze(1)
     Q1 = idx.numel()
     if Q1 == 0:
@@ -219,28 +217,29 @@ def select_points(point_ids, xyz, track_len, bbox_corners=None, max_num_kp3d: in
     # 4. the merge
     chunk_len, C = pair_chunks(N0)
     counts = torch.empty(N0 * C, dtype=i64, device=dev)
-    call("opsfm_pair_count", Pt(pts, torch.float64), N0, float(dist_threshold), chunk_len, C, Pt(counts, i64), S)
+    launch("opsfm_pair_count", dict(xyz=pts, N=N0, dist_threshold=dist_threshold, chunk_len=chunk_len, n_chunks=C, counts=counts))
     positions = torch.cat([torch.zeros(1, dtype=i64, device=dev), torch.cumsum(counts, 0)])
     E = int(positions[-1])                                                 # read-back: sizes the sparse lists
     if E > MAX_ITEMS:
         raise ValueError(f"{E} close pairs: at most {MAX_ITEMS}")
     nbr = torch.empty(E, dtype=torch.int32, device=dev)
-    call("opsfm_pair_emit", Pt(pts, torch.float64), N0, float(dist_threshold), chunk_len, C, Pt(positions, i64), Pt(nbr, torch.int32), E, S)
+    launch("opsfm_pair_emit", dict(xyz=pts, N=N0, dist_threshold=dist_threshold, chunk_len=chunk_len, n_chunks=C, positions=positions,
+                                   neighbours=nbr, E=E))
     rows = positions[::C]                                                  # [N0 + 1]: point j owns nbr[rows[j] : rows[j + 1]]
     deg = rows[1:] - rows[:-1]
     accepted = (deg == 1).to(u8)                                           # alone: by symmetry nobody can have recorded it
     multi = torch.nonzero(deg > 1).squeeze(1)
     ws, nbytes = _workspace(0, N0, dev)
-    call("opsfm_merge_resolve", Pt(positions, i64), C, Pt(nbr, torch.int32), Pt(multi, i64), multi.numel(), N0, Pt(ws, None), nbytes,
-         Pt(accepted, u8), S)
+    launch("opsfm_merge_resolve", dict(positions=positions, n_chunks=C, neighbours=nbr, multi=multi, M=multi.numel(), N=N0, workspace=ws,
+                                       workspace_bytes=nbytes, accepted=accepted))
     acc = torch.nonzero(accepted).squeeze(1)
     N = acc.numel()
     goff = torch.cat([torch.zeros(1, dtype=i64, device=dev), torch.cumsum(deg[acc], 0)])
     total = int(goff[-1])
     kp3d = torch.empty(N, 3, dtype=torch.float64, device=dev)
     members = torch.empty(total, dtype=i64, device=dev)
-    call("opsfm_group_emit", Pt(pts, torch.float64), Pt(ids, i64), Pt(acc, i64), Pt(positions, i64), C, Pt(nbr, torch.int32), Pt(goff, i64), N,
-         N0, Pt(kp3d, torch.float64), Pt(members, i64), total, S)
+    launch("opsfm_group_emit", dict(xyz=pts, ids=ids, accepted_idx=acc, positions=positions, n_chunks=C, neighbours=nbr, group_offsets=goff, G=N,
+                                    N=N0, keypoints3d=kp3d, group_members=members, members_total=total))
     return {"keypoints3d": kp3d, "group_offsets": goff, "group_members": members, "track_length": track_length,
             "counts": {"input": Q, "after_bbox": Q1, "after_track_length": N0, "after_merge": N, "close_entries": E}}
 
@@ -283,8 +282,7 @@ def point_means(table, obs, runs) -> torch.Tensor:
         raise ValueError(f"table: expected float32 [U, dim], got {table.dtype} {list(table.shape)}")
     N, (U, dim) = runs.numel() - 1, table.shape
     out = torch.empty(N, dim, dtype=torch.float64, device=table.device)
-    call("opsfm_point_mean", hip.ptr(table.contiguous()), U, dim, hip.ptr(obs, torch.int64), hip.ptr(runs, torch.int64), N,
-         hip.ptr(out, torch.float64), hip.stream_handle())
+    launch("opsfm_point_mean", dict(table=table.contiguous(), U=U, dim=dim, obs=obs, run_offsets=runs, G=N, out=out))
     return out
 
 

@@ -67,6 +67,7 @@ from . import cabi, hip, postopt
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 MAX_IMAGES, MAX_ITEMS, CTRL_INTS = map(_BINDING.constant, ("MAX_IMAGES", "MAX_ITEMS", "CTRL_INTS"))
@@ -168,7 +169,7 @@ def assign_tracks(model: dict, feature_track_assignment_strategy: str = "greedy"
     d = check_model(model, feature_track_assignment_strategy)
     I, U, Q, E = d["I"], d["U"], d["Q"], d["E"]
     dev = model["xys"].device
-    Pt, S, i32, i64, f64 = hip.ptr, hip.stream_handle(), torch.int32, torch.int64, torch.float64
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
     c = {k: model[k].contiguous() for k in MODEL_KEYS}
     registered = d["slot_point"] >= 0
     state = torch.where(registered, -2, -1).to(i32)
@@ -178,13 +179,13 @@ def assign_tracks(model: dict, feature_track_assignment_strategy: str = "greedy"
     assigned_kpt = torch.full((Q,), -1, dtype=i32, device=dev)
     keyframes = torch.full((I,), -1, dtype=i32, device=dev)
     ctrl = torch.tensor([0, I, 0, -1], dtype=i32, device=dev)
-    call("opsft_assign", Pt(c["kpt_offsets"], i64), Pt(d["slot_point"], i64), Pt(c["track_offsets"], i64), Pt(c["track_image"], i64),
-         Pt(d["elem_slot"], i64), I, U, Q, E, d["max_slots"], Pt(state, i32), Pt(count, i32), Pt(order, i32), Pt(assigned_image, i32),
-         Pt(assigned_kpt, i32), Pt(keyframes, i32), Pt(ctrl, i32), S)
+    launch("opsft_assign", dict(kpt_offsets=c["kpt_offsets"], slot_point=d["slot_point"], track_offsets=c["track_offsets"],
+                                elem_image=c["track_image"], elem_slot=d["elem_slot"], I=I, U=U, Q=Q, E=E, max_slots=d["max_slots"], state=state,
+                                count=count, order=order, assigned_image=assigned_image, assigned_kpt=assigned_kpt, keyframes=keyframes, ctrl=ctrl))
     state_ids = torch.empty(U, dtype=i64, device=dev)
     depth = torch.empty(U, dtype=f64, device=dev)
-    call("opsft_finish", Pt(state, i32), Pt(d["slot_image"], i64), Pt(c["point_ids"], i64), Pt(c["xyz"], f64), Pt(c["K"], f64),
-         Pt(c["R"], f64), Pt(c["t"], f64), I, U, Q, Pt(state_ids, i64), Pt(depth, f64), S)
+    launch("opsft_finish", dict(state=state, slot_image=d["slot_image"], point_ids=c["point_ids"], xyz=c["xyz"], K=c["K"], R=c["R"], t=c["t"], I=I,
+                                U=U, Q=Q, state_ids=state_ids, initial_depth=depth))
     done, _, n_kf, _ = ctrl.tolist()                                       # the read-back after the rounds
     if not done or bool((assigned_image < 0).any()):
         raise RuntimeError("the greedy rounds ended with unassigned points")
@@ -206,13 +207,13 @@ def _track_rows(plan: dict, model: dict) -> dict:
     d = plan["_tables"]
     Q, E = d["Q"], d["E"]
     dev = model["xys"].device
-    Pt, i64 = hip.ptr, torch.int64
+    i64 = torch.int64
     other = torch.empty(E, dtype=torch.uint8, device=dev)
     match_kpt = torch.empty(E, dtype=i64, device=dev)
     ref_kpt = torch.empty(E, dtype=i64, device=dev)
-    call("opsft_track_rows", Pt(model["track_offsets"].contiguous(), i64), Pt(d["elem_point"], i64), Pt(model["track_image"].contiguous(), i64),
-         Pt(model["track_kpt"].contiguous(), i64), Pt(plan["_assigned_image"], torch.int32), Q, E, Pt(other, torch.uint8), Pt(match_kpt, i64),
-         Pt(ref_kpt, i64), hip.stream_handle())
+    launch("opsft_track_rows", dict(track_offsets=model["track_offsets"].contiguous(), elem_point=d["elem_point"],
+                                    elem_image=model["track_image"].contiguous(), track_kpt=model["track_kpt"].contiguous(),
+                                    assigned_image=plan["_assigned_image"], Q=Q, E=E, other=other, match_kpt=match_kpt, ref_kpt=ref_kpt))
     rows_e = torch.nonzero(other).squeeze(1)
     n_query = torch.bincount(d["elem_point"][rows_e], minlength=Q)
     plan["_rows"] = {"rows_e": rows_e, "n_query": n_query, "row_offsets": hip.exclusive(n_query), "match_kpt": match_kpt, "ref_kpt": ref_kpt}
@@ -226,7 +227,7 @@ def matching_pairs(plan: dict, model: dict) -> dict:
     d = plan["_tables"]
     I, U, E = d["I"], d["U"], d["E"]
     dev = model["xys"].device
-    Pt, S, i64, f64 = hip.ptr, hip.stream_handle(), torch.int64, torch.float64
+    i64, f64 = torch.int64, torch.float64
     owned = torch.nonzero(plan["_state"] >= 0).squeeze(1)                  # ascending slot = image, then keypoint index
     point_of = plan["_state"][owned].to(i64)
     per_slot = tr["n_query"][point_of]
@@ -243,15 +244,14 @@ def matching_pairs(plan: dict, model: dict) -> dict:
     id_rank[torch.argsort(model["image_ids"])] = torch.arange(I, device=dev)
     ko, ti = model["kpt_offsets"].contiguous(), model["track_image"].contiguous()
     keys = torch.empty(M, dtype=i64, device=dev)
-    call("opsft_pair_keys", Pt(owner_slot, i64), Pt(row_elem, i64), Pt(d["slot_image"], i64), Pt(ko, i64), Pt(ti, i64), Pt(id_rank, i64), I, U, E,
-         M, d["max_slots"], Pt(keys, i64), S)
+    launch("opsft_pair_keys", dict(owner_slot=owner_slot, row_elem=row_elem, slot_image=d["slot_image"], kpt_offsets=ko, elem_image=ti,
+                                   id_rank=id_rank, I=I, U=U, E=E, M=M, key_stride=d["max_slots"], keys=keys))
     sorted_keys, perm = torch.sort(keys)                                   # the keys are distinct: (left, right, left keypoint)
     out = {"mkpts0_c": torch.empty(M, 2, dtype=f64, device=dev), "mkpts1_c": torch.empty(M, 2, dtype=f64, device=dev),
            "mkpts0_idx": torch.empty(M, dtype=i64, device=dev), "row_left": torch.empty(M, dtype=i64, device=dev),
            "row_right": torch.empty(M, dtype=i64, device=dev)}
-    call("opsft_pair_emit", Pt(perm, i64), Pt(owner_slot, i64), Pt(row_elem, i64), Pt(d["slot_image"], i64), Pt(ko, i64), Pt(ti, i64),
-         Pt(tr["match_kpt"], i64), Pt(model["xys"].contiguous(), f64), I, U, E, M, Pt(out["mkpts0_c"], f64), Pt(out["mkpts1_c"], f64),
-         Pt(out["mkpts0_idx"], i64), Pt(out["row_left"], i64), Pt(out["row_right"], i64), S)
+    launch("opsft_pair_emit", dict(perm=perm, owner_slot=owner_slot, row_elem=row_elem, slot_image=d["slot_image"], kpt_offsets=ko, elem_image=ti,
+                                   match_kpt=tr["match_kpt"], xys=model["xys"].contiguous(), I=I, U=U, E=E, M=M, **out))
     _, per_pair = torch.unique_consecutive(torch.div(sorted_keys, d["max_slots"], rounding_mode="floor"), return_counts=True)
     offsets = hip.exclusive(per_pair)
     out.update(pair_offsets=offsets, pair_left=out["row_left"][offsets[:-1]], pair_right=out["row_right"][offsets[:-1]])
@@ -281,7 +281,7 @@ def optimisation_rows(plan: dict, model: dict, pairs: dict) -> dict:
     d = plan["_tables"]
     I, Q = d["I"], d["Q"]
     dev = model["xys"].device
-    Pt, i64, i32 = hip.ptr, torch.int64, torch.int32
+    i64, i32 = torch.int64, torch.int32
     rows_e = tr["rows_e"]
     R = rows_e.numel()
     if bool((tr["n_query"] == 0).any()):
@@ -297,10 +297,11 @@ def optimisation_rows(plan: dict, model: dict, pairs: dict) -> dict:
     ref_kpt = tr["ref_kpt"][rows_e].contiguous()
     fine_row = torch.empty(R, dtype=i64, device=dev)
     err = torch.zeros(1, dtype=i32, device=dev)
-    call("opsft_fine_rows", Pt(row_point, i64), Pt(ref_image, i64), Pt(plan["_assigned_image"], i32), Pt(plan["_assigned_kpt"], i32),
-         Pt(model["image_ids"].contiguous(), i64), Pt(pairs["pair_left"].contiguous(), i64), Pt(pairs["pair_right"].contiguous(), i64),
-         Pt(pairs["pair_offsets"].contiguous(), i64), Pt(pairs["mkpts0_idx"].contiguous(), i64), I, Q, R, Np, M, Pt(fine_row, i64),
-         Pt(err, i32), hip.stream_handle())
+    launch("opsft_fine_rows", dict(row_point=row_point, ref_image=ref_image, assigned_image=plan["_assigned_image"],
+                                   assigned_kpt=plan["_assigned_kpt"], image_ids=model["image_ids"].contiguous(),
+                                   pair_left=pairs["pair_left"].contiguous(), pair_right=pairs["pair_right"].contiguous(),
+                                   pair_offsets=pairs["pair_offsets"].contiguous(), mkpts0_idx=pairs["mkpts0_idx"].contiguous(), I=I, Q=Q, R=R,
+                                   Np=Np, M=M, fine_row=fine_row, error_flag=err))
     if int(err.item()):
         j = int(torch.nonzero(fine_row < 0)[0, 0])
         raise ValueError(f"row {j} (point {int(row_point[j])}, image {int(ref_image[j])}): the pair list does not hold exactly one row "

@@ -55,6 +55,7 @@ from . import cabi, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 MAX_ITEMS, SHORT_TRACK, MAX_HYPOTHESES, MAX_REFINE_STEPS, MAX_ROUNDS, CAMERA_DOUBLES = map(_BINDING.constant, (
@@ -161,8 +162,7 @@ def components(slot0: torch.Tensor, slot1: torch.Tensor, U: int) -> torch.Tensor
     dev = slot0.device
     parent = torch.arange(U, dtype=torch.int32, device=dev)
     labels = torch.empty(U, dtype=torch.int64, device=dev)
-    call("opstr_components", hip.ptr(slot0, torch.int64), hip.ptr(slot1, torch.int64), slot0.numel(), U, hip.ptr(parent, torch.int32),
-         hip.ptr(labels, torch.int64), hip.stream_handle())
+    launch("opstr_components", dict(slot0=slot0, slot1=slot1, T=slot0.numel(), U=U, parent=parent, labels=labels))
     return labels
 
 
@@ -175,7 +175,7 @@ def triangulate(merged: dict, cameras: dict, **options) -> dict:
     d = check_inputs(merged, cameras)
     I, U = d["I"], d["U"]
     dev = merged["keypoints"].device
-    Pt, S, i32, i64, f64 = hip.ptr, hip.stream_handle(), torch.int32, torch.int64, torch.float64
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
     K, R, t = (cameras[k].contiguous() for k in ("K", "R", "t"))
     ko = merged["kpt_offsets"].contiguous()
     slot_image = d["slot_image"]
@@ -183,7 +183,7 @@ def triangulate(merged: dict, cameras: dict, **options) -> dict:
     labels = components(d["slot0"], d["slot1"], U)
     cams = torch.empty(I, CAMERA_DOUBLES, dtype=f64, device=dev)
     dirs = torch.empty(U, 3, dtype=f64, device=dev)
-    call("opstr_prepare", Pt(K, f64), Pt(R, f64), Pt(t, f64), Pt(xys, f64), Pt(slot_image, i64), I, U, Pt(cams, f64), Pt(dirs, f64), S)
+    launch("opstr_prepare", dict(K=K, R=R, t=t, xys=xys, slot_image=slot_image, I=I, U=U, cameras=cams, dirs=dirs))
     assigned = torch.full((U,), -1, dtype=i64, device=dev)            # the round-local point number of every slot
     cos_min = math.cos(math.radians(o["min_tri_angle"]))
     kept_xyz, kept_err, kept_min, kept_num = [], [], [], []
@@ -208,10 +208,11 @@ def triangulate(merged: dict, cameras: dict, **options) -> dict:
         min_slot = torch.full((C,), -1, dtype=i64, device=dev)
         nbytes = load().opstr_workspace_bytes(n_elems) if n_long else 0
         ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
-        call("opstr_round", Pt(offsets, i64), Pt(comp_label.contiguous(), i64), Pt(elem_slot, i64), Pt(long_comps, i64) if n_long else None, C,
-             n_long, n_elems, Pt(slot_image, i64), Pt(xys, f64), Pt(cams, f64), Pt(dirs, f64), I, U, rnd, float(o["max_reproj_error"]), cos_min,
-             int(o["max_hypotheses"]), int(o["refine_steps"]), base, Pt(ws, None), nbytes, Pt(ok, i32), Pt(xyz, f64), Pt(err, f64),
-             Pt(min_slot, i64), Pt(assigned, i64), S)
+        launch("opstr_round", dict(comp_offsets=offsets, comp_label=comp_label.contiguous(), elem_slot=elem_slot,
+                                   long_comps=long_comps if n_long else None, C=C, n_long=n_long, n_elems=n_elems, slot_image=slot_image, xys=xys,
+                                   cameras=cams, dirs=dirs, I=I, U=U, round=rnd, max_reproj_error=o["max_reproj_error"], cos_min_tri_angle=cos_min,
+                                   max_hypotheses=o["max_hypotheses"], refine_steps=o["refine_steps"], point_base=base, workspace=ws,
+                                   workspace_bytes=nbytes, ok=ok, xyz=xyz, point_error=err, min_slot=min_slot, assigned=assigned))
         keep = torch.nonzero(ok).squeeze(1)
         if keep.numel() == 0:                                            # read-back: the points this round added
             break

@@ -26,6 +26,7 @@ from .lazy_conf import LazyConfMatrixBase
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call, order = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call, _BINDING.order
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 BLOCK, MAX_BATCH, MAX_ROWS, OK, NONE, FORCED, EMPTY = map(_BINDING.constant, ("BLOCK", "MAX_BATCH", "MAX_ROWS", "OK", "NONE", "FORCED", "EMPTY"))
@@ -131,17 +132,15 @@ def ground_truth(keypoints3d, point_ids, pose_gt, K, image_hw, *, counts=None, r
     hw_c = (H // s, W // s)
     M = hw_c[0] * hw_c[1]
     point_ids, counts = point_ids.contiguous(), None if counts is None else counts.contiguous()
-    P, S = hip.ptr, hip.stream_arg(stream)
     with hip.enqueue_on(dev, stream):
         owner = torch.empty(B, M, dtype=torch.int32, device=dev)
         gt_j = torch.empty(B, N, dtype=torch.int64, device=dev)
         gt_xy = torch.empty(B, N, 2, dtype=torch.float32, device=dev)
         gt_i = torch.empty(B, M, dtype=torch.int64, device=dev)
         n_gt = torch.empty(B, dtype=torch.int32, device=dev)
-        _BINDING.call_named("opsup_ground_truth", keypoints3d=P(keypoints3d), kp_bstride=hip.bstride(keypoints3d),
-                            point_ids=P(point_ids, torch.int64), counts=P(counts, torch.int32), pose_gt=P(pose), K=P(Kf),
-                            k_shared=int(Kf.dim() == 2), B=B, N=N, A=A, H=H, W=W, stride=s, owner=P(owner, torch.int32),
-                            gt_j=P(gt_j, torch.int64), gt_xy=P(gt_xy), gt_i=P(gt_i, torch.int64), n_gt=P(n_gt, torch.int32), stream=S)
+        launch("opsup_ground_truth", dict(keypoints3d=keypoints3d, kp_bstride=hip.bstride(keypoints3d), point_ids=point_ids, counts=counts,
+                                          pose_gt=pose, K=Kf, k_shared=Kf.dim() == 2, B=B, N=N, A=A, H=H, W=W, stride=s, owner=owner, gt_j=gt_j,
+                                          gt_xy=gt_xy, gt_i=gt_i, n_gt=n_gt), stream)
     return GroundTruth(gt_j, gt_xy, gt_i, n_gt, hw_c, keep=(keypoints3d, point_ids, counts, pose, Kf, owner))
 
 
@@ -169,12 +168,10 @@ def fine_targets(b_ids, i_ids, j_ids, gt: GroundTruth, w_c, *, count=None, resol
         raise ValueError(f"out: float32 [{cap}, 2], contiguous")
     if cap == 0:                                            # nothing to launch (and empty tensors have no address to hand over)
         return out
-    P = hip.ptr
     with hip.enqueue_on(dev, stream):
-        _BINDING.call_named("opsup_fine_targets", b_ids=P(b_ids.contiguous(), torch.int64), i_ids=P(i_ids.contiguous(), torch.int64),
-                            j_ids=P(j_ids.contiguous(), torch.int64), count=P(count, torch.int32), cap=cap, gt_j=P(gt.gt_j, torch.int64),
-                            gt_xy=P(gt.gt_xy), B=B, N=N, w_c=int(w_c), coarse_res=int(resolution[0]), fine_res=int(resolution[1]),
-                            radius=int(radius), scale=P(scale), expec_f_gt=P(out), stream=hip.stream_arg(stream))
+        launch("opsup_fine_targets", dict(b_ids=b_ids.contiguous(), i_ids=i_ids.contiguous(), j_ids=j_ids.contiguous(), count=count, cap=cap,
+                                          gt_j=gt.gt_j, gt_xy=gt.gt_xy, B=B, N=N, w_c=w_c, coarse_res=resolution[0], fine_res=resolution[1],
+                                          radius=radius, scale=scale, expec_f_gt=out), stream)
     return out
 
 
@@ -206,16 +203,13 @@ def coarse_loss(conf_matrix, gt: GroundTruth, *, alpha=0.25, gamma=2.0, pos_weig
         conf_matrix = conf_matrix.contiguous()
     B, N, M = gt.shape
     dev = conf_matrix.device
-    P = hip.ptr
     with hip.enqueue_on(dev, stream):
         partials = torch.empty(B * N + 1, 2, dtype=torch.float64, device=dev)
         sums = torch.empty(3, dtype=torch.float64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        _BINDING.call_named("opsup_coarse_loss", conf=P(conf_matrix), conf_bstride=int(conf_matrix.stride(0)),
-                            conf_rstride=int(conf_matrix.stride(1)), gt_j=P(gt.gt_j, torch.int64), B=B, N=N, M=M, alpha=float(alpha),
-                            gamma=float(gamma), pos_weight=float(pos_weight), neg_weight=float(neg_weight),
-                            partials=P(partials, torch.float64), sums=P(sums, torch.float64), counts=P(counts, torch.int64),
-                            stream=hip.stream_arg(stream))
+        launch("opsup_coarse_loss", dict(conf=conf_matrix, conf_bstride=conf_matrix.stride(0), conf_rstride=conf_matrix.stride(1), gt_j=gt.gt_j,
+                                         B=B, N=N, M=M, alpha=alpha, gamma=gamma, pos_weight=pos_weight, neg_weight=neg_weight,
+                                         partials=partials, sums=sums, counts=counts), stream)
     return CoarseLoss(sums, counts, keep=(conf_matrix, gt, partials))
 
 
@@ -236,13 +230,11 @@ def fine_loss(expec_f, expec_f_gt, *, count=None, correct_thr=1.0, training=Fals
     count = devargs.count_arg(count, dev)
     expec_f, expec_f_gt, count, _ = devargs.at_least_one_row(expec_f.contiguous(), expec_f_gt.contiguous(), count)
     cap = int(expec_f.shape[0])
-    P = hip.ptr
     with hip.enqueue_on(dev, stream):
         loss_f = torch.empty(1, dtype=torch.float64, device=dev)
         n_correct, status = (torch.empty(1, dtype=torch.int32, device=dev) for _ in range(2))
-        _BINDING.call_named("opsup_fine_loss", expec_f=P(expec_f), expec_f_gt=P(expec_f_gt), count=P(count, torch.int32), cap=cap,
-                            correct_thr=float(correct_thr), training=int(bool(training)), loss_f=P(loss_f, torch.float64),
-                            n_correct=P(n_correct, torch.int32), status=P(status, torch.int32), stream=hip.stream_arg(stream))
+        launch("opsup_fine_loss", dict(expec_f=expec_f, expec_f_gt=expec_f_gt, count=count, cap=cap, correct_thr=correct_thr,
+                                       training=bool(training), loss_f=loss_f, n_correct=n_correct, status=status), stream)
     return loss_f, n_correct, status
 
 

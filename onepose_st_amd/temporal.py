@@ -23,6 +23,7 @@ from . import cabi, devargs, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 (DEGENERATE, OUT_OF_IMAGE, FB_FAIL, BAD_INPUT, FLAG_MAX_ITERS, LOST,
@@ -76,7 +77,7 @@ def build_pyramid(frame_u8: torch.Tensor, levels: int = DEFAULTS["levels"], stre
         raise ValueError(f"levels={levels} for a {H} x {W} frame: levels in [1, {MAX_LEVELS}], sides in [2, 16384], the smallest level at least 2 x 2")
     frame_u8 = frame_u8.contiguous()
     data = torch.empty(nbytes, dtype=torch.uint8, device=frame_u8.device)
-    call("optmp_pyramid", hip.ptr(frame_u8, torch.uint8), H, W, int(levels), hip.ptr(data, None), nbytes, hip.stream_arg(stream))
+    launch("optmp_pyramid", dict(frame=frame_u8, H=H, W=W, levels=levels, pyramid=data, pyramid_bytes=nbytes), stream)
     return Pyramid(data, H, W, int(levels))
 
 
@@ -122,11 +123,10 @@ def track(src: Pyramid, dst: Pyramid, pts, *, count=None, guess=None, pts_3d=Non
                      torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.float64, device=dev))
     elif (tuple(out.pts.shape), tuple(out.flags.shape), tuple(out.iterations.shape), tuple(out.fb_error.shape)) != ((cap, 2), (cap,), (cap,), (cap,)):
         raise ValueError(f"out: Tracks of {cap} rows")
-    P = hip.ptr
-    call("optmp_track", P(src.data, None), P(dst.data, None), src.H, src.W, src.levels, P(pts, torch.float64), P(count, torch.int32), cap,
-         P(guess, torch.float64), P(pts_3d), P(pose, torch.float64), P(K, torch.float64), float(scale), int(window), int(max_iters), float(eps),
-         float(min_eig), -1.0 if fb_threshold is None else float(fb_threshold), P(out.pts, torch.float64), P(out.flags, torch.int32),
-         P(out.iterations, torch.int32), P(out.fb_error, torch.float64), hip.stream_arg(stream))
+    launch("optmp_track", dict(src=src.data, dst=dst.data, H=src.H, W=src.W, levels=src.levels, pts=pts, count=count, cap=cap, guess=guess,
+                               pts_3d=pts_3d, pose=pose, K=K, scale=scale, window=window, max_iters=max_iters, eps=eps, min_eig_threshold=min_eig,
+                               fb_threshold=-1.0 if fb_threshold is None else fb_threshold, out_pts=out.pts, flags=out.flags,
+                               iterations=out.iterations, fb_error=out.fb_error), stream)
     out.count = count
     out._keep = (src, dst, pts, guess, pts_3d, pose, K)
     return out
@@ -147,9 +147,8 @@ def collect(pts_2d, pts_3d, trans, *, count=None, mask=None, stream=None) -> Que
     trans, count = devargs.mat64("trans", trans, [(3, 3)], dev), devargs.count_arg(count, dev)
     out = Queries(torch.empty(cap, 2, dtype=torch.float64, device=dev), torch.empty(cap, 3, dtype=torch.float32, device=dev),
                   torch.empty(1, dtype=torch.int32, device=dev), keep=(pts_2d, pts_3d, mask, trans, count))
-    P = hip.ptr
-    call("optmp_collect", P(pts_2d), P(pts_3d), P(count, torch.int32), cap, P(mask, torch.uint8), P(trans, torch.float64),
-         P(out.pts, torch.float64), P(out.pts_3d), P(out.count, torch.int32), hip.stream_arg(stream))
+    launch("optmp_collect", dict(pts_2d=pts_2d, pts_3d=pts_3d, count=count, cap=cap, mask=mask, trans=trans, pts_orig=out.pts, out_3d=out.pts_3d,
+                                 out_count=out.count), stream)
     return out
 
 
@@ -191,10 +190,9 @@ def inject(own_2d, own_3d, own_count, sources, trans, *, stream=None):
     a_pts, a_3d, a_flags = table([tr.pts for _, tr in sources]), table([q.pts_3d for q, _ in sources]), table([tr.flags for _, tr in sources])
     a_count = table([tr.count for _, tr in sources])
     a_cap = (ctypes.c_int * max(n, 1))(*caps)
-    P = hip.ptr
-    call("optmp_inject", P(own_2d), P(own_3d), P(own_count, torch.int32), cap_own, a_pts, a_3d, a_flags, a_count,
-         ctypes.cast(a_cap, ctypes.c_void_p), n, P(trans, torch.float64), P(out_2d), P(out_3d), P(out_count, torch.int32), cap_total,
-         hip.stream_arg(stream))
+    launch("optmp_inject", dict(own_2d=own_2d, own_3d=own_3d, own_count=own_count, cap_own=cap_own, src_pts=a_pts, src_3d=a_3d, src_flags=a_flags,
+                                src_count=a_count, src_cap=ctypes.cast(a_cap, ctypes.c_void_p), n_sources=n, trans=trans, out_2d=out_2d,
+                                out_3d=out_3d, out_count=out_count, cap_total=cap_total), stream)
     return out_2d, out_3d, out_count
 
 

@@ -26,6 +26,7 @@ from . import cabi, hip
 
 _BINDING = cabi.Binding.of(__name__)                # the header is the one place a signature or a constant is written
 library_path, load, check_arity, call = _BINDING.library_path, _BINDING.load, _BINDING.check_arity, _BINDING.call
+launch = hip.launcher(_BINDING, globals())          # every stream-taking entry is called through it, by the header's parameter names
 EXPORTED_SYMBOLS = _BINDING.exported_symbols
 ABI_VERSION = _BINDING.abi_version
 LOST_POSE, LOST_BOX, STALE, NEEDS_HOST, MAX_BOX_SIDE, MAX_CROP = map(_BINDING.constant, (
@@ -94,10 +95,8 @@ def set_box(bbox, K, crop_size: int = 512, device=None) -> TrackState:
         device = K.device
     Kd = _device_K(K, device)
     st = TrackState(Kd.device)
-    P = hip.ptr
     with hip.enqueue_on(Kd.device):
-        call("optrk_box_set", x0, y0, x1, y1, P(Kd, torch.float64), S, P(st.box, torch.int32), P(st.flag, torch.int32), P(st.K_crop, torch.float64),
-             P(st.trans, torch.float64), hip.stream_handle())
+        launch("optrk_box_set", dict(x0=x0, y0=y0, x1=x1, y1=y1, K=Kd, S=S, box=st.box, flag=st.flag, K_crop=st.K_crop, trans=st.trans))
     return st
 
 
@@ -123,11 +122,10 @@ def next_box(poses, prev_state: TrackState, K, bbox3d, *, frame: int = 0, min_in
     pose = poses.pose[frame].contiguous()
     n_in, status = poses.n_inliers[frame:frame + 1], poses.status[frame:frame + 1]
     st = TrackState(Kd.device)                           # no reference to the inputs: a chain of states must not keep every solve's workspace
-    P = hip.ptr
     with hip.enqueue_on(Kd.device):
-        call("optrk_box_from_pose", P(Kd, torch.float64), P(pose, torch.float64), P(n_in, torch.int32), P(status, torch.int32), P(bbox3d, torch.float64),
-             P(prev_state.box, torch.int32), P(prev_state.flag, torch.int32), int(min_inliers), S, P(st.box, torch.int32), P(st.flag, torch.int32),
-             P(st.K_crop, torch.float64), P(st.trans, torch.float64), hip.stream_handle())
+        launch("optrk_box_from_pose", dict(K=Kd, pose=pose, n_inliers=n_in, status=status, bbox3d=bbox3d, prev_box=prev_state.box,
+                                           prev_flag=prev_state.flag, min_inliers=min_inliers, S=S, box=st.box, flag=st.flag, K_crop=st.K_crop,
+                                           trans=st.trans))
     return st
 
 
@@ -140,6 +138,5 @@ def crop(frame_u8: torch.Tensor, state: TrackState, crop_size: int = 512) -> tor
     frame_u8 = frame_u8.contiguous()
     out = torch.empty(1, 1, S, S, dtype=torch.float32, device=frame_u8.device)
     with hip.enqueue_on(frame_u8.device):
-        call("optrk_crop", hip.ptr(frame_u8, torch.uint8), frame_u8.shape[0], frame_u8.shape[1], hip.ptr(state.box, torch.int32), S, hip.ptr(out),
-             hip.stream_handle())
+        launch("optrk_crop", dict(image=frame_u8, H=frame_u8.shape[0], W=frame_u8.shape[1], box=state.box, S=S, out=out))
     return out
