@@ -2,7 +2,7 @@
 library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures, the constants and the loaded
 handle of one HIP library.  The headers are the only place a C signature or a constant is written; the modules ``LIBRARIES`` names and
 ``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES`` or, with its header under ``include/ext/``, of
-``EXTENSIONS`` or ``ADDONS``; the host library alone keeps a loader of its own (``pnp.py``).
+``EXTENSIONS``, ``ADDONS`` or ``TRAINING``; the host library alone keeps a loader of its own (``pnp.py``).
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -44,6 +44,8 @@ EXTENSIONS = (Library("opfcx", "ext/onepose_fine_context.h", "libonepose_fine_co
 # Libraries beside the inference path (training and validation signals): rows like those of ``EXTENSIONS`` in every respect, kept apart
 # because that table is the LoFTR matcher's.
 ADDONS = (Library("opsup", "ext/onepose_supervision.h", "libonepose_supervision.so", "OPSUP_LIB", "supervision"),)
+# The training-mode forward's own step: a row like those of ``ADDONS``, in a table of its own because that one is held to its one row.
+TRAINING = (Library("optrn", "ext/onepose_train_forward.h", "libonepose_train_forward.so", "OPTRN_LIB", "train_forward"),)
 
 
 def names_of(*prefixes: str) -> str:
@@ -174,8 +176,8 @@ class Binding:
 
     @classmethod
     def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
-        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, or ``ADDONS``) entry whose module is ``module`` (a ``__name__``)"""
-        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS if e.module == module.rpartition(".")[2]]
+        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, ``ADDONS``, ``TRAINING``) entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS + TRAINING if e.module == module.rpartition(".")[2]]
         return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors, None if entry in LIBRARIES else names_of(entry.prefix))
 
     @property

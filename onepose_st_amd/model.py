@@ -29,7 +29,7 @@ from collections import namedtuple
 import torch
 import torch.nn as nn
 
-from . import hip, host_math, layercall, ops, packing
+from . import hip, host_math, layercall, ops, packing, supervision, train_forward
 from .backbone import build_backbone
 from .backbone_hip import HipBackbone, pack_backbone
 from .config import encoder_layer_names, validate_config
@@ -198,6 +198,12 @@ class OnePosePlus_model(nn.Module):
         self._plan_ids = set()
         weakref.finalize(self, ops.drop_frame_plans, self._plan_ids)
         self._frame_call_pending = set()     # compute streams whose last frame went through the C entry point
+        # the training-mode forward (off: a training-mode call raises): the eval forward stage by stage on the current
+        # stream with conf_matrix stored, and between its coarse and fine stages the reference's GT padding (train_forward.pad_matches).
+        # Its draws are (hip_train_seed, train_calls): the model counts its training calls; reseed() sets both.
+        self.train_forward = bool(config.get("hip_train_forward", False))
+        self.train_seed = int(config.get("hip_train_seed", 0))
+        self.train_calls = 0
 
         pretrained = config["loftr_backbone"]["pretrained"]
         if pretrained is not None:
@@ -309,14 +315,14 @@ class OnePosePlus_model(nn.Module):
     def enqueue(self, data, host_copy=False):
         """``forward`` without the final wait: backbone + rows a1-a11 enqueued on the current stream; returns the
         :class:`PendingFrame` (see :meth:`enqueue_features`)."""
-        if self.training:
+        if self.training and not self.train_forward:
             raise NotImplementedError("the HIP path implements inference; call .eval() (training padding "
                                       "of coarse_matching.py:177-217 is out of scope)")
         if "mask0" in data:
             raise NotImplementedError("data['mask0']: not implemented (the reference raises as well, coarse_matching.py:149-152)")
         data.update({"bs": data["query_image"].size(0), "q_hw_i": data["query_image"].shape[2:]})
         img = data["query_image"]
-        if self.hip_backbone:
+        if self.hip_backbone and not self.training:          # training: torch's BatchNorm in training mode is the reference's; the folded-BN convolutions are eval arithmetic
             feat_c, feat_f = self.backbone_features(img)
             return self.enqueue_features(data, feat_c, feat_f, host_copy=host_copy, _pe_applied=True)
         with torch.no_grad():
@@ -355,6 +361,8 @@ class OnePosePlus_model(nn.Module):
         fi = self._frame_inputs(data, feat_c, feat_f, image_hw)
         main = _current_stream(fi.dev)
         fkey = (str(fi.dev), main.cuda_stream)
+        if self.training and self.train_forward:
+            return self._enqueue_training(data, feat_c, feat_f, fi, main, fkey, want_fine_debug, host_copy, _pe_applied)
         lazy = self.conf_matrix_mode == "lazy" and not _force_eager
         # a lazy frame whose selection meets an exact row tie it cannot resolve without the stored row is run again with conf_matrix
         rerun = (lambda: self.enqueue_features(data, feat_c, feat_f, image_hw, want_fine_debug, host_copy, _pe_applied, False, True)) if lazy else None
@@ -375,6 +383,56 @@ class OnePosePlus_model(nn.Module):
         pend = self._fine_stage(data, fi, cb, select, ff, ff_strides, main, fkey, want_fine_debug, host_copy)      # a9-a11
         pend._rerun = rerun
         return pend
+
+    def reseed(self, seed, calls=0):
+        """The training-mode forward's sampler: ``hip_train_seed`` and the call counter ``train_calls`` (the ``step`` of the next call)"""
+        self.train_seed, self.train_calls = int(seed), int(calls)
+
+    def _enqueue_training(self, data, feat_c, feat_f, fi, main, fkey, want_fine_debug, host_copy, _pe_applied):
+        """The training-mode forward (``hip_train_forward``; OnePosePlusModel.py:95-203 with ``self.training``): the stages of the eval
+        forward, all on the current stream (``hip_overlap_fine`` is ignored, the frame call never used), ``conf_matrix`` stored (the loss
+        reads it), the coarse stage with its whole selection, and with ``coarse_matching.train.train_padding`` the reference's cut and GT
+        padding (coarse_matching.py:174-217) into buffers of the host-known capacity ``T``, over which the fine stage then runs.  Without
+        the padding the eval lists are returned as they are."""
+        if "mask0" in data:
+            raise NotImplementedError("data['mask0']: not implemented (the reference raises as well, coarse_matching.py:149-152)")
+        if fkey in self._frame_call_pending:                          # order this frame's encoder behind the C path's last fine stage
+            self._frame_call_pending.discard(fkey)
+            hip.call("ophip_frame_order_after_fine", ctypes.c_void_p(main.cuda_stream))
+        step, self.train_calls = self.train_calls, self.train_calls + 1
+        x2d, x3d, ff, ff_strides = self._input_stage(fi, feat_c, feat_f, main, fkey, _pe_applied, False)
+        x3d, x2d = self._coarse_encoder_stage(fi, x3d, x2d, main, fkey)
+        if self.debug:
+            data["_feat3d_c"], data["_feat2d_c"] = x3d, x2d
+        cb, _ = self._coarse_matching_stage(data, fi, x3d, x2d, main, False, overlap=False)
+        padded = bool(self.config["coarse_matching"]["train"]["train_padding"])
+        if padded:
+            cb = self._train_padding_stage(data, fi, cb, step)
+        pend = self._fine_stage(data, fi, cb, None, ff, ff_strides, main, fkey, want_fine_debug, host_copy, overlap=False)
+        pend.padded = padded
+        return pend
+
+    def _train_padding_stage(self, data, fi, cb, step):
+        """``train_forward.pad_matches`` behind the coarse stage's buffers ``cb``, on the current stream -> the same dictionary over buffers of
+        capacity ``T``.  The block the host reads back holds ``T``'s count, ``n_keep`` and ``status`` in its first 16 bytes."""
+        B, N, M, dev = fi.B, fi.N, fi.M, fi.dev
+        tr = self.config["coarse_matching"]["train"]
+        T, G = train_forward.train_rows(B, N, M, tr["train_coarse_percent"]), int(tr["train_pad_num_gt_min"])
+        gt = supervision._ground_truth_of(data)
+        if tuple(gt.shape) != (B, N, M):
+            raise ValueError(f"the ground truth is of [B, N, M] = {list(gt.shape)}, the frame of {[B, N, M]}")
+        f32, i64 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int64)
+        rows = max(T, 1)
+        blob, count, b_ids, mk3d, mk2d = _result_views(torch.empty(16 + 28 * rows, dtype=torch.uint8, device=dev), rows)
+        n_keep, status = blob[8:12].view(torch.int32), blob[12:16].view(torch.int32)
+        fine_on = bool(self.config["fine_matching"]["enable"])
+        out = MatchLists(b_ids, torch.empty(rows, **i64), torch.empty(rows, **i64), torch.empty(rows, **f32), mk3d,
+                         torch.empty(rows, 2, **f32) if fine_on else mk2d, b_ids, torch.empty(rows, device=dev, dtype=torch.bool), count)
+        pred = MatchLists(cb["b_ids"], cb["i_ids"], cb["j_ids"], cb["mconf"], cb["mk3d"], cb["mkc"], None, None, cb["count"])
+        done = train_forward.pad_matches(pred, gt, fi.kpts_d, T=T, G=G, seed=self.train_seed, step=step, w_c=fi.wc, scale=data["q_hw_i"][0] / fi.hc,
+                                         query_scale=fi.qscale, out=out, n_keep=n_keep, status=status)
+        return dict(blob=blob, b_ids=out.b_ids, i_ids=out.i_ids, j_ids=out.j_ids, mconf=out.mconf, mk3d=mk3d, mk2d=mk2d, mkc=out.mkc, count=count,
+                    m_bids=out.b_ids, gt_mask=out.gt_mask, cap=rows, held=(*cb["held"], cb, done))
 
     def _frame_inputs(self, data, feat_c, feat_f, image_hw):
         """Check one call's inputs and gather them as a :class:`FrameInputs`; fills the ``bs`` / ``q_hw_*`` keys of ``data``."""
@@ -530,7 +588,7 @@ class OnePosePlus_model(nn.Module):
             x3d, y3d, x2d, y2d = y3d, (z3d if li == 0 else x3d), y2d, x2d
         return x3d, x2d
 
-    def _coarse_matching_stage(self, data, fi, x3d, x2d, main, lazy):
+    def _coarse_matching_stage(self, data, fi, x3d, x2d, main, lazy, overlap=None):
         """Rows a7 + a8 on the compute stream; sets ``data["conf_matrix"]``.  Returns the stage's buffers (read-only from here on; ``held``: what
         must stay referenced until ``finish()``) and ``select``: with the fine stage on its side stream the single-workgroup select kernel goes there with it (it only feeds that stage
         and the read-back: the next frame's input kernels then run beside it, not behind it) -- ``select(stream)`` launches it; else None."""
@@ -550,7 +608,7 @@ class OnePosePlus_model(nn.Module):
         scale = data["q_hw_i"][0] / fi.hc
         temperature = float(cm["dual_softmax"]["temperature"])
         lists = MatchLists(b_ids, i_ids, j_ids, mconf, mk3d, mkc, m_bids, gt_mask, count)
-        split_select = fine_on and self.overlap_fine
+        split_select = fine_on and (self.overlap_fine if overlap is None else overlap)      # (the training-mode forward: all on one stream)
 
         def match(parts, stream):
             coarse_match(x3d, x2d, kpts_d, wc=fi.wc, temperature=temperature, thr=cm["thr"], border_rm=cm["border_rm"], scale=scale,
@@ -563,7 +621,7 @@ class OnePosePlus_model(nn.Module):
         return dict(blob=blob, b_ids=b_ids, i_ids=i_ids, j_ids=j_ids, mconf=mconf, mk3d=mk3d, mk2d=mk2d, mkc=mkc, count=count, m_bids=m_bids,
                     gt_mask=gt_mask, held=(x3d, x2d, cws, conf)), select
 
-    def _fine_stage(self, data, fi, cb, select, ff, ff_strides, main, fkey, want_fine_debug, host_copy):
+    def _fine_stage(self, data, fi, cb, select, ff, ff_strides, main, fkey, want_fine_debug, host_copy, overlap=None):
         """Rows a9-a11 on the coarse stage's buffers ``cb`` (behind the kept-back selection ``select``) and the frame's :class:`PendingFrame`.  With ``hip_overlap_fine`` they run on
         the compute stream's fine stream, behind an event of the coarse stage, and leave the event the next frame's encoder waits for.  The grid
         is sized by the capacity B * N (one match per 3D point at most; surplus workgroups exit on the device-side count): no sync yet."""
@@ -571,9 +629,9 @@ class OnePosePlus_model(nn.Module):
         cfg = self.config
         fine_on = bool(cfg["fine_matching"]["enable"])
         f32 = dict(device=dev, dtype=torch.float32)
-        cap = B * N
+        cap = cb.get("cap", B * N)                    # (the training-mode forward's padded lists: T)
         fine_ctx, fine_entry = contextlib.nullcontext(), None
-        if fine_on and self.overlap_fine:
+        if fine_on and (self.overlap_fine if overlap is None else overlap):
             fine_entry = _side_stream(self._fine_streams, fkey, dev, with_event=True)
             coarse_done = torch.cuda.Event()
             coarse_done.record(main)
@@ -619,7 +677,7 @@ class OnePosePlus_model(nn.Module):
         FineMatching on the one 3D token per match into ``expec`` and ``cb["mk2d"]``.  Every row count is the capacity: the kernels read the device-side count.  Returns the
         encoder's output rows (windows [cap, 25, 128], 3D tokens [cap, 128])."""
         f32 = dict(device=fi.dev, dtype=torch.float32)
-        desc, cap, cnt = fi.desc_fine_d, fi.B * fi.N, cb["count"]
+        desc, cap, cnt = fi.desc_fine_d, cb.get("cap", fi.B * fi.N), cb["count"]
         WS, WW = 5, 25
         win, f3 = torch.empty(cap, WW, 128, **f32), torch.empty(cap, 128, **f32)
         hip.launch("ophip_fine_full_gather", dict(zip(("fs_b", "fs_c", "fs_y", "fs_x"), ff_strides), feat_f=ff, hf=fi.hf, wf=fi.wf, desc3d_f=desc,
@@ -843,6 +901,7 @@ class PendingFrame:
         self._key, self._host_copy = key, bool(host_copy)
         self._slot = None
         self._rerun = None
+        self.padded = False         # the training-mode forward's padded lists: the block's first 16 bytes hold n_keep and status too
         # the D2H of the result block runs on a side stream behind an event: on the compute stream the PCIe round trip
         # (~40 us per frame) would sit between this frame's last kernel and the next frame's first one
         main = torch.cuda.current_stream(dev)
@@ -872,6 +931,7 @@ class PendingFrame:
         self._pin, self._key, self._host_copy = pin, (cap, bool(host_copy)), bool(host_copy)
         self.event = None
         self._rerun = None
+        self.padded = False
         self.done = False
         return self
 
@@ -941,9 +1001,18 @@ class PendingFrame:
             self.host = again.host
             return self.data
         B, N, M, cap = self.B, self.N, self.M, self.cap
+        n_keep = K
+        if self.padded:
+            # coarse_matching.py:231-239, fine_matching.py:105: the ids, gt_mask and expec_f keep all T rows, the prediction's keys the
+            # n_keep predicted rows
+            n_keep, status = (int(v) for v in self._pin[8:16].view(torch.int32))
+            if status == train_forward.NO_GT:
+                self._release_pin()
+                self.done = True
+                raise ValueError("no ground-truth match in the batch")
         if self._host_copy:
             _, _, hb, h3, h2 = _result_views(self._pin, cap)
-            self.host = {"K": K, "mkpts_3d_db": h3[:K].numpy().copy(), "mkpts_2d": h2[:K].numpy().copy(), "b_ids": hb[:K].numpy().copy()}
+            self.host = {"K": n_keep, "mkpts_3d_db": h3[:n_keep].numpy().copy(), "mkpts_2d": h2[:n_keep].numpy().copy(), "b_ids": hb[:n_keep].numpy().copy()}
             if on_host is not None:
                 on_host(self.host)
         self._release_pin()
@@ -952,10 +1021,10 @@ class PendingFrame:
         bf = self.bufs
         data, dev = self.data, self.dev
         b_ids, i_ids, j_ids = bf["b_ids"][:K], bf["i_ids"][:K], bf["j_ids"][:K]
-        mconf, mk3d, mkc = bf["mconf"][:K], bf["mk3d"][:K], bf["mkc"][:K]
+        mconf, mk3d, mkc = bf["mconf"][:n_keep], bf["mk3d"][:n_keep], bf["mkc"][:n_keep]
         data.update({
             "b_ids": b_ids, "i_ids": i_ids, "j_ids": j_ids,
-            "gt_mask": bf["gt_mask"][:K], "m_bids": bf["m_bids"][:K],
+            "gt_mask": bf["gt_mask"][:K], "m_bids": bf["m_bids"][:n_keep],
             "mkpts_3d_db": mk3d, "mkpts_query_c": mkc, "mconf": mconf,
         })
         self.done = True
@@ -966,7 +1035,7 @@ class PendingFrame:
         if K == 0:
             data.update({"expec_f": torch.empty(0, 3, device=dev), "mkpts_3d_db": mk3d, "mkpts_query_f": mkc})
             return data
-        data.update({"expec_f": bf["expec"][:K], "mkpts_3d_db": mk3d, "mkpts_query_f": bf["mkf"][:K]})
+        data.update({"expec_f": bf["expec"][:K], "mkpts_3d_db": mk3d, "mkpts_query_f": bf["mkf"][:n_keep]})
         if self.want_dbg:
             data["_fine_win"], data["_fine_f3"] = bf["dbg_w"][:K], bf["dbg_3"][:K]
         return data
