@@ -2,7 +2,7 @@
 library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures, the constants and the loaded
 handle of one HIP library.  The headers are the only place a C signature or a constant is written; the modules ``LIBRARIES`` names and
 ``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES`` or, with its header under ``include/ext/``, of
-``EXTENSIONS``, ``ADDONS`` or ``TRAINING``; the host library alone keeps a loader of its own (``pnp.py``).
+``EXTENSIONS``, ``ADDONS``, ``TRAINING`` or ``BACKWARD``; the host library alone keeps a loader of its own (``pnp.py``).
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -46,6 +46,9 @@ EXTENSIONS = (Library("opfcx", "ext/onepose_fine_context.h", "libonepose_fine_co
 ADDONS = (Library("opsup", "ext/onepose_supervision.h", "libonepose_supervision.so", "OPSUP_LIB", "supervision"),)
 # The training-mode forward's own step: a row like those of ``ADDONS``, in a table of its own because that one is held to its one row.
 TRAINING = (Library("optrn", "ext/onepose_train_forward.h", "libonepose_train_forward.so", "OPTRN_LIB", "train_forward"),)
+# The backward of the training loss down to the matcher's feature boundaries: a row like those of ``ADDONS`` and ``TRAINING``, in a table of
+# its own because each of those two is held to its one row.
+BACKWARD = (Library("opbwd", "ext/onepose_loss_backward.h", "libonepose_loss_backward.so", "OPBWD_LIB", "loss_backward"),)
 
 
 def names_of(*prefixes: str) -> str:
@@ -176,8 +179,8 @@ class Binding:
 
     @classmethod
     def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
-        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, ``ADDONS``, ``TRAINING``) entry whose module is ``module`` (a ``__name__``)"""
-        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS + TRAINING if e.module == module.rpartition(".")[2]]
+        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, ``ADDONS``, ``TRAINING``, ``BACKWARD``) entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS + TRAINING + BACKWARD if e.module == module.rpartition(".")[2]]
         return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors, None if entry in LIBRARIES else names_of(entry.prefix))
 
     @property

@@ -204,6 +204,10 @@ class OnePosePlus_model(nn.Module):
         self.train_forward = bool(config.get("hip_train_forward", False))
         self.train_seed = int(config.get("hip_train_seed", 0))
         self.train_calls = 0
+        # the training-mode forward also leaves the four feature tensors the loss backward starts from (loss_backward.backward; DESIGN.md
+        # section 6u) in ``data``: feat_c0 / feat_c1 (the coarse encoder's outputs) and feat_f0 / feat_f1 (the fine encoder's, at the
+        # lists' capacity).  Off: no key of ``data`` changes and no buffer is allocated.
+        self.keep_features = bool(config.get("hip_keep_features", False))
 
         pretrained = config["loftr_backbone"]["pretrained"]
         if pretrained is not None:
@@ -408,8 +412,10 @@ class OnePosePlus_model(nn.Module):
         padded = bool(self.config["coarse_matching"]["train"]["train_padding"])
         if padded:
             cb = self._train_padding_stage(data, fi, cb, step)
-        pend = self._fine_stage(data, fi, cb, None, ff, ff_strides, main, fkey, want_fine_debug, host_copy, overlap=False)
-        pend.padded = padded
+        pend = self._fine_stage(data, fi, cb, None, ff, ff_strides, main, fkey, want_fine_debug or self.keep_features, host_copy, overlap=False)
+        pend.padded, pend.want_dbg = padded, want_fine_debug
+        if self.keep_features:
+            pend.kept = (x3d, x2d)
         return pend
 
     def _train_padding_stage(self, data, fi, cb, step):
@@ -902,6 +908,7 @@ class PendingFrame:
         self._slot = None
         self._rerun = None
         self.padded = False         # the training-mode forward's padded lists: the block's first 16 bytes hold n_keep and status too
+        self.kept = None            # hip_keep_features: the coarse encoder's outputs, written to data with the fine encoder's at finish()
         # the D2H of the result block runs on a side stream behind an event: on the compute stream the PCIe round trip
         # (~40 us per frame) would sit between this frame's last kernel and the next frame's first one
         main = torch.cuda.current_stream(dev)
@@ -932,6 +939,7 @@ class PendingFrame:
         self.event = None
         self._rerun = None
         self.padded = False
+        self.kept = None
         self.done = False
         return self
 
@@ -1028,6 +1036,10 @@ class PendingFrame:
             "mkpts_3d_db": mk3d, "mkpts_query_c": mkc, "mconf": mconf,
         })
         self.done = True
+        if self.kept is not None:
+            data["feat_c0"], data["feat_c1"] = self.kept
+            if self.fine_on:
+                data["feat_f0"], data["feat_f1"] = bf["dbg_3"], bf["dbg_w"]      # every row of the capacity: rows past the count are not written
         if not self.fine_on:
             data.update({"mkpts_3d_db": data["mkpts_3d_db"], "mkpts_query_f": data["mkpts_query_c"]})
             return data

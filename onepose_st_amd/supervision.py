@@ -8,7 +8,8 @@ SPARSE: a 3D point has at most one cell, so ``gt_j [B, N]`` and ``gt_xy [B, N, 2
 ``fine_location_matrix_gt`` hold (:meth:`GroundTruth.to_dense` / :meth:`GroundTruth.from_dense` for callers of reference code).  The focal
 loss is one streaming pass over ``conf_matrix`` with float64 sums in a fixed order: two runs give identical bytes.
 
-Not here: the backward pass, the homography augmentation (the training-mode forward and its random GT padding: ``train_forward.py``),
+Not here: the backward pass (the gradient of these losses at the matcher's four feature tensors is ``loss_backward.py``; the backward of
+the transformers, the window gather and the backbone behind them is not built), the homography augmentation (the training-mode forward and its random GT padding: ``train_forward.py``),
 ``mask0`` / ``mask1`` loss weights, an image scale other than 1 in :func:`ground_truth`, and a loss taken from the lazy ``conf_matrix``
 without making the matrix.
 

@@ -8,8 +8,8 @@ always has exactly ``T = train_rows(B, N, M, train_coarse_percent)`` rows, so ev
 the split between predicted and padded rows (``n_keep``) stays a device int.  The draws are a counter-based sampler of this project's own
 (``seed``, ``step``): they cannot equal ``torch.randint``'s stream; two calls with one ``(seed, step)`` give identical bytes.
 
-Not here: the backward pass, ``mask0``, and a dense ground truth with several entries in one row (``GroundTruth.from_dense`` keeps the
-first).
+Not here: the backward of the transformers, the window gather and the backbone (``loss_backward.py`` stops at their outputs), ``mask0``, and
+a dense ground truth with several entries in one row (``GroundTruth.from_dense`` keeps the first).
 
 The kernels are HIP (``csrc/train_forward.hip`` in ``libonepose_train_forward.so``, the row of ``cabi.TRAINING``).  CPU tensors raise
 :class:`hip.HipLibraryError` (no CPU fallback); nothing is synchronised and no count is read on the host.
