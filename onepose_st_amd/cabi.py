@@ -2,7 +2,7 @@
 library), the one rule that turns a C type into a ctypes class, and ``Binding``: the header, the signatures, the constants and the loaded
 handle of one HIP library.  The headers are the only place a C signature or a constant is written; the modules ``LIBRARIES`` names and
 ``pnp.py`` bind from what this reads.  Every HIP library is an entry of ``LIBRARIES`` or, with its header under ``include/ext/``, of
-``EXTENSIONS``, ``ADDONS``, ``TRAINING`` or ``BACKWARD``; the host library alone keeps a loader of its own (``pnp.py``).
+``EXTENSIONS``, ``ADDONS``, ``TRAINING``, ``BACKWARD`` or ``ENCODER_BACKWARD``; the host library alone keeps a loader of its own (``pnp.py``).
 
 Not a C parser: it reads the regular subset those headers use and raises ``HeaderError`` (with the line) on anything else that looks
 like an entry point.  Standard library only."""
@@ -49,6 +49,9 @@ TRAINING = (Library("optrn", "ext/onepose_train_forward.h", "libonepose_train_fo
 # The backward of the training loss down to the matcher's feature boundaries: a row like those of ``ADDONS`` and ``TRAINING``, in a table of
 # its own because each of those two is held to its one row.
 BACKWARD = (Library("opbwd", "ext/onepose_loss_backward.h", "libonepose_loss_backward.so", "OPBWD_LIB", "loss_backward"),)
+# The backward of the coarse transformer's encoder layer: the next consumer of what ``BACKWARD``'s row writes, in a table of its own because
+# that one too is held to its one row.
+ENCODER_BACKWARD = (Library("openb", "ext/onepose_encoder_backward.h", "libonepose_encoder_backward.so", "OPENB_LIB", "encoder_backward"),)
 
 
 def names_of(*prefixes: str) -> str:
@@ -179,8 +182,8 @@ class Binding:
 
     @classmethod
     def of(cls, module: str, mirrors: dict | None = None) -> "Binding":
-        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, ``ADDONS``, ``TRAINING``, ``BACKWARD``) entry whose module is ``module`` (a ``__name__``)"""
-        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS + TRAINING + BACKWARD if e.module == module.rpartition(".")[2]]
+        """The binding of the ``LIBRARIES`` (or ``EXTENSIONS``, ``ADDONS``, ``TRAINING``, ``BACKWARD``, ``ENCODER_BACKWARD``) entry whose module is ``module`` (a ``__name__``)"""
+        entry, = [e for e in LIBRARIES + EXTENSIONS + ADDONS + TRAINING + BACKWARD + ENCODER_BACKWARD if e.module == module.rpartition(".")[2]]
         return cls(entry.header, entry.so, entry.prefix, entry.env, mirrors, None if entry in LIBRARIES else names_of(entry.prefix))
 
     @property

@@ -208,6 +208,10 @@ class OnePosePlus_model(nn.Module):
         # section 6u) in ``data``: feat_c0 / feat_c1 (the coarse encoder's outputs) and feat_f0 / feat_f1 (the fine encoder's, at the
         # lists' capacity).  Off: no key of ``data`` changes and no buffer is allocated.
         self.keep_features = bool(config.get("hip_keep_features", False))
+        # the training-mode forward also keeps every coarse layer's inputs for the coarse transformer's backward (encoder_backward.coarse_backward;
+        # DESIGN.md section 6v): each layer then writes fresh buffers instead of the ping-pong pair, and ``data["layer_inputs_c"]`` is the list
+        # of ``(x3d, x2d)`` per layer.  Off: no key of ``data`` changes, no buffer is allocated, the same bytes come out.
+        self.keep_layer_inputs = bool(config.get("hip_keep_layer_inputs", False))
 
         pretrained = config["loftr_backbone"]["pretrained"]
         if pretrained is not None:
@@ -405,7 +409,10 @@ class OnePosePlus_model(nn.Module):
             hip.call("ophip_frame_order_after_fine", ctypes.c_void_p(main.cuda_stream))
         step, self.train_calls = self.train_calls, self.train_calls + 1
         x2d, x3d, ff, ff_strides = self._input_stage(fi, feat_c, feat_f, main, fkey, _pe_applied, False)
-        x3d, x2d = self._coarse_encoder_stage(fi, x3d, x2d, main, fkey)
+        layer_inputs = [] if self.keep_layer_inputs else None
+        x3d, x2d = self._coarse_encoder_stage(fi, x3d, x2d, main, fkey, layer_inputs)
+        if layer_inputs is not None:
+            data["layer_inputs_c"] = layer_inputs
         if self.debug:
             data["_feat3d_c"], data["_feat2d_c"] = x3d, x2d
         cb, _ = self._coarse_matching_stage(data, fi, x3d, x2d, main, False, overlap=False)
@@ -574,19 +581,26 @@ class OnePosePlus_model(nn.Module):
             hip.launch(entry, named, S)
         return launch
 
-    def _coarse_encoder_stage(self, fi, x3d, x2d, main, fkey):
+    def _coarse_encoder_stage(self, fi, x3d, x2d, main, fkey, layer_inputs=None):
         """Rows a4-a6 on the compute stream: the coarse encoder's layers over the 3D rows ``x3d`` and the 2D rows ``x2d``; returns the
         final ``(x3d, x2d)``.  It starts once the previous frame's fine stage is done: the two MFMA-heavy stages (attn_apply is the
-        roofline kernel) never share the chip."""
+        roofline kernel) never share the chip.  ``layer_inputs`` (a list; the training-mode forward with ``hip_keep_layer_inputs``): every
+        layer's ``(x3d, x2d)`` is appended and no buffer is written twice."""
         names = self.loftr_coarse.layer_names
         y3d, y2d = torch.empty_like(x3d), torch.empty_like(x2d)
-        z3d = torch.empty_like(x3d) if self.cache_object else x3d
+        z3d = torch.empty_like(x3d) if self.cache_object and layer_inputs is None else x3d      # (kept layer inputs: never used)
         prev = self._fine_streams.get(fkey)
         if (names or self.precision == "f32") and self.overlap_fine and prev is not None and prev[1] is not None:
             main.wait_event(prev[1])          # (the exact-f32 mode waits with no layer to run as well)
         launch = self._coarse_layer_launch(fi, main, (x3d, x2d, y3d, y2d))
         for li, name in enumerate(names):
             launch(li, name, x3d, x2d, y3d, y2d)
+            if layer_inputs is not None:      # the inputs stay as they are: the next layer reads these outputs and writes fresh buffers
+                layer_inputs.append((x3d, x2d))
+                x3d, x2d = y3d, y2d
+                if li < len(names) - 1:
+                    y3d, y2d = torch.empty_like(x3d), torch.empty_like(x2d)
+                continue
             # Ping-pong: the layer's outputs become the next layer's inputs, its inputs the next outputs.  The one invariant of this
             # function: a cached ``x3d`` (``hip_cache_object``: the object's entry, shared with later frames) is never an output buffer --
             # after layer 0 the 3D stream alternates between ``y3d`` and ``z3d``, which is a buffer of this frame's own when the encoding
