@@ -100,6 +100,16 @@ class Arena:
             f"region {name!r}: {side} it, bytes {first} .. {last} from its edge" for name, side, first, last in found)
 
 
+def arena_for(device, *nbytes: int) -> Arena:
+    """An arena with room for one region of each of ``nbytes`` bytes, guards and alignment included"""
+    return Arena(device, sum(int(n) for n in nbytes) + (len(nbytes) + 1) * (GUARD + 256))
+
+
+def is_fill(t: torch.Tensor, pattern: int = 0xFF) -> bool:
+    """every byte of ``t`` (a view of a region) still holds ``pattern``: as 0xFF, NaN in every float"""
+    return bool((t.contiguous().view(torch.uint8) == _pattern(pattern)).all())
+
+
 class _TorchView:
     """The ``torch`` a patched module sees: ``empty`` / ``empty_like`` replaced, everything else the real module's"""
 
